@@ -1,8 +1,13 @@
 #!/usr/bin/env python
 """bench.py -- the headline benchmark of the SpMV / SpMSpV-with-semiring hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: launched by torch.distributed.run, one rank per GPU, RCCL)
+
+A plain run sets up, warms up, times the K steps and prints the JSON line; `--dump-outputs DIR` also writes what the
+last timed step computed (the dense result y, float32) as DIR/y.npy, for comparing two builds output for output.
+Everything else -- the self-check, the roofline's HIP events, the extra legs below, the multi-GPU pre-flight -- runs
+with `--full` only.
 
 Workload (BASELINE.json `metric`): float32 (+,x) SpMV on the orkut stand-in (3 072 441 vertices,
 ~213 M edges, symmetrised R-MAT seed 6), prepared exactly as the reference's
@@ -15,13 +20,14 @@ x8, x in {0,1} (seeded).  A "step" is one pass of the hot path over the whole ma
 with the matrix, x and y resident in HBM before the timed region; wall time is bracketed by
 barrier + synchronize on both sides and MAX-reduced over ranks.
 
-Extra objects on the same JSON line:
+Extra objects on the same JSON line (`--full`):
   roofline      HBM roofline of the dominant kernel (spmv_rbcs_kernel): algorithmic bytes per launch /
                 its mean duration from HIP events recorded on the launch stream inside the timed region.
   cpu_baseline  the oracle's single-thread restatement of SpMVModule::compute_reference_results timed
                 on this host (rank 0, N = 1 only), same byte formula.
   bfs           BFS pull_push on the same graph (bench_bfs.cpp:68-89 definition: nnz * iters / t).
   host_buffers  the SpMV step with x uploaded and y downloaded over PCIe inside it (the module API's host vectors).
+  selfcheck_ok  the timed result against float64 on a sample of rows.
 """
 import argparse
 import json
@@ -37,6 +43,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBPS = 8000.0   # MI355X HBM3E spec peak (MI355X_MICROARCH.md: 8.0 TB/s; ~6.3 TB/s achievable)
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs: a larger y is written as a fixed, seeded sample of its rows
 
 
 def spmv_bytes(nnz, n_rows, n_cols, masked=False):
@@ -82,6 +89,12 @@ def main():
                          "recorded into the schedule's hipGraph) instead of torch.distributed")
     ap.add_argument("--force-dist", action="store_true",
                     help="with --gpus 1: still create the process group and run every collective (one-rank RCCL on one GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline: the self-check, the roofline (HIP events inside the timed region), the pattern-plan, "
+                         "host-buffer, BFS, SpMSpV, six-graph and CPU-baseline legs and, with N > 1, the exchange pre-flight")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the result y of the last one as DIR/y.npy (float32; above 64 MB a seeded "
+                         "sample of rows: DIR/y_sample.npy + DIR/y_sample_rows.npy)")
     args = ap.parse_args()
 
     # `python bench.py --gpus N` from a plain shell: start the N ranks ourselves (one process per GPU, the launch the
@@ -152,7 +165,7 @@ def main():
     atexit.register(close_comms)
 
     # ------------------------------------------------------------------ first contact with the peers, before anything is timed
-    if use_dist:
+    if use_dist and args.full:
         from graphlily_amd import dist as gdist
         preflight = gdist.preflight(comm, dev, args.gpus if world > 1 else 1, cabi=bfs_comm,
                                     fail_cabi="dist_preflight_fail_cabi=1" in os.environ.get("GRAPHLILY_DEBUG", ""))
@@ -170,7 +183,7 @@ def main():
     else:
         g = datasets.PAPER_GRAPHS.get(args.graph) or datasets.EXTRA_GRAPHS[args.graph]
         csr = datasets.paper_graph(args.graph, args.scale, device=dev)
-    raw = csr.copy() if not args.no_bfs else None
+    raw = csr.copy() if args.full and not args.no_bfs else None
     csr.adj_data = np.full(csr.nnz, np.float32(1.0 / csr.num_rows), dtype=np.float32)   # bench_spmv.cpp:50
     io.util_round_csr_matrix_dim(csr, 16 * 8, 8)                                        # bench_spmv.cpp:52-55
     n_rows, n_cols, nnz = csr.num_rows, csr.num_cols, csr.nnz
@@ -228,33 +241,26 @@ def main():
             dist.all_reduce(tk, op=dist.ReduceOp.MAX)
             k = int(tk.item())
         args.steps = k
-    # HIP events bracket every 4th launch of the dominant kernel inside the timed region: an event pair keeps the
+    # --full: HIP events bracket every 4th launch of the dominant kernel inside the timed region: an event pair keeps the
     # neighbouring launches from overlapping the kernel's first and last workgroups (every launch bracketed: +5 %
     # per step), so the roofline's per-launch time is the isolated one while `value` stays near the unprofiled rate
-    capi.prof_begin(args.steps, every=args.prof_every)
+    if args.full:
+        capi.prof_begin(args.steps, every=args.prof_every)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
     fence()
     wall = time.perf_counter() - t0
-    kern_ms_total, launches = capi.prof_end()
+    if args.full:
+        kern_ms_total, launches = capi.prof_end()
     if use_dist:
         t = torch.tensor([wall], dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         wall = float(t.item())
     ms_per_step = wall * 1e3 / args.steps
     value = alg_bytes * args.steps / wall / 1e9
-    kern_ms = kern_ms_total / max(launches, 1)
-    achieved = shard_bytes / (kern_ms * 1e-3) / 1e9
-
-    # quick self-check of the timed result against float64 on a row sample (rank-local rows)
-    yh = y[r0:r1].cpu().numpy()
-    xs = x.cpu().numpy().astype(np.float64)
-    rs = np.random.default_rng(0).integers(r0, max(r1, r0 + 1), size=min(2000, max(r1 - r0, 1)))
-    ip = csr.adj_indptr.astype(np.int64)
-    chk = np.array([np.dot(csr.adj_data[ip[r]:ip[r + 1]].astype(np.float64), xs[csr.adj_indices[ip[r]:ip[r + 1]]])
-                    for r in rs]) if r1 > r0 else np.zeros(0)
-    ok = bool(np.allclose(yh[rs - r0], chk, rtol=1e-5, atol=1e-12)) if r1 > r0 else True
+    if args.dump_outputs and rank == 0:       # (N > 1: the step's all-gather has left the whole y on every rank)
+        _dump_outputs(args.dump_outputs, y[:n_rows].cpu().numpy())
 
     out = {
         "metric": "SpMV effective HBM GB/s (fp32 (+,x), %s stand-in); BFS GTEPS in `bfs`" % args.graph,
@@ -278,20 +284,36 @@ def main():
                    "algorithmic_bytes_per_step": alg_bytes},
         "gteps": round(nnz * args.steps / wall / 1e9, 3),
         "frac_hbm_peak": round(value / (HBM_PEAK_GBPS * world), 4),
-        "selfcheck_ok": ok,
         "conditioning": {"untimed_steps_before_warmup": cond_steps, "ms": args.condition_ms, "idle_s_before": args.settle},
         "setup_s": {"graph": round(t_gen, 2), "plan": round(t_plan, 2)},
-        "roofline": {
-            "bound": "hbm", "kernel": "spmv_rbcs_kernel<MULADD,NOMASK,WIDE>",
-            "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-            "frac": round(achieved / HBM_PEAK_GBPS, 4),
-            "traffic": _pmc_traffic(args.graph, world, args.scale),
-            "traffic_source": "profiles/pmc_traffic.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of a RECORDED run of this "
-                              "workload (counters cannot be read from inside the benchmark process); null = no recorded run matches",
-            "bytes_per_launch": shard_bytes, "kernel_ms": round(kern_ms, 5), "launches": launches,
-            "launches_timed": "every %d-th of %d" % (args.prof_every, args.steps),
-        },
     }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        close_comms(normal=True)
+        return
+
+    kern_ms = kern_ms_total / max(launches, 1)
+    achieved = shard_bytes / (kern_ms * 1e-3) / 1e9
+    out["roofline"] = {
+        "bound": "hbm", "kernel": "spmv_rbcs_kernel<MULADD,NOMASK,WIDE>",
+        "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+        "frac": round(achieved / HBM_PEAK_GBPS, 4),
+        "traffic": _pmc_traffic(args.graph, world, args.scale),
+        "traffic_source": "profiles/pmc_traffic.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of a RECORDED run of this "
+                          "workload (counters cannot be read from inside the benchmark process); null = no recorded run matches",
+        "bytes_per_launch": shard_bytes, "kernel_ms": round(kern_ms, 5), "launches": launches,
+        "launches_timed": "every %d-th of %d" % (args.prof_every, args.steps),
+    }
+
+    # quick self-check of the timed result against float64 on a row sample (rank-local rows)
+    yh = y[r0:r1].cpu().numpy()
+    xs = x.cpu().numpy().astype(np.float64)
+    rs = np.random.default_rng(0).integers(r0, max(r1, r0 + 1), size=min(2000, max(r1 - r0, 1)))
+    ip = csr.adj_indptr.astype(np.int64)
+    chk = np.array([np.dot(csr.adj_data[ip[r]:ip[r + 1]].astype(np.float64), xs[csr.adj_indices[ip[r]:ip[r + 1]]])
+                    for r in rs]) if r1 > r0 else np.zeros(0)
+    out["selfcheck_ok"] = bool(np.allclose(yh[rs - r0], chk, rtol=1e-5, atol=1e-12)) if r1 > r0 else True
 
     # ------------------------------------------------------------------ same SpMV on the pattern layout
     # (what a caller gets by default for this matrix: column-constant values are detected at plan creation)
@@ -424,6 +446,19 @@ def _ordered(out):
         hl["six_cols"] = "frac wall, frac kernel, pattern ms, pagerank ms/it, bfs pp ms"
     o["headline"] = hl
     return o
+
+
+def _dump_outputs(d, y):
+    """--dump-outputs: the dense result of the last timed step as DIR/y.npy (float32); one above DUMP_LIMIT_BYTES is written as
+    the values at a fixed, seeded sample of rows (DIR/y_sample.npy) and those rows (DIR/y_sample_rows.npy, float64: exact)."""
+    os.makedirs(d, exist_ok=True)
+    y = np.ascontiguousarray(y, dtype=np.float32)
+    if y.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(d, "y.npy"), y)
+        return
+    rows = np.sort(np.random.default_rng(0).choice(y.shape[0], DUMP_LIMIT_BYTES // 16, replace=False))
+    np.save(os.path.join(d, "y_sample.npy"), y[rows])
+    np.save(os.path.join(d, "y_sample_rows.npy"), rows.astype(np.float64))
 
 
 def _self_launch(n):

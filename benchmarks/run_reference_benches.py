@@ -16,9 +16,11 @@ runs `bench_spmspv hw unused.xclbin <log>` -- 7 matrices x 7 vector sparsities, 
 reference's own compute_reference_results -- and removes the files, the marker and every directory level it created again
 (`--keep` leaves them; files found there from an earlier `--keep` run are always REGENERATED, never trusted).
 
-`--apps tests --write-reference-dataset-dir` does the same for the reference's own ACCEPTANCE SUITES (tests/test_module_apply.cpp,
-tests/test_module_spmv_spmspv.cpp, tests/test_app.cpp, compiled unmodified by `make -C oracle ref_tests`), whose sources name
-dense_32 / dense_1K / uniform_10K_10 / gplus_108K_13M under /work/shared/common/project_build/...: float and ap_ufixed<32, 8>.
+`--apps tests` runs the reference's own ACCEPTANCE SUITES (tests/test_module_apply.cpp, tests/test_module_spmv_spmspv.cpp,
+tests/test_app.cpp, compiled by `make -C oracle ref_tests`), float and ap_ufixed<32, 8>, over stand-ins of the dense_32 /
+dense_1K / uniform_10K_10 / gplus_108K_13M their sources name.  The sources put those under the authors' absolute directory
+/work/shared/common/project_build/...; oracle/Makefile drops that prefix on the way to the compiler (the only edit), so the
+stand-ins go to graphblas/data/sparse_matrix_graph/ inside the suites' scratch working directory and need no opt-in.
 """
 import argparse
 import os
@@ -43,8 +45,9 @@ REF_SPMSPV_FILES = [("gplus_108K_13M_csr_float32.npz", "googleplus"), ("ogbl_ppa
 MARKER = ".written_by_graphlily_hip_run_reference_benches"
 
 
-# tests/test_module_spmv_spmspv.cpp:144-145,167-168,251-266 and tests/test_app.cpp:57-58,91-92,111-112
-REF_TESTS_DIR = "/work/shared/common/project_build/graphblas/data/sparse_matrix_graph/"
+# tests/test_module_spmv_spmspv.cpp:144-145,167-168,251-266 and tests/test_app.cpp:57-58,91-92,111-112, relative to the working
+# directory (oracle/Makefile REF_TESTS_DATA)
+REF_TESTS_DIR = "graphblas/data/sparse_matrix_graph/"
 REF_TESTS_FILES = [("dense_32_csr_float32.npz", "dense_32"), ("dense_1K_csr_float32.npz", "dense_1K"),
                    ("uniform_10K_10_csr_float32.npz", "uniform_10K_10"), ("gplus_108K_13M_csr_float32.npz", "googleplus")]
 
@@ -148,23 +151,26 @@ def run_spmspv(dev, keep, allow_abs):
 REF_TEST_SUITES = ["test_module_apply", "test_module_spmv_spmspv", "test_app"]
 
 
-def run_tests(dev, keep, allow_abs, variants=("", "_ufixed")):
+def run_tests(dev, variants=("", "_ufixed")):
     """The reference's own acceptance suites -- tests/test_module_apply.cpp, tests/test_module_spmv_spmspv.cpp, tests/test_app.cpp,
-    compiled UNMODIFIED against include/ (`make -C oracle ref_tests`: include/ap_fixed.h, tests/cpp/gtest/gtest.h) -- for
-    val_t = float and for the reference's shipped ap_ufixed<32, 8>, over stand-ins under the names and in the directory the sources
-    have compiled in.  Prints every suite's RUN / OK / FAILED lines; returns the number of failing binaries."""
-    exes = [(s + v, os.path.join(ROOT, "oracle", "_ref", "ref_" + s + v)) for v in variants for s in REF_TEST_SUITES]
+    compiled against include/ (`make -C oracle ref_tests`: include/ap_fixed.h, tests/cpp/gtest/gtest.h), unmodified but for their
+    dataset directory -- for val_t = float and for the reference's shipped ap_ufixed<32, 8>, over stand-ins under the names the
+    sources have compiled in, in the scratch directory the suites run in.  Prints every suite's RUN / OK / FAILED lines; returns the
+    number of failing binaries."""
+    exes = [(s + v, os.path.join(ROOT, "oracle", "_ref", "suite_" + s + v)) for v in variants for s in REF_TEST_SUITES]
     missing = [e for _, e in exes if not os.path.exists(e)]
     if missing:
         print("# not built (needs /root/reference: make -C oracle ref_tests): %s" % ", ".join(missing))
         return 2
     bad = 0
     try:
-        with ReferenceDatasetDir(REF_TESTS_DIR, REF_TESTS_FILES, dev, allow_abs, keep), tempfile.TemporaryDirectory(dir="/tmp") as tmp:
+        with tempfile.TemporaryDirectory(dir="/tmp") as tmp, \
+                ReferenceDatasetDir(os.path.join(tmp, REF_TESTS_DIR), REF_TESTS_FILES, dev, allow_abs=True, keep=False):
             for name, exe in exes:
                 t0 = time.time()
                 r = subprocess.run([exe], capture_output=True, text=True, cwd=tmp)     # (the Clean fixtures rm -rf ./proj: inside tmp)
-                lines = [l for l in r.stdout.splitlines() if l.startswith("[") or "Failure" in l or "Which is" in l or "Actual" in l]
+                lines = [l for l in r.stdout.splitlines()
+                         if l.startswith("[") or "Failure" in l or "Which is" in l or "Actual" in l or "Error" in l or "error" in l]
                 print("## %s (exit code %d, %.1f s)" % (name, r.returncode, time.time() - t0))
                 sys.stdout.write("\n".join(lines) + "\n" + r.stderr[-1500:])
                 sys.stdout.flush()
@@ -196,7 +202,7 @@ def main():
     if args.apps == "spmspv":
         sys.exit(run_spmspv(dev, args.keep, args.write_reference_dataset_dir))
     if args.apps == "tests":
-        sys.exit(run_tests(dev, args.keep, args.write_reference_dataset_dir))
+        sys.exit(run_tests(dev))
     with tempfile.TemporaryDirectory(dir="/tmp") as tmp:
         if args.npz:
             path = args.npz

@@ -292,12 +292,12 @@ def test_reference_benchmark_drivers_run_on_hip_backend(gpu):
 
 
 @pytest.mark.gpu
-@pytest.mark.skipif(not os.path.exists(os.path.join(ROOT, "oracle", "_ref", "ref_test_app")),
+@pytest.mark.skipif(not os.path.exists(os.path.join(ROOT, "oracle", "_ref", "suite_test_app")),
                     reason="prebuilt reference test suites did not travel")
 def test_reference_test_suites_pass_on_hip_backend(gpu):
     """tests/test_module_apply.cpp:54-261, tests/test_module_spmv_spmspv.cpp:137-314 and tests/test_app.cpp:51-135 -- the files
     that DEFINE the acceptance bar (eps 1e-4, the semiring x mask matrix, the three apps on uniform_10K_10) -- byte-identical to
-    the checkout, on the HIP backend, for val_t = float and for the reference's shipped ap_ufixed<32, 8>: every TEST passes
+    the checkout but for their dataset directory (made relative to the working directory: oracle/Makefile), on the HIP backend, for val_t = float and for the reference's shipped ap_ufixed<32, 8>: every TEST passes
     (Synthesize is a no-op print, Clean removes ./proj in a scratch directory)."""
     r = subprocess.run(["python", os.path.join(ROOT, "benchmarks", "run_reference_benches.py"), "--apps", "tests",
                         "--write-reference-dataset-dir"], capture_output=True, text=True, timeout=1800)

@@ -140,7 +140,7 @@ def test_bench_self_launches_two_ranks(gpu):
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     root = os.path.dirname(HERE)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--same-gpu",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--backend", "gloo", "--same-gpu",
                         "--steps", "20", "--warmup", "2", "--scale", "0.1", "--bfs-runs", "1"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
@@ -161,7 +161,7 @@ def test_bench_self_launches_eight_ranks(gpu):
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     root = os.path.dirname(HERE)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--backend", "gloo", "--same-gpu",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "8", "--backend", "gloo", "--same-gpu",
                         "--steps", "5", "--warmup", "1", "--scale", "0.05", "--bfs-runs", "1", "--no-pattern"],
                        capture_output=True, text=True, timeout=1500, env=env, cwd=root)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
@@ -182,7 +182,7 @@ def test_bench_one_rank_rccl(gpu):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     root = os.path.dirname(HERE)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--force-dist", "--steps", "20", "--warmup", "2",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "1", "--force-dist", "--steps", "20", "--warmup", "2",
                         "--scale", "0.1", "--bfs-runs", "1", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
@@ -208,7 +208,7 @@ def test_bench_falls_back_when_the_c_abi_preflight_fails(gpu):
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     env["GRAPHLILY_DEBUG"] = "dist_preflight_fail_cabi=1"
     root = os.path.dirname(HERE)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--force-dist", "--cabi-comm", "--no-six-graphs", "--no-spmspv",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "1", "--force-dist", "--cabi-comm", "--no-six-graphs", "--no-spmspv",
                         "--steps", "10", "--warmup", "2", "--scale", "0.1", "--bfs-runs", "1", "--no-cpu-baseline", "--no-pattern"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
@@ -230,7 +230,7 @@ def test_bench_one_rank_rccl_exchange_inside_the_graph(gpu):
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     env["GRAPHLILY_DEBUG"] = "dist_self_probe=1"
     root = os.path.dirname(HERE)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--force-dist", "--cabi-comm", "--no-six-graphs", "--no-spmspv", "--steps", "10", "--warmup", "2",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "1", "--force-dist", "--cabi-comm", "--no-six-graphs", "--no-spmspv", "--steps", "10", "--warmup", "2",
                         "--scale", "0.1", "--bfs-runs", "1", "--no-cpu-baseline", "--no-pattern"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
