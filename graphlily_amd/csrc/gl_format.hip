@@ -1,4 +1,4 @@
-// Plan creation on the GPU: the O(nnz) half of gl_spmv_plan_create_ex / bool_plan_build.
+// Plan creation on the GPU: the O(nnz) half of gl_spmv_plan_create_ex (gl_spmv_plan.cpp) / bool_plan_build.
 //
 // The reference formats its matrices on the host, single-threaded (csr2cpsr, io/data_formatter.h:456-534: 6.8 s for
 // 16.7 M non-zeros); round 1 of this build did it with OpenMP (2.2 s for the 212 M non-zeros of the orkut

@@ -978,45 +978,10 @@ static Shape choose_shape_bool(uint64_t rows, uint64_t cols, uint64_t nnz, int n
     return best;
 }
 
-int bool_plan_build(gl_spmv_plan p, const uint32_t *h_indptr, const uint32_t *h_indices, const float *h_data) {
-    const uint32_t num_cols = p->num_cols, row_begin = p->row_begin, row_end = p->row_end;
-    const uint32_t rows = row_end - row_begin;
-    const Shape shape = choose_shape_bool(rows, num_cols, p->nnz, ctx().num_cus);
-    // block boundaries on multiples of 64 rows: the fused BFS epilogue writes whole 64-bit frontier words
-    const BlockPlan bp = plan_blocks(shape, h_indptr, row_begin, row_end, kBoolHubBit0 / 64u * 64u, 64u);
-    const uint32_t nblocks = bp.nblocks, nunits = bp.nunits;
-    const uint32_t nphases = cdiv(num_cols, kBoolPhaseCols);
-
-    if (format_on_device(p->flags, p->nnz)) {
-        // the record loop below as kernels over a staged copy of the shard (gl_format.hip); identical arrays
-        struct Staged {
-            DevCsr *c = nullptr;
-            ~Staged() { devcsr_release(c); }
-        } staged;
-        int rc = devcsr_stage(&staged.c, h_indptr, h_indices, h_data, row_begin, row_end);
-        if (rc != GL_OK) return rc;
-        EmitBool eb;
-        eb.bp = &bp;
-        eb.h_indptr = h_indptr;
-        eb.num_cols = num_cols;
-        uint32_t tallest = 0;
-        if ((rc = fmt_emit_bool(staged.c, eb, p, &tallest)) != GL_OK) return rc;
-        if (debug_knob("bfs_keep_rows", 1) != 0) {
-            if ((rc = devcsr_adopt_rows(staged.c, &p->d_csr_indptr, &p->d_csr_indices)) != GL_OK) return rc;
-            p->csr_nz_base = h_indptr[row_begin];
-            p->device_bytes += ((size_t)rows + 1u) * 4u + (size_t)p->nnz * 4u;
-        }
-        p->boolean = true;
-        p->nblocks = nblocks;
-        p->segments = bp.Smax;
-        p->nunits = nunits;
-        p->max_block_rows = tallest;
-        p->nphases = nphases;
-        GL_HIP(hipMalloc((void **)&p->d_xbits, (size_t)nphases * kBoolPhaseWords * 4u));
-        p->device_bytes += (size_t)nphases * kBoolPhaseWords * 4u;
-        return GL_OK;
-    }
-
+// host twin of fmt_emit_bool (gl_format.hip): the record loop with OpenMP; fills the same arrays and *max_rows
+static int emit_bool_host(gl_spmv_plan p, const BlockPlan &bp, const uint32_t *h_indptr, const uint32_t *h_indices, const float *h_data,
+                          uint32_t *max_rows) {
+    const uint32_t num_cols = p->num_cols, nblocks = bp.nblocks, nunits = bp.nunits;
     // every unit is emitted on its own (groups, bases, spans), then the pieces are laid out in unit order
     struct UnitOut {
         std::vector<uint32_t> ent;     // 128 per group
@@ -1027,7 +992,6 @@ int bool_plan_build(gl_spmv_plan p, const uint32_t *h_indptr, const uint32_t *h_
     std::vector<uint4> units((size_t)nunits * 2);
     std::vector<uint32_t> hub_rows((size_t)nblocks * kBoolHubMax, 0u);
     int bad_col = 0;
-    uint32_t max_rows = 0;
 #pragma omp parallel
     {
         std::vector<Rec> recs, tmp;
@@ -1115,7 +1079,7 @@ int bool_plan_build(gl_spmv_plan p, const uint32_t *h_indptr, const uint32_t *h_
     }
     if (bad_col)
         return set_error(GL_ERR_INVALID_ARG, "gl_spmv_plan_create: column index out of range (num_cols %u)", num_cols);
-    for (uint32_t b = 0; b < nblocks; b++) max_rows = std::max(max_rows, bp.bstart[b + 1] - bp.bstart[b]);
+    for (uint32_t b = 0; b < nblocks; b++) *max_rows = std::max(*max_rows, bp.bstart[b + 1] - bp.bstart[b]);
 
     std::vector<uint64_t> goff((size_t)nunits + 1, 0), soff((size_t)nunits + 1, 0);
     for (size_t u = 0; u < nunits; u++) {
@@ -1143,42 +1107,69 @@ int bool_plan_build(gl_spmv_plan p, const uint32_t *h_indptr, const uint32_t *h_
         UnitOut().ent.swap(o.ent);
     }
 
-    p->boolean = true;
-    p->nblocks = nblocks;
-    p->segments = bp.Smax;
-    p->nunits = nunits;
-    p->ngroups = total_groups;
-    p->max_block_rows = max_rows;
-    p->nphases = nphases;
-    auto up = [&](void **d, const void *h, size_t bytes) -> int {
-        GL_HIP(hipMalloc(d, bytes ? bytes : 16));
-        if (bytes) GL_HIP(hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice));
-        p->device_bytes += bytes;
-        return GL_OK;
-    };
     int rc;
-    if ((rc = up((void **)&p->d_entries, entries.data(), entries.size() * 4u)) != GL_OK ||
-        (rc = up((void **)&p->d_bases, bases.data(), bases.size() * 4u)) != GL_OK ||
-        (rc = up((void **)&p->d_units, units.data(), units.size() * sizeof(uint4))) != GL_OK ||
-        (rc = up((void **)&p->d_hub_rows, hub_rows.data(), hub_rows.size() * sizeof(uint32_t))) != GL_OK ||
-        (rc = up((void **)&p->d_spans, spans.data(), spans.size() * sizeof(uint4))) != GL_OK)
+    if ((rc = plan_upload(p, p->d_entries, entries.data(), entries.size() * 4u)) != GL_OK ||
+        (rc = plan_upload(p, p->d_bases, bases.data(), bases.size() * 4u)) != GL_OK ||
+        (rc = plan_upload(p, p->d_units, units.data(), units.size() * sizeof(uint4))) != GL_OK ||
+        (rc = plan_upload(p, p->d_hub_rows, hub_rows.data(), hub_rows.size() * sizeof(uint32_t))) != GL_OK ||
+        (rc = plan_upload(p, p->d_spans, spans.data(), spans.size() * sizeof(uint4))) != GL_OK)
         return rc;
     p->b_entries = entries.size() * 4u;
     p->b_bases = bases.size() * 4u;
     p->b_units = units.size() * sizeof(uint4);
     p->b_hub_rows = hub_rows.size() * sizeof(uint32_t);
     p->b_spans = spans.size() * sizeof(uint4);
+    p->ngroups = total_groups;
+    return GL_OK;
+}
+
+// (the caller owns p: an error return leaves it half built, to gl_spmv_plan_destroy)
+int bool_plan_build(gl_spmv_plan p, const uint32_t *h_indptr, const uint32_t *h_indices, const float *h_data) {
+    const uint32_t num_cols = p->num_cols, row_begin = p->row_begin, row_end = p->row_end;
+    const uint32_t rows = row_end - row_begin;
+    const Shape shape = choose_shape_bool(rows, num_cols, p->nnz, ctx().num_cus);
+    // block boundaries on multiples of 64 rows: the fused BFS epilogue writes whole 64-bit frontier words
+    const BlockPlan bp = plan_blocks(shape, h_indptr, row_begin, row_end, kBoolHubBit0 / 64u * 64u, 64u);
+    const uint32_t nblocks = bp.nblocks, nunits = bp.nunits;
+    const uint32_t nphases = cdiv(num_cols, kBoolPhaseCols);
+
+    StagedCsr staged;
+    uint32_t max_rows = 0;
+    int rc;
+    if (format_on_device(p->flags, p->nnz)) {
+        // the record loop below as kernels over a staged copy of the shard (gl_format.hip); identical arrays
+        if ((rc = devcsr_stage(&staged.c, h_indptr, h_indices, h_data, row_begin, row_end)) != GL_OK) return rc;
+        EmitBool eb;
+        eb.bp = &bp;
+        eb.h_indptr = h_indptr;
+        eb.num_cols = num_cols;
+        if ((rc = fmt_emit_bool(staged.c, eb, p, &max_rows)) != GL_OK) return rc;
+    } else if ((rc = emit_bool_host(p, bp, h_indptr, h_indices, h_data, &max_rows)) != GL_OK) {
+        return rc;
+    }
+
+    p->boolean = true;
+    p->nblocks = nblocks;
+    p->segments = bp.Smax;
+    p->nunits = nunits;
+    p->max_block_rows = max_rows;
+    p->nphases = nphases;
     GL_HIP(hipMalloc((void **)&p->d_xbits, (size_t)nphases * kBoolPhaseWords * 4u));
     p->device_bytes += (size_t)nphases * kBoolPhaseWords * 4u;
     if (debug_knob("bfs_keep_rows", 1) != 0) {
         // the rows as plain CSR for the bottom-up BFS step (see gl_spmv_plan.h); zero values -> column 0xffffffff
         const uint64_t nz0 = h_indptr[row_begin];
-        std::vector<uint32_t> cols(h_indices + nz0, h_indices + nz0 + p->nnz);
-        for (uint64_t i = 0; i < p->nnz; i++)
-            if (h_data[nz0 + i] == 0.0f) cols[i] = 0xffffffffu;
-        if ((rc = up((void **)&p->d_csr_indptr, h_indptr + row_begin, ((size_t)rows + 1u) * 4u)) != GL_OK ||
-            (rc = up((void **)&p->d_csr_indices, cols.data(), cols.size() * 4u)) != GL_OK)
-            return rc;
+        if (staged.c) {
+            if ((rc = devcsr_adopt_rows(staged.c, &p->d_csr_indptr, &p->d_csr_indices)) != GL_OK) return rc;
+            p->device_bytes += ((size_t)rows + 1u) * 4u + (size_t)p->nnz * 4u;
+        } else {
+            std::vector<uint32_t> cols(h_indices + nz0, h_indices + nz0 + p->nnz);
+            for (uint64_t i = 0; i < p->nnz; i++)
+                if (h_data[nz0 + i] == 0.0f) cols[i] = 0xffffffffu;
+            if ((rc = plan_upload(p, p->d_csr_indptr, h_indptr + row_begin, ((size_t)rows + 1u) * 4u)) != GL_OK ||
+                (rc = plan_upload(p, p->d_csr_indices, cols.data(), cols.size() * 4u)) != GL_OK)
+                return rc;
+        }
         p->csr_nz_base = (uint32_t)nz0;
     }
     return GL_OK;

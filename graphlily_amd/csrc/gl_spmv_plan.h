@@ -1,5 +1,5 @@
-// Shared by gl_spmv.hip (general semiring SpMV) and gl_spmv_bool.hip ((||,&&)-only SpMV): the plan object,
-// the row-block / segment planner and the host-side sorting helpers.
+// Shared by gl_spmv_plan.cpp (host planning), gl_spmv.hip (general semiring SpMV) and gl_spmv_bool.hip ((||,&&)-only SpMV):
+// the plan object, the row-block / segment planner and the host-side sorting helpers.
 #ifndef GL_SPMV_PLAN_H_
 #define GL_SPMV_PLAN_H_
 
@@ -203,7 +203,6 @@ struct gl_spmv_plan_s {
                                      // per column 0x80000000 | hot slot, packed index, or 0xffffffff
     float *d_colval_bycol = nullptr; // pattern plans in that mode: the column values indexed by column
     bool self_hot = false;           // no helper launch: the workgroups gather their (small) hot table from x themselves
-    bool wide = false;               // general layout with lane-interleaved group pairs (16-byte stream loads)
     bool pattern = false;            // every column's values are equal: 4-byte entries, z = colval (x) x per run
     float *d_colval = nullptr, *d_z = nullptr;
     float *d_diag = nullptr;         // pattern plans whose diagonal differs from the column values: A[r][r] per local row
@@ -233,6 +232,25 @@ struct gl_spmv_plan_s {
 };
 
 namespace gl {
+// Device arrays of a plan under construction (gl_spmv_plan.cpp, bool_plan_build), counted in its device_bytes.
+// plan_upload: a copy of `bytes` host bytes (16 bytes allocated when empty: the plan's arrays are never null).
+template <typename T>
+int plan_upload(gl_spmv_plan p, T *&d, const void *h, size_t bytes) {
+    GL_HIP(hipMalloc((void **)&d, bytes ? bytes : 16));
+    if (bytes) GL_HIP(hipMemcpy(d, h, bytes, hipMemcpyHostToDevice));
+    p->device_bytes += bytes;
+    return GL_OK;
+}
+// plan_alloc: a buffer the runs fill, of which `counted` bytes count; zeroed on the library's stream if asked
+template <typename T>
+int plan_alloc(gl_spmv_plan p, T *&d, size_t bytes, size_t counted, const char *what, bool zero = false) {
+    hipError_t e = hipMalloc((void **)&d, bytes);
+    if (e == hipSuccess && zero) e = hipMemsetAsync(d, 0, bytes, ctx().stream);
+    if (e != hipSuccess) return set_error(GL_ERR_HIP, "gl_spmv_plan_create: hipMalloc(%s): %s", what, hipGetErrorString(e));
+    p->device_bytes += counted;
+    return GL_OK;
+}
+
 // ------------------------------------------------------------------------------------------ gl_format.hip
 // Plan creation on the GPU.  The O(rows + columns) decisions of a plan -- row blocks, hot columns,
 // packed gather order, hub rows, group budgets -- stay on the host and are shared with the host formatter; every
@@ -243,6 +261,10 @@ struct DevCsr;   // the shard's indptr / indices / data on the device
 int devcsr_stage(DevCsr **out, const uint32_t *h_indptr, const uint32_t *h_indices, const float *h_data,
                  uint32_t row_begin, uint32_t row_end);
 void devcsr_release(DevCsr *c);
+struct StagedCsr {   // a staged copy that lives until the end of the scope
+    DevCsr *c = nullptr;
+    ~StagedCsr() { devcsr_release(c); }
+};
 // hand the staged rows over to a plan (the bottom-up BFS step reads them); zero-valued entries get column 0xffffffff
 int devcsr_adopt_rows(DevCsr *c, uint32_t **d_indptr, uint32_t **d_indices);
 bool format_on_device(uint32_t flags, uint64_t nnz);   // policy: GL_PLAN_HOST_FORMAT / GRAPHLILY_PLAN_DEVICE / size
@@ -250,7 +272,7 @@ int fmt_column_degrees(DevCsr *c, uint32_t num_cols, std::vector<uint32_t> &deg,
 int fmt_detect_pattern(DevCsr *c, uint32_t num_cols, std::vector<uint32_t> &colbits, std::vector<uint32_t> &diag_has,
                        std::vector<float> &diag_val, int *mismatch, uint64_t *exceptions);
 
-struct EmitGeneral {   // what the host planner decided (gl_spmv_plan_create_ex)
+struct EmitGeneral {   // what the host planner decided (gl_spmv_plan.cpp, plan_general)
     const BlockPlan *bp;
     uint32_t dummy_max;                // layout_units' bound on the dummy entries of a unit
     const uint32_t *colmap;            // per column: 0x80000000 | hot slot, or the index the cold entry gathers from
@@ -258,7 +280,7 @@ struct EmitGeneral {   // what the host planner decided (gl_spmv_plan_create_ex)
     bool diag_mode;                    // diagonal entries that differ from their column's value are dropped
     const uint32_t *colbits;           // host copy of the column values (diag_mode)
     const uint32_t *diag_has;          // host bitmap of the rows whose diagonal entry is an exception (diag_mode)
-    bool pattern, wide;                // (pattern plans carry the ROW-PACKED hot stream)
+    bool pattern;                      // (pattern plans carry the ROW-PACKED hot stream)
     uint32_t group_mult;
     uint32_t hub_div;
     const uint32_t *h_indptr;          // host indptr (global), for the per-row counts
