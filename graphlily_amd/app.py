@@ -28,6 +28,70 @@ from . import module as M
 from .dist import Comm, partition_rows_by_nnz
 
 
+NO_PARENT = 0xFFFFFFFF      # BFS.parents(): the vertex has no predecessor (unreached, or an orphan of a non-BFS level array)
+
+
+def validate_bfs_tree(csr, source, distance, parent, num_iterations=None):
+    """Host-side check (numpy) that `parent` is a BFS tree of `csr` -- row v lists the vertices v is pulled from, entries with
+    value 0 are no edges -- consistent with the drivers' levels `distance` (1 on the source, 0 = unreached).  Raises ValueError
+    naming the first offending vertex; returns the number of reached vertices.  The rules (Graph500's, in the drivers' terms):
+      1. the source has level 1 and is its own parent;
+      2. a vertex is reached (level >= 1) exactly if it has a parent;
+      3. parent[v] -> v is an edge: A[v, parent[v]] != 0;
+      4. level[parent[v]] == level[v] - 1;
+      5. no edge A[v, u] leads from an EXPANDED vertex u to a vertex v that is unreached or more than one level deeper.  With
+         `num_iterations` given, the search stopped there: u was expanded if 1 <= level[u] <= num_iterations (the last level,
+         num_iterations + 1, never was); otherwise every reached u was.
+    `distance` / `parent` may be longer than the matrix (the drivers pad it): the extra vertices have empty rows."""
+    indptr = np.asarray(csr.adj_indptr).astype(np.int64)
+    nr = int(csr.num_rows)
+    d = np.asarray(distance, dtype=np.float64)
+    p = np.asarray(parent).astype(np.int64)
+    n = d.shape[0]
+    if p.shape[0] != n or n < max(nr, int(csr.num_cols)):
+        raise ValueError("validate_bfs_tree: %d levels and %d parents for a %d x %d matrix" % (n, p.shape[0], nr, csr.num_cols))
+
+    def first(bad):
+        return int(np.flatnonzero(bad)[0])
+
+    source = int(source)
+    if d[source] != 1 or p[source] != source:
+        raise ValueError("validate_bfs_tree: source %d has level %g and parent %d (rule 1)" % (source, d[source], p[source]))
+    reached, has_parent = d >= 1, p != NO_PARENT
+    if np.any(reached != has_parent):
+        v = first(reached != has_parent)
+        raise ValueError("validate_bfs_tree: vertex %d has level %g and parent %s (rule 2)" % (v, d[v], "none" if p[v] == NO_PARENT else p[v]))
+    child = reached.copy()
+    child[source] = False
+    if np.any(child & ((p < 0) | (p >= n))):
+        raise ValueError("validate_bfs_tree: vertex %d has parent %d, which is no vertex (rule 3)" % (first(child & ((p < 0) | (p >= n))), p[first(child & ((p < 0) | (p >= n)))]))
+    pc = np.where(child, p, 0)
+    if np.any(child & (d[pc] != d - 1)):
+        v = first(child & (d[pc] != d - 1))
+        raise ValueError("validate_bfs_tree: vertex %d on level %g has parent %d on level %g (rule 4)" % (v, d[v], p[v], d[p[v]]))
+    expanded = reached if num_iterations is None else reached & (d <= num_iterations)
+    is_edge = np.zeros(n, dtype=bool)
+    step = 1 << 18                       # rows per block: bounds the temporaries on matrices of 1e8 entries
+    for r0 in range(0, nr, step):
+        r1 = min(nr, r0 + step)
+        lo, hi = indptr[r0], indptr[r1]
+        if hi == lo:
+            continue
+        cols = np.asarray(csr.adj_indices[lo:hi]).astype(np.int64)
+        live = np.asarray(csr.adj_data[lo:hi]) != 0
+        rows = np.repeat(np.arange(r0, r1, dtype=np.int64), np.diff(indptr[r0:r1 + 1]))
+        is_edge[rows[live & (cols == p[rows])]] = True
+        bad = live & expanded[cols] & ((d[rows] == 0) | (d[rows] > d[cols] + 1))
+        if np.any(bad):
+            k = first(bad)
+            raise ValueError("validate_bfs_tree: edge %d -> %d leads from level %g to level %g (rule 5)"
+                             % (cols[k], rows[k], d[cols[k]], d[rows[k]]))
+    if np.any(child & ~is_edge):
+        v = first(child & ~is_edge)
+        raise ValueError("validate_bfs_tree: vertex %d has parent %d, but the matrix has no entry A[%d, %d] (rule 3)" % (v, p[v], v, p[v]))
+    return int(reached.sum())
+
+
 class HipBackend:
     """Allocation / transfer hooks of the drivers.  The CPU tests substitute a stand-in with the
     same methods to exercise the distributed control flow over gloo."""
@@ -276,6 +340,7 @@ class BFS(_GraphApp):
 
     def _finish_distance(self, distance):
         self._gather(distance)
+        self.levels_ = (distance, None)      # BFS.parents(): this run's levels, whole on every rank
         self.backend.sync()
         return self.backend.download_result(distance, self.n_)
 
@@ -522,6 +587,10 @@ class BFS(_GraphApp):
             self.readback_ = {"way": way, "packed_ms": None if rb["packed"] is None else round(rb["packed"] * 1e3, 4),
                               "float_ms": None if rb["float"] is None else round(rb["float"] * 1e3, 4)}
         self.result_range_ = (lo, hi)
+        # BFS.parents(): this run's levels stay in the schedule's buffer (a rank that read back only its slice holds only its
+        # rows of them: parents() all-gathers first)
+        # (plain handles, no closure over self: a reference cycle would leave the driver's plans and buffers to the garbage collector)
+        self.levels_ = (distance, st["both"] if sliced else None)
         self.push_iterations_ = int(c[1])          # the reference's count (first push phase)
         self.push_iterations_again_ = int(c[3])    # pushes after a pull step handed back
         S = (cw - 16) // 2
@@ -575,6 +644,37 @@ class BFS(_GraphApp):
             it += 1
         return self._finish_distance(distance)
 
+
+    # -- predecessor tree (an extension: the reference's drivers return levels only) ------------------------------------------
+    def parents(self, distance=None):
+        """The BFS predecessor tree as uint32[n]: parent[v] = v on the source (level 1), NO_PARENT (0xffffffff) on an unreached
+        vertex (level 0), otherwise the SMALLEST u with an entry A[v, u] != 0 and level[u] == level[v] - 1 -- unique, whichever
+        mix of push / pull / bottom-up steps found the levels.  One pass over the rows from the finished level vector
+        (gl_bfs_parents): `distance=None` takes the levels of this object's last pull / push / pull_push, which are still on the
+        device; an array (n floats, the drivers' levels) is uploaded and used instead.  Row shards compute their own rows from
+        the whole level vector and all-gather the slices.  `orphans_` = vertices of level >= 2 without such a u among this
+        rank's rows (0 for a BFS result)."""
+        B, n = self.backend, self.n_
+        if distance is None:
+            last = getattr(self, "levels_", None)
+            if last is None:
+                raise RuntimeError("BFS.parents(): no pull / push / pull_push has run on this object; pass the level array")
+            levels, partial = last
+            if partial is not None:      # the schedule's buffer of a rank that read back only its slice
+                self.comm.all_gather_slices(partial.tensor[:n] if partial.tensor is not None else partial, self.bounds_)
+        else:
+            arr = np.ascontiguousarray(distance, dtype=np.float32)
+            if arr.shape != (n,):
+                raise ValueError("BFS.parents(): the level array has shape %s, the (padded) matrix has %d rows" % (arr.shape, n))
+            levels = B.alloc(n, np.float32)
+            B.upload(levels, arr)
+        par = B.alloc(n + 1, np.float32)      # (32-bit words: vertex numbers, then the orphan count)
+        self.SpMV_.bfs_parents(levels, self._own(par), B.view(par, n, 1, 4))
+        self._gather(par)
+        B.sync()
+        out = B.download(par, np.uint32, n + 1)
+        self.orphans_ = int(out[n])
+        return out[:n]
 
     def pull_push_time_breakdown(self, source, num_iterations, threshold=0.05):
         """app/bfs.h:222-347: pull_push with the reference's four wall-clock buckets.  Every step is followed by

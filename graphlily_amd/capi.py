@@ -40,6 +40,7 @@ EXPORTS = [
     "gl_buf_alloc", "gl_buf_free", "gl_buf_h2d", "gl_buf_d2h", "gl_buf_d2d", "gl_buf_fill_f32", "gl_buf_fill_u32",     "gl_host_alloc", "gl_host_free", "gl_host_pool_alloc", "gl_host_pool_free", "gl_pool_trim", "gl_pool_stats", "gl_host_pool_reserve", "gl_host_fill_u32", "gl_host_sparse_to_dense",
     "gl_spmv_plan_create", "gl_spmv_plan_create_ex", "gl_spmv_plan_destroy", "gl_spmv_plan_describe", "gl_spmv_plan_export", "gl_spmv_run", "gl_spmv_plan_chain",
     "gl_spmv_plan_bits_words", "gl_pack_bits", "gl_unpack_bits", "gl_bfs_bits_begin_from", "gl_spmv_run_bits", "gl_bfs_pull_step",
+    "gl_bfs_parents", "gl_bfs_parents_entries", "gl_spmv_plan_rows_sorted",
     "gl_prof_begin", "gl_prof_end", "gl_span_begin", "gl_span_end",
     "gl_spmspv_plan_create", "gl_spmspv_plan_destroy", "gl_spmspv_plan_info", "gl_spmspv_run", "gl_spmspv_run_assign",
     "gl_spmspv_plan_attach_pull", "gl_spmspv_plan_hint", "gl_spmspv_plan_hint_work", "gl_spmspv_last_direction", "gl_spmspv_wait", "gl_spmspv_failed_runs",
@@ -109,6 +110,7 @@ def lib():
         "gl_spmv_plan_export": [vp, i32, vp, ctypes.c_size_t, P(ctypes.c_size_t)], "gl_spmv_plan_chain": [vp, i32, P(i32)],
         "gl_spmv_plan_bits_words": [vp, P(u64)], "gl_pack_bits": [vp, u32, vp], "gl_unpack_bits": [vp, u32, vp], "gl_bfs_bits_begin_from": [vp, u32, vp, u32, vp, u32, vp, vp], "gl_spmv_run_bits": [vp, vp, vp, vp, f32, i32],
         "gl_bfs_pull_step": [vp, vp, vp, vp, f32],
+        "gl_bfs_parents": [vp, vp, vp, vp], "gl_bfs_parents_entries": [vp, vp, vp, P(u64)], "gl_spmv_plan_rows_sorted": [vp, P(i32)],
         "gl_spmv_run": [vp, vp, vp, vp, i32, f32, i32],
         "gl_prof_begin": [u32, u32], "gl_prof_end": [P(ctypes.c_double), P(u32)], "gl_span_begin": [], "gl_span_end": [P(ctypes.c_double)],
         "gl_spmspv_plan_create": [P(vp), u32, u32, vp, vp, vp, u32, u32],
@@ -412,6 +414,23 @@ class SpMVPlan:
 
     def bfs_pull_step(self, bits_in, bits_out, distance, level):
         check(lib().gl_bfs_pull_step(ctypes.c_void_p(self.handle), _p(bits_in), _p(bits_out), _p(distance), float(level)))
+
+    def bfs_parents(self, distance, parent, orphans=None):
+        """gl_bfs_parents: the predecessor tree of the level vector `distance` (num_cols floats) for this plan's rows into
+        `parent` (uint32 words); `orphans`: an optional device word for the count of vertices without a predecessor."""
+        check(lib().gl_bfs_parents(ctypes.c_void_p(self.handle), _p(distance), _p(parent), _p(orphans)))
+
+    def bfs_parents_entries(self, distance, parent):
+        """gl_bfs_parents_entries: the same pass, returning the number of row entries it read (waits)."""
+        v = ctypes.c_uint64(0)
+        check(lib().gl_bfs_parents_entries(ctypes.c_void_p(self.handle), _p(distance), _p(parent), ctypes.byref(v)))
+        return v.value
+
+    def rows_sorted(self):
+        """gl_spmv_plan_rows_sorted: do the columns of every row of the plan's CSR copy ascend?"""
+        v = ctypes.c_int(0)
+        check(lib().gl_spmv_plan_rows_sorted(ctypes.c_void_p(self.handle), ctypes.byref(v)))
+        return bool(v.value)
 
     def run_bits(self, bits, mask, y, zero, mask_type):
         check(lib().gl_spmv_run_bits(ctypes.c_void_p(self.handle), _p(bits), _p(mask), _p(y), float(zero), int(mask_type)))

@@ -222,6 +222,10 @@ struct gl_spmv_plan_s {
     // d_csr_indices holds the shard's part starting at csr_nz_base)
     uint32_t *d_csr_indptr = nullptr, *d_csr_indices = nullptr;
     uint32_t csr_nz_base = 0;
+    // gl_bfs_parents (gl_bfs_parents.hip), both set up by the first call: do the valid columns of every row of that copy
+    // ascend (-1: not established yet), and the pass's scratch -- 256 bytes of control words + one byte per column
+    int rows_sorted = -1;
+    unsigned char *d_parents_scratch = nullptr;
     // GL_PLAN_REFERENCE_ORDER: the shard's plain CSR (indptr rebased to 0, values kept), evaluated a thread per row in
     // the reference's own order -- a diagnostic layout, not a fast one
     bool reference_order = false;

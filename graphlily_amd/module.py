@@ -253,6 +253,15 @@ class SpMVModule(BaseModule):
         self.plan_.bfs_pull_step(bits_in, bits_out, distance_buf, level)
         self._finish(bits_out, distance_buf)
 
+    def bfs_parents(self, distance_buf, parent_buf, orphans_buf=None):
+        """Extension (gl_bfs_parents): the BFS predecessor tree of the level vector in `distance_buf` (get_num_cols() floats)
+        for this module's rows, into `parent_buf` (uint32 words; 0xffffffff = none).  Raises GraphLilyError
+        (GL_ERR_UNSUPPORTED) when the plan keeps no row copy (only the (||,&&) layout does)."""
+        if self.plan_ is None:
+            _fatal("SpMVModule.bfs_parents: send_matrix_host_to_device first")
+        self.plan_.bfs_parents(distance_buf, parent_buf, orphans_buf)
+        self._finish(parent_buf)
+
     def fused_bfs_ok(self):
         if self.plan_ is None or not self._plan_serves(self.semiring_.op) or self.semiring_.zero != 0.0:
             return False

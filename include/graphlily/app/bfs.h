@@ -88,6 +88,8 @@ private:
     uint64_t nnz_global_ = 0;
     RowShards shards_;           // world of one unless set_comm() was called
     uint32_t push_iterations_ = 0;
+    DeviceBuffer last_levels_;   // parents(): the level vector of the last pull / push / pull_push, still on the device
+    uint32_t orphans_ = 0;
 
     bool schedule_ok_() {
         const char *e = getenv("GRAPHLILY_BFS_HOST_LOOP");
@@ -209,7 +211,27 @@ private:
             GRAPHLILY_CHECK(gl_buf_d2h(c.data(), ctl, 4u * s.ctl_words));
         }
         push_iterations_ = c[1];
+        last_levels_ = s.both;
         return result;
+    }
+
+    std::vector<uint32_t, aligned_allocator<uint32_t>> parents_(DeviceBuffer levels) {
+        const uint32_t n = matrix_num_rows_;
+        if (!kFloat) {
+            printf("BFS::parents(): needs float levels (val_t = float)\n");
+            exit(EXIT_FAILURE);
+        }
+        const uint32_t r0 = (shards_.world > 1 || shards_.comm) ? shards_.row_begin() : 0u;
+        if (shards_.comm) GRAPHLILY_CHECK(gl_dist_all_gather_f32(shards_.comm, (float *)levels.ptr(), shards_.bounds.data()));
+        DeviceBuffer par(sizeof(uint32_t) * ((size_t)n + 1));    // vertex numbers, then the orphan count
+        uint32_t *d_par = (uint32_t *)par.ptr();
+        GRAPHLILY_CHECK(gl_bfs_parents(SpMV_->plan_handle(), (const float *)levels.ptr(), d_par + r0, d_par + n));
+        if (shards_.comm) GRAPHLILY_CHECK(gl_dist_all_gather_f32(shards_.comm, (float *)d_par, shards_.bounds.data()));   // (32-bit words)
+        std::vector<uint32_t, aligned_allocator<uint32_t>> out((size_t)n + 1);
+        par.download(out.data(), sizeof(uint32_t) * ((size_t)n + 1));
+        orphans_ = out[n];
+        out.resize(n);
+        return out;
     }
 
     // ---- the reference's module-call sequences (bfs.h:106-219), for push() and as the fallback of the other two
@@ -320,12 +342,14 @@ public:
         SpMV_->send_mask_host_to_device(distance);
         bind_pull_();
         for (uint32_t iter = 1; iter <= num_iterations; iter++) pull_iteration_(iter);
+        last_levels_ = SpMV_->mask_buf;
         return SpMV_->send_mask_device_to_host();
     }
 
     aligned_dense_vec_t push(uint32_t source, uint32_t num_iterations) {
         start_push_(source);
         for (uint32_t iter = 1; iter <= num_iterations; iter++) push_iteration_(iter);
+        last_levels_ = SpMSpV_->mask_buf;
         return SpMSpV_->send_mask_device_to_host();
     }
 
@@ -345,8 +369,33 @@ public:
         std::cout << "SpMSpV runs for " << (iter - 1) << " iterations" << std::endl;
         switch_to_pull_();
         for (; iter <= num_iterations; iter++) pull_iteration_(iter);
+        last_levels_ = SpMSpV_->mask_buf;
         return SpMSpV_->send_mask_device_to_host();   // the mask of SpMV on the host is not valid
     }
+
+    // ---- extension: the predecessor tree (the reference's drivers return levels only).  parent[v] = v on the source (level 1),
+    // 0xffffffff on an unreached vertex (level 0), otherwise the SMALLEST u with an entry A[v, u] and level[u] == level[v] - 1:
+    // unique, whichever steps found the levels.  One pass over the rows from the finished level vector (gl_bfs_parents).
+    // parents(): the levels of this object's last pull / push / pull_push, still on the device; parents(distance): the given
+    // levels.  Row shards compute their rows from the whole level vector and all-gather the slices.
+    typedef std::vector<uint32_t, aligned_allocator<uint32_t>> aligned_parent_vec_t;
+    aligned_parent_vec_t parents() {
+        if (!last_levels_.valid()) {
+            printf("BFS::parents(): no pull / push / pull_push has run on this object; pass the level vector\n");
+            exit(EXIT_FAILURE);
+        }
+        return parents_(last_levels_);
+    }
+    aligned_parent_vec_t parents(const aligned_dense_vec_t &distance) {
+        if (distance.size() != matrix_num_rows_) {
+            printf("BFS::parents(): %zu levels for a matrix of %u rows\n", distance.size(), matrix_num_rows_);
+            exit(EXIT_FAILURE);
+        }
+        DeviceBuffer levels(sizeof(graphlily::val_t) * std::max<size_t>(distance.size(), 1));
+        if (!distance.empty()) levels.upload(distance.data(), sizeof(graphlily::val_t) * distance.size());
+        return parents_(levels);
+    }
+    uint32_t orphans() const { return orphans_; }   // vertices of level >= 2 without a predecessor in the last parents() (0 for a BFS result)
 
     // the reference's four wall-clock buckets (bfs.h:222-347) around the module-call sequence, every call followed by a device
     // synchronisation (the reference's module calls are blocking)

@@ -165,6 +165,14 @@ public:
         finish_();
         return true;
     }
+    // extension (gl_bfs_parents): the BFS predecessor tree of the level vector in `distance` (get_num_cols() floats) for this
+    // module's rows into `parent` (32-bit words, 0xffffffff = none); `orphans`: an optional device word for the number of
+    // vertices of level >= 2 without a predecessor.  Only the (||,&&) layout keeps the rows this pass walks.
+    void bfs_parents(DeviceBuffer distance, DeviceBuffer parent, uint32_t *orphans = nullptr) {
+        barrier_();
+        GRAPHLILY_CHECK(gl_bfs_parents(plan_, (const float *)distance.ptr(), (uint32_t *)parent.ptr(), orphans));
+        finish_();
+    }
     uint32_t get_num_rows() { return csr_matrix_float_.num_rows; }
     uint32_t get_num_cols() { return csr_matrix_float_.num_cols; }
     uint32_t get_nnz() { return csr_matrix_float_.adj_indptr[csr_matrix_float_.num_rows]; }

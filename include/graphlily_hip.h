@@ -260,6 +260,27 @@ int gl_spmv_run_bits(gl_spmv_plan plan, const uint32_t *d_bits, const float *d_m
  * row range starts on a multiple of 64 (GL_ERR_UNSUPPORTED otherwise: use the three calls).  Both bit vectors
  * have gl_spmv_plan_bits_words words, are 16-byte aligned and distinct. */
 int gl_bfs_pull_step(gl_spmv_plan plan, const uint32_t *d_bits_in, uint32_t *d_bits_out, float *d_distance, float level);
+/* Extension: the BFS PREDECESSOR TREE of a finished level array (the drivers return levels only, app/bfs.h:106-219).  Levels
+ * are the drivers' own: 1 on the source, it + 1 on a vertex reached in iteration it, 0 on an unreached one.  For the rows
+ * [row_begin,row_end) of the plan, whose row v lists the vertices v is pulled from:
+ *   parent[v] = v           where level[v] == 1,
+ *             = 0xffffffff  where level[v] == 0,
+ *             = min { u : A[v,u] != 0 and level[u] == level[v] - 1 }  otherwise; if there is no such u (the array is not a
+ *               BFS result) 0xffffffff, and the vertex counts as an ORPHAN.
+ * The minimum makes the result unique whatever the order of a row's entries and whichever steps the search took.  d_distance
+ * is the whole vector (num_cols floats), d_parent covers the plan's rows (row_end - row_begin words), *d_orphans (a device
+ * word, may be NULL) receives the number of orphans -- an output, not an error.  One pass over the plain CSR copy a
+ * GL_PLAN_BOOLEAN plan keeps for the bottom-up step (GL_ERR_UNSUPPORTED for a plan without it); a plan's first call also
+ * allocates num_cols + 256 bytes of scratch and establishes whether its rows' columns ascend (then a row's scan stops at
+ * its first match), so it synchronises once; later calls only enqueue, on the library's stream. */
+int gl_bfs_parents(gl_spmv_plan plan, const float *d_distance, uint32_t *d_parent, uint32_t *d_orphans);
+/* Measurement hook: the same pass, counting the row entries it reads (with early exit: a fraction of the shard's nnz);
+ * waits for the result.  Slower than gl_bfs_parents by the counting. */
+int gl_bfs_parents_entries(gl_spmv_plan plan, const float *d_distance, uint32_t *d_parent, uint64_t *entries_read);
+/* *sorted = 1 if the non-zero-valued columns of every row of the plan's CSR copy ascend (gl_bfs_parents exits early), 0 if
+ * not (it reads every entry).  Established on first use, then cached.  (gl_spmv_plan_desc keeps its size: callers compiled
+ * against an older header hold one.) */
+int gl_spmv_plan_rows_sorted(gl_spmv_plan plan, int *sorted);
 /* gl_spmv_run replaces enqueueTask(overlay, mode = 1) (module/spmv_module.h:471-475,
  * hw/overlay.cpp:308-330 -> hw/kernel_spmv_impl.h:392-819):
  *   y[r] = mask_r ? ( zero (+) sum_{i in row r} A_i (x) x[col_i] ) : 0
