@@ -18,6 +18,8 @@ Differences that do not change results:
   * vectors are allocated by the driver and bound into the modules, so the same buffers can be
     handed to the collective.
 """
+import collections
+import functools
 import os
 import time
 
@@ -26,7 +28,13 @@ import numpy as np
 from . import capi, io
 from . import module as M
 from .dist import Comm, partition_rows_by_nnz
+from .readback import BookKey, ReadbackBook
 
+
+# BFS's device-resident schedule (BFS._pull_push_bits): what a recorded hipGraph depends on (packed_read_back: the graph holds
+# the pack of levels [lo, lo + own) into the page-locked block), and how one call's levels come back (BFS._readback_plan)
+GraphKey = collections.namedtuple("GraphKey", "N threshold back pull_only packed_read_back lo own")
+ReadbackPlan = collections.namedtuple("ReadbackPlan", "lo hi own pbits can_pack as_bytes streamed in_graph")
 
 NO_PARENT = 0xFFFFFFFF      # BFS.parents(): the vertex has no predecessor (unreached, or an orphan of a non-BFS level array)
 
@@ -253,6 +261,13 @@ class BFS(_GraphApp):
         self.eWiseAdd_ = B.eWiseAddModule()
         for m in (self.SpMV_, self.DenseAssign_, self.SpMSpV_, self.SparseAssign_, self.eWiseAdd_):
             self.add_module(m)
+        self.gather_result_ = True      # knob: row shards all-gather the distances; False: every rank reads back its slice
+        self.time_schedule_ = False     # knob: leave the schedule's GPU time alone (no read-back in it) in schedule_ms_
+        self.schedule_ms_ = None        # GPU ms of the last run with time_schedule_ set
+        self.readback_ = None           # the last measured read-back: {"way", "packed_ms", "float_ms"}
+        self.levels_ = None             # BFS.parents(): the last run's levels on the device
+        self.bits_loop_ = None          # resources of the device-resident schedule (_bits_state), per matrix
+        self.results_ = self.bits_a_ = self.bits_b_ = None      # scratch of the module-call pull loop, per matrix
 
     def load_and_format_matrix(self, csr_float_npz_path, skip_empty_rows=True):
         csr = self._load(csr_float_npz_path)
@@ -285,7 +300,7 @@ class BFS(_GraphApp):
     # -- pull ------------------------------------------------------------------------------------
     def _bind_pull(self, vector, distance):
         B, n = self.backend, self.n_
-        results = getattr(self, "results_", None)     # scratch of the unfused path, kept across calls
+        results = self.results_     # scratch of the unfused path, kept across calls
         if results is None:
             results = self.results_ = B.alloc(n, np.float32)
         self.SpMV_.bind_vector_buf(vector)
@@ -309,7 +324,7 @@ class BFS(_GraphApp):
             if self.fused_ or self.comm.distributed:
                 # opaque 32-bit words, kept across calls: pack_bits / the fused step rewrite every word of the row
                 # range, words past it stay 0 from the allocation
-                if getattr(self, "bits_a_", None) is None:
+                if self.bits_a_ is None:
                     self.bits_a_, self.bits_b_ = B.alloc(words, np.float32), B.alloc(words, np.float32)
                     B.fill(self.bits_a_, 0.0, words)
                     B.fill(self.bits_b_, 0.0, words)
@@ -418,127 +433,180 @@ class BFS(_GraphApp):
         vector (n/8 bytes) and carries every rank's tallies (256 bytes each), from which every rank takes the same decision;
         every rank reads back ITS SLICE of the distances (`gather_result_` = True all-gathers them first).
 
-        Rounds 2-3 kept four earlier generations of this loop alive behind switches (a list-based gated schedule, two- and
-        three-launch slots); round 4 retired them: same-box A/B in profiles/r04_ab_schedules.txt.  What remains beside this
-        schedule is the reference's own module-call loop (GRAPHLILY_BFS_HOST_LOOP=1, and wherever the plans do not offer
-        the bit layout)."""
-        B, n, N = self.backend, self.n_, num_iterations
+        What remains beside this schedule is the reference's own module-call loop (GRAPHLILY_BFS_HOST_LOOP=1, and wherever the
+        plans do not offer the bit layout); the earlier generations of this loop: EXPERIMENTS.md R4.3.
+
+        The phases, in the order they run: _bits_state, _emulation_inputs, _result_range, _readback_plan, _levels_block,
+        _launch_or_replay (_enqueue_bits_schedule, _enqueue_packed_levels), _gather_distances, _fetch_levels, _record_readback,
+        _publish_ctl."""
+        N, timed = num_iterations, self.time_schedule_
         self.fused_ = True          # (every pull step of this schedule is the fused one, see _bind_pull)
-        sharded = self.comm.distributed
-        st = getattr(self, "bits_loop_", None)
-        if st is None or st["N"] < N:
-            words = (int(self.SpMV_.bits_words()) + 3) & ~3
-            nvec, ctl_words = N + 2, (18 + 2 * N + 15) & ~15
-            both = B.alloc(n + ctl_words, np.float32)          # distances, then the control words: one read-back fetches both
-            # row shards: the ranks' tallies (gl_bfs_bits_shard_step) live behind the bit vectors and are cleared with them
-            tally_words = capi.bfs_tally_words(N, self.comm.world_size)
-            nvec_all = nvec + (tally_words + words - 1) // words
-            vecs = B.alloc(nvec_all * words, np.float32)
-            st = self.bits_loop_ = {"N": N, "both": both, "vecs": vecs, "words": words, "nvec": nvec, "ctl_words": ctl_words,
-                                    "ctl": B.view(both, n, ctl_words, 4), "distance": B.view(both, 0, n, 4),
-                                    "bits": [B.view(vecs, k * words, words, 4) for k in range(nvec)], "graphs": {},
-                                    "src": np.zeros(1, np.uint32), "warm": set(), "nvec_all": nvec_all}
-            st["col_len"] = capi.DeviceBuffer.from_host(self.col_len_)
-            st["tally"] = B.view(vecs, nvec * words, tally_words, 4)
-            if sharded:
-                st["row_len"] = capi.DeviceBuffer.from_host(self.row_len_)
-        ctl, distance, bits, words = st["ctl"], st["distance"], st["bits"], st["words"]
+        st = self._bits_state(N)
+        gathered, tally_in = self._emulation_inputs(st, source, N)
         # Once the reference's rule has switched to pulling (frontier / n >= threshold, app/bfs.h:180-190), every later slot is
         # handed back to the push step (an extension: the reference pulls to the end), which leaves heavy frontiers to the
         # streaming pull anyway: from then on the direction follows the work.  Distances do not depend on the direction.
         back = 0.0 if pull_only else 1.0
-        csc_plan, pull_plan = self.SpMSpV_.plan_, self.SpMV_.plan_
-        # (one-GPU emulation of a rank without an exchange step, dist.EmulatedComm: the slots read the whole run's vectors)
-        gathered = bits
-        if sharded and getattr(self.comm, "emulated", False) and not self.comm.copy:
-            gathered = [self.comm.truth_vector(k) for k in range(st["nvec"])]
-        rank, world = self.comm.rank, self.comm.world_size
-        tally, tally_in = st.get("tally"), None
-        if getattr(self.comm, "emulated", False):
-            table = self.comm.truth_tally((source, N), N, self.bounds_, self.col_len_, self.row_len_, n)
-            tally_in = None if self.comm.copy else table
+        sliced, lo, hi = self._result_range()
+        book = st["readback"][BookKey(N, float(threshold), back, pull_only, lo, hi - lo)]
+        plan = self._readback_plan(N, lo, hi, sliced, timed, book)
+        t_call = time.perf_counter()
+        self._levels_block(st, plan)
+        capi.fill_u32(self.backend.view(st["ctl"], capi.GL_BFS_CTL_SOURCE, 1, 4), int(source), 1)   # (a device word: replays take any source)
+        key = GraphKey(N, float(threshold), back, pull_only, plan.in_graph, lo, plan.own)
+        enqueue = functools.partial(self._enqueue_bits_schedule, st, N, threshold, pull_only, back, gathered, tally_in)
+        replayed = self._launch_or_replay(st, key, enqueue, functools.partial(self._enqueue_packed_levels, st, plan))
+        if not sliced:
+            self._gather_distances(st)
+        res, c = self._fetch_levels(st, plan, replayed)
+        if plan.can_pack and not timed:
+            self._record_readback(book, plan, time.perf_counter() - t_call)
+        self.result_range_ = (lo, hi)
+        # BFS.parents(): this run's levels stay in the schedule's buffer (a rank that read back only its slice holds only its
+        # rows of them: parents() all-gathers first)
+        # (plain handles, no closure over self: a reference cycle would leave the driver's plans and buffers to the garbage collector)
+        self.levels_ = (st["distance"], st["both"] if sliced else None)
+        self._publish_ctl(c, N, st["ctl_words"])
+        return res
+
+    def _result_range(self):
+        """-> (sliced, lo, hi): a row shard with `gather_result_` off reads back its own rows [lo, hi) only."""
+        sliced = self.comm.distributed and not self.gather_result_
+        return (sliced, self.r0_, self.r1_) if sliced else (sliced, 0, self.n_)
+
+    def _gather_distances(self, st):
+        """Row shards: every rank's rows of the distances to every rank, behind the schedule."""
+        if self.comm.distributed:
+            both = st["both"]
+            self.comm.all_gather_slices(both.tensor[:self.n_] if both.tensor is not None else both, self.bounds_)
+
+    def _record_readback(self, book, plan, seconds):
+        """A whole call that could have gone either way is a measurement of the way it went."""
+        way = "packed" if plan.as_bytes else "float"
+        book.record(way, seconds)
+        self.readback_ = book.report(way)
+
+    def _bits_state(self, N):
+        """self.bits_loop_, built on the first run and again when a run needs more slots than it has (send_matrix_host_to_device
+        drops it).  A plain dict of resources:
+          N, nvec, nvec_all, words, ctl_words   slots it serves; bit vectors (N + 2), those plus the room of the tallies; 32-bit
+                                                words of a bit vector and of the control words
+          both, distance, ctl                   n distances and the control words behind them (one read-back fetches both); views
+          vecs, bits, tally                     the bit vectors in one allocation; a view of each; the ranks' tallies behind them
+                                                (gl_bfs_bits_shard_step), cleared with them
+          col_len, row_len                      the GLOBAL column (and, row-sharded, row) lengths on the device
+          graphs, warm, graph_error             GraphKey -> recorded hipGraph (False: capture failed, the message is in
+                                                graph_error); the keys enqueued once
+          readback                              the packed-or-float books: BookKey -> readback.ReadbackBook
+          lev8_key, lev8, h8                    (_levels_block) the packed read-back's device and page-locked blocks"""
+        st = self.bits_loop_
+        if st is not None and st["N"] >= N:
+            return st
+        B, n = self.backend, self.n_
+        words = (int(self.SpMV_.bits_words()) + 3) & ~3
+        nvec, ctl_words = N + 2, (18 + 2 * N + 15) & ~15
+        both = B.alloc(n + ctl_words, np.float32)
+        tally_words = capi.bfs_tally_words(N, self.comm.world_size)
+        nvec_all = nvec + (tally_words + words - 1) // words
+        vecs = B.alloc(nvec_all * words, np.float32)
+        st = self.bits_loop_ = {"N": N, "both": both, "vecs": vecs, "words": words, "nvec": nvec, "ctl_words": ctl_words,
+                                "ctl": B.view(both, n, ctl_words, 4), "distance": B.view(both, 0, n, 4),
+                                "bits": [B.view(vecs, k * words, words, 4) for k in range(nvec)], "graphs": {},
+                                "warm": set(), "nvec_all": nvec_all, "readback": collections.defaultdict(ReadbackBook)}
+        st["col_len"] = capi.DeviceBuffer.from_host(self.col_len_)
+        st["tally"] = B.view(vecs, nvec * words, tally_words, 4)
+        if self.comm.distributed:
+            st["row_len"] = capi.DeviceBuffer.from_host(self.row_len_)
+        return st
+
+    def _emulation_inputs(self, st, source, N):
+        """-> (the bit vectors the slots read, the tally table they read).  A real run reads its own: (st["bits"], None).  The
+        one-GPU emulation of a rank (dist.EmulatedComm) has the whole run's tallies computed, and without an exchange step
+        (copy=False) its slots read the whole run's vectors and tallies."""
+        comm = self.comm
+        if not getattr(comm, "emulated", False):
+            return st["bits"], None
+        table = comm.truth_tally((source, N), N, self.bounds_, self.col_len_, self.row_len_, self.n_)
+        if comm.copy:
+            return st["bits"], None
+        return [comm.truth_vector(k) for k in range(st["nvec"])], table
+
+    def _enqueue_bits_schedule(self, st, N, threshold, pull_only, back, gathered, tally_in):
+        """The launches of one run: begin, one step per slot (and its exchange, row-sharded), finish."""
+        ctl, distance, bits, words, tally, col_len = st["ctl"], st["distance"], st["bits"], st["words"], st["tally"], st["col_len"]
+        csc_plan, pull_plan, nnz = self.SpMSpV_.plan_, self.SpMV_.plan_, self.nnz_global_
+        rank, world, sharded = self.comm.rank, self.comm.world_size, self.comm.distributed
 
         def may_of(it):
             return (1 if it + 1 < N else 0) | (2 if it + 1 <= N else 0)
 
-        def schedule():
-            capi.bfs_bits_begin(ctl, st["ctl_words"], distance, n, st["vecs"], words, st["nvec_all"], 0 if pull_only else 0xffffffff)
-            for it in range(1, N + 1):
-                capi.bfs_bits_shard_step(csc_plan, pull_plan, gathered[it], bits[it + 1], words, distance, float(it + 1), ctl, tally,
-                                         tally_in, it, rank, world, st["col_len"], self.nnz_global_, threshold,
-                                         may_of(it - 1) if it > 1 else 0, back)
-                if sharded:
-                    self._exchange_bits(st, it + 1, it)
-            capi.bfs_bits_shard_finish(csc_plan, pull_plan, ctl, tally, tally_in, N, rank, world, self.nnz_global_, threshold, may_of(N), back)
+        capi.bfs_bits_begin(ctl, st["ctl_words"], distance, self.n_, st["vecs"], words, st["nvec_all"], 0 if pull_only else 0xffffffff)
+        for it in range(1, N + 1):
+            capi.bfs_bits_shard_step(csc_plan, pull_plan, gathered[it], bits[it + 1], words, distance, float(it + 1), ctl, tally,
+                                     tally_in, it, rank, world, col_len, nnz, threshold, may_of(it - 1) if it > 1 else 0, back)
+            if sharded:
+                self._exchange_bits(st, it + 1, it)
+        capi.bfs_bits_shard_finish(csc_plan, pull_plan, ctl, tally, tally_in, N, rank, world, nnz, threshold, may_of(N), back)
 
-        # Levels are small integers: when they fit a byte (N + 1 <= 255; a nibble up to 14 iterations) the result crosses PCIe
-        # PACKED -- 1.5 or 3 MB instead of 12 MB on orkut, 28 or 55 us instead of 225, the control words behind them in the
-        # same copy -- and a few host threads turn them into the floats the caller gets (woken while the GPU is still busy).
-        # GRAPHLILY_BFS_U8=0: the floats themselves.  The pack and the copy kernel are part of the recorded schedule (fixed
-        # buffers) unless the bench wants the schedule's GPU time alone, or the distances are all-gathered first.
-        cw = st["ctl_words"]
-        timed = getattr(self, "time_schedule_", False)      # bench: GPU time of the schedule without the read-back
-        sliced = sharded and not getattr(self, "gather_result_", True)
-        lo, hi = (self.r0_, self.r1_) if sliced else (0, n)
+    def _readback_plan(self, N, lo, hi, sliced, timed, book):
+        """How this call's levels [lo, hi) come back.  Levels are small integers: when they fit a byte (N + 1 <= 255; a nibble up
+        to 14 iterations) the result can cross PCIe PACKED -- 1.5 or 3 MB instead of 12 MB on orkut, 28 or 55 us instead of 225,
+        the control words behind them in the same copy -- and a few host threads turn them into the floats the caller gets
+        (woken while the GPU is still busy).  The packed way is possible (can_pack) from half a million rows on: in a
+        same-machine A/B (profiles/r04_ab_schedules.txt) the googleplus stand-in's 108 K levels, 0.43 MB as floats, came back
+        24 us SOONER unpacked, ogbl-ppa's 576 K tie, hollywood's 1 M gain 22 us packed.  Where it is possible, `book` (this
+        schedule's readback.ReadbackBook) chooses between packed and floats from what it has measured (as_bytes);
+        GRAPHLILY_BFS_U8=0 / =2 pin the float / packed way.  The pack is part of the recorded schedule (fixed buffers) unless
+        the schedule's GPU time alone is wanted, or the distances are all-gathered first.  The pack kernel stores into the
+        page-locked block itself, chunk by chunk with a flag behind each, and the host threads expand a chunk as soon as it has
+        landed -- the expansion overlaps the PCIe transfer (GRAPHLILY_BFS_STREAM=0: pack -> copy -> wait -> expand)."""
         own = hi - lo
-        pbits = 4 if N + 1 <= 15 else 8
-        # (from half a million rows on: same-box A/B, profiles/r04_ab_schedules.txt -- the googleplus stand-in's 108 K levels are
-        # 0.43 MB as floats and came back 24 us SOONER unpacked, ogbl-ppa's 576 K tie, hollywood's 1 M gain 22 us packed)
-        can_pack = (N + 1 <= 255 and own % 8 == 0 and lo % 4 == 0 and own >= (1 << 19)
-                    and os.environ.get("GRAPHLILY_BFS_U8", "1") != "0" and capi.host_unpack_threads() >= 4)
-        # The packed read-back's second half runs on HOST threads: on a busy box it loses to the plain float copy (round 3:
-        # 0.39 - 0.52 ms for the same call over the round's boxes; same-box, same-process spread 0.39 - 0.55).  So the driver
-        # MEASURES: both ways are timed (whole call), the faster one by the MEDIAN of its last seven calls is used, and every
-        # 32nd call tries the other one again.  The books are kept per schedule (pull and pull_push each have their own: round 4
-        # kept one exponential average for both, and the first calls of the second mode -- which enqueue and record its graph,
-        # 12 ms -- poisoned the average of whichever way was active: the mode measured second ran on the slower way, 33 %
-        # apart between two legs of one bench process).  GRAPHLILY_BFS_U8=0 / =2 pin the float / packed way.
-        rb = st.setdefault("readback", {}).setdefault((N, float(threshold), back, pull_only, lo, own),
-                                                      {"packed": None, "float": None, "calls": 0, "t_packed": [], "t_float": []})
         pin = os.environ.get("GRAPHLILY_BFS_U8", "1")
-        if not can_pack or timed:
-            as_bytes = can_pack
-        elif pin == "2" or rb["packed"] is None:
-            as_bytes = True
-        elif rb["float"] is None:
-            as_bytes = rb["calls"] < 8        # (the first calls warm up and record the packed way's graph)
-        else:
-            better = rb["packed"] <= rb["float"]
-            as_bytes = better if rb["calls"] % 32 != 31 else not better
-        t_call = time.perf_counter()
-        in_graph = as_bytes and not timed and (sliced or not sharded)
-        # Round 6: the pack kernel stores into the page-locked block itself, chunk by chunk with a flag behind each, and the host
-        # threads expand a chunk as soon as it has landed -- the expansion overlaps the PCIe transfer (GRAPHLILY_BFS_STREAM=0: the
-        # round-5 way, pack -> copy -> wait -> expand)
+        can_pack = (N + 1 <= 255 and own % 8 == 0 and lo % 4 == 0 and own >= (1 << 19)
+                    and pin != "0" and capi.host_unpack_threads() >= 4)
+        as_bytes = book.choose(can_pack, timed, pin)
+        in_graph = as_bytes and not timed and (sliced or not self.comm.distributed)
         streamed = as_bytes and os.environ.get("GRAPHLILY_BFS_STREAM", "1") != "0"
-        if as_bytes:
-            pw = capi.levels_packed_words(own, pbits)
-            if st.get("lev8_key") != (own, pbits, streamed):
-                st["lev8_key"] = (own, pbits, streamed)
-                st["lev8"] = None if streamed else capi.DeviceBuffer(4 * (pw + cw))
-                st["h8"] = capi.pinned_empty(capi.levels_stream_bytes(own, pbits, cw) if streamed else 4 * (pw + cw), np.uint8)
-                st["graphs"] = {k: v for k, v in st["graphs"].items() if not k[5]}   # (graphs that recorded the old buffers)
-            if streamed:
-                capi.levels_stream_arm(st["h8"], own, pbits, cw)      # (before anything of this run is launched)
+        return ReadbackPlan(lo, hi, own, 4 if N + 1 <= 15 else 8, can_pack, as_bytes, streamed, in_graph)
 
-        def packed_read_back():
-            if streamed:
-                capi.levels_pack_stream(B.view(distance, lo, own, 4), own, pbits, ctl, cw, st["h8"])
-                return
-            capi.levels_pack(B.view(distance, lo, own, 4), own, pbits, ctl, cw, st["lev8"])   # (levels, then the control words)
-            st["lev8"].read_async(st["h8"])
+    def _levels_block(self, st, plan):
+        """The blocks a packed read-back lands in, kept while (own, bits per level, streamed) stay: a change drops the graphs
+        that recorded the old ones.  A streamed block is armed here: before anything of this run is launched."""
+        if not plan.as_bytes:
+            return
+        own, pbits, streamed, cw = plan.own, plan.pbits, plan.streamed, st["ctl_words"]
+        if st.get("lev8_key") != (own, pbits, streamed):
+            nbytes = 4 * (capi.levels_packed_words(own, pbits) + cw)
+            st["lev8_key"] = (own, pbits, streamed)
+            st["lev8"] = None if streamed else capi.DeviceBuffer(nbytes)
+            st["h8"] = capi.pinned_empty(capi.levels_stream_bytes(own, pbits, cw) if streamed else nbytes, np.uint8)
+            st["graphs"] = {k: g for k, g in st["graphs"].items() if not k.packed_read_back}
+        if streamed:
+            capi.levels_stream_arm(st["h8"], own, pbits, cw)
 
-        capi.fill_u32(B.view(ctl, 2, 1, 4), int(source), 1)   # ctl[2] = source (see _pull_push_device)
-        key = (N, float(threshold), back, pull_only, True, in_graph, lo, own)
+    def _enqueue_packed_levels(self, st, plan):
+        """The device half of the packed read-back: levels [lo, hi), then the control words, into the page-locked block."""
+        levels, cw = self.backend.view(st["distance"], plan.lo, plan.own, 4), st["ctl_words"]
+        if plan.streamed:
+            capi.levels_pack_stream(levels, plan.own, plan.pbits, st["ctl"], cw, st["h8"])
+            return
+        capi.levels_pack(levels, plan.own, plan.pbits, st["ctl"], cw, st["lev8"])
+        st["lev8"].read_async(st["h8"])
+
+    def _launch_or_replay(self, st, key, enqueue, enqueue_levels):
+        """The schedule of `key` (`enqueue()`; key.packed_read_back: `enqueue_levels()` behind it in the recording): enqueued on
+        the first call, recorded as a hipGraph on the second, replayed from then on.  -> whether a graph ran.  With
+        `time_schedule_` the run's GPU time is left in `schedule_ms_`."""
+        timed = self.time_schedule_
         g = st["graphs"].get(key)
         # (a torch.distributed collective is not recorded by the library's capture: those runs are enqueued call by call)
-        capturable = not sharded or getattr(self.comm, "capturable", False)
+        capturable = not self.comm.distributed or getattr(self.comm, "capturable", False)
         if g is None and capturable and key in st["warm"]:
             try:
                 with capi.Graph.capture() as g:
-                    schedule()
-                    if in_graph:
-                        packed_read_back()
+                    enqueue()
+                    if key.packed_read_back:
+                        enqueue_levels()
                 st["graphs"][key] = g
             except capi.GraphLilyError as e:
                 g = st["graphs"][key] = False              # capture not possible here: keep enqueueing
@@ -548,55 +616,41 @@ class BFS(_GraphApp):
         if g:
             g.launch()
         else:
-            schedule()
+            enqueue()
             st["warm"].add(key)
         if timed:
             self.schedule_ms_ = capi.span_end()
-        if sharded and not sliced:
-            self.comm.all_gather_slices(st["both"].tensor[:n] if st["both"].tensor is not None else st["both"], self.bounds_)
-        if as_bytes:
-            if not (g and in_graph):
-                packed_read_back()
-            res = capi.pinned_recycled(own, np.float32)       # (recycled: already paged in)
-            if streamed:
-                c = capi.sync_levels_unpack_stream(res, st["h8"], own, pbits, cw)   # (the host threads start now: chunk by chunk)
-            else:
-                capi.sync_levels_unpack(res, st["h8"], own, pbits)   # (the host threads start now and spin until the stream is done)
-                c = st["h8"][4 * pw:].view(np.uint32).copy()
-        else:
+        return bool(g)
+
+    def _fetch_levels(self, st, plan, replayed):
+        """Waits for the run.  -> (levels [lo, hi) as floats, the control words as uint32)."""
+        own, cw = plan.own, st["ctl_words"]
+        if not plan.as_bytes:
             # the distances (this rank's slice of them) + the control words: two copies behind the schedule, one wait
-            out = capi.pinned_recycled(own + cw, np.float32)
+            n, out = self.n_, capi.pinned_recycled(own + cw, np.float32)
             if own == n:
                 st["both"].read_async(out)                    # (the control words follow the distances: one copy)
             else:
-                st["both"].read_async(out[:own], 4 * lo)
+                st["both"].read_async(out[:own], 4 * plan.lo)
                 st["both"].read_async(out[own:], 4 * n)
-            B.sync()
-            res, c = out[:own], out[own:].view(np.uint32)
-        if can_pack and not timed:
-            # (the first two calls of a way enqueue / record its schedule: not what the steady state costs)
-            way, dt = ("packed" if as_bytes else "float"), time.perf_counter() - t_call
-            seen = rb.setdefault("n_" + way, 0)
-            rb["n_" + way] = seen + 1
-            if seen >= 2:
-                ts = rb["t_" + way]
-                ts.append(dt)
-                del ts[:-7]
-                rb[way] = float(np.median(ts))
-            rb["calls"] += 1
-            self.readback_ = {"way": way, "packed_ms": None if rb["packed"] is None else round(rb["packed"] * 1e3, 4),
-                              "float_ms": None if rb["float"] is None else round(rb["float"] * 1e3, 4)}
-        self.result_range_ = (lo, hi)
-        # BFS.parents(): this run's levels stay in the schedule's buffer (a rank that read back only its slice holds only its
-        # rows of them: parents() all-gathers first)
-        # (plain handles, no closure over self: a reference cycle would leave the driver's plans and buffers to the garbage collector)
-        self.levels_ = (distance, st["both"] if sliced else None)
-        self.push_iterations_ = int(c[1])          # the reference's count (first push phase)
-        self.push_iterations_again_ = int(c[3])    # pushes after a pull step handed back
-        S = (cw - 16) // 2
-        self.bfs_slot_counts_ = c[17:17 + N].copy()             # vertices reached per slot
-        self.bfs_slot_modes_ = c[17 + S:17 + S + N].copy()      # 1 scattered, 2 streamed row-wise, 3 bottom-up, 0 nothing ran
-        return res
+            self.backend.sync()
+            return out[:own], out[own:].view(np.uint32)
+        if not (replayed and plan.in_graph):
+            self._enqueue_packed_levels(st, plan)
+        res = capi.pinned_recycled(own, np.float32)       # (recycled: already paged in)
+        if plan.streamed:
+            return res, capi.sync_levels_unpack_stream(res, st["h8"], own, plan.pbits, cw)   # (the host threads start now: chunk by chunk)
+        capi.sync_levels_unpack(res, st["h8"], own, plan.pbits)   # (the host threads start now and spin until the stream is done)
+        return res, st["h8"][4 * capi.levels_packed_words(own, plan.pbits):].view(np.uint32).copy()
+
+    def _publish_ctl(self, c, N, ctl_words):
+        """The run's books from its control words (capi.GL_BFS_CTL_*)."""
+        counts = capi.GL_BFS_CTL_HEAD_WORDS + 1               # (slots are numbered from 1)
+        modes = counts + capi.bfs_ctl_slots(ctl_words)
+        self.push_iterations_ = int(c[capi.GL_BFS_CTL_PUSHES])                # the reference's count (first push phase)
+        self.push_iterations_again_ = int(c[capi.GL_BFS_CTL_PUSHES_AGAIN])    # pushes after a pull step handed back
+        self.bfs_slot_counts_ = c[counts:counts + N].copy()      # vertices reached per slot
+        self.bfs_slot_modes_ = c[modes:modes + N].copy()         # 1 scattered, 2 streamed row-wise, 3 bottom-up, 0 nothing ran
 
     def _exchange_bits(self, st, k, tally_slot):
         """The one exchange step of a sharded slot: every rank's rows of bit vector k to every rank, and every rank's tallies
@@ -656,7 +710,7 @@ class BFS(_GraphApp):
         rank's rows (0 for a BFS result)."""
         B, n = self.backend, self.n_
         if distance is None:
-            last = getattr(self, "levels_", None)
+            last = self.levels_
             if last is None:
                 raise RuntimeError("BFS.parents(): no pull / push / pull_push has run on this object; pass the level array")
             levels, partial = last

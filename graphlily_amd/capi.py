@@ -658,10 +658,20 @@ def bfs_bits_pull_step(pull_plan, csc_plan, bits_in, bits_out, distance, level, 
                                       float(back_threshold)))
 
 
-
-
 GL_BFS_TALLY_HEAD_WORDS = 64
 GL_BFS_TALLY_RANK_WORDS = 64
+
+# The control words of the bit-frontier schedule, as far as the host reads or writes them (the layout is BfsBitsCtl's,
+# csrc/gl_common.h:269-327): 16 header words, then two arrays of S = (ctl_words - 16) / 2 entries, one per slot s = 1..N
+GL_BFS_CTL_PUSHES = 1            # push iterations of the first push phase (the reference's count)
+GL_BFS_CTL_SOURCE = 2            # the source vertex
+GL_BFS_CTL_PUSHES_AGAIN = 3      # pushes after a pull step handed the loop back
+GL_BFS_CTL_HEAD_WORDS = 16       # slot s: vertices reached at HEAD_WORDS + s, how it was evaluated at HEAD_WORDS + S + s
+
+
+def bfs_ctl_slots(ctl_words):
+    """S: the entries of each of the two per-slot arrays behind the header"""
+    return (int(ctl_words) - GL_BFS_CTL_HEAD_WORDS) // 2
 
 
 def bfs_tally_words(slots, world):

@@ -189,7 +189,7 @@ class EmulatedComm:
         return True
 
     def set_truth(self, vecs_buf, words):
-        """vecs_buf: the (N + 2) x words bit vectors a whole-matrix BFS._pull_push_bits left behind (device)."""
+        """vecs_buf: the (N + 2) x words bit vectors a whole-matrix BFS run left behind (device): bits_loop_["vecs"], app.BFS._bits_state."""
         self.truth, self.truth_words = vecs_buf, int(words)
 
     def exchange_bits(self, bits_buf, k, bounds, tally_slot_buf=None, tally_slot=None):
