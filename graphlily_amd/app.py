@@ -100,6 +100,75 @@ def validate_bfs_tree(csr, source, distance, parent, num_iterations=None):
     return int(reached.sum())
 
 
+def validate_sssp_tree(csr, source, distance, parent, unreached=M.FLOAT_INF, converged=True):
+    """Host-side check (numpy) that `parent` is a shortest-path tree of `csr` -- row v lists the vertices v is pulled from, every
+    stored entry is an edge, weight 0 included -- consistent with the distances `distance` (0 on the source, `unreached` where no
+    path was found).  All sums are formed in float32, as the (min,+) operators form them.  Raises ValueError naming the first
+    offending vertex and the rule; returns the number of reached vertices.  The rules (Graph500's SSSP checks, in the drivers' terms):
+      1. the source has distance 0 and is its own parent;
+      2. a vertex is reached (d < unreached) exactly if it has a parent;
+      3. parent[v] is a vertex, some stored entry A[v, parent[v]] of weight w has (float)(d[p] + w) == d[v], and d[p] < d[v];
+      4. with `converged`: no stored entry A[v, u] with u reached has (float)(d[u] + w) < d[v] -- v unreached included.  A run
+         that was cut short (too few iterations) is checked with converged=False.
+    `distance` / `parent` may be longer than the matrix (the drivers pad it): the extra vertices have empty rows."""
+    indptr = np.asarray(csr.adj_indptr).astype(np.int64)
+    nr = int(csr.num_rows)
+    d = np.asarray(distance, dtype=np.float32)
+    p = np.asarray(parent).astype(np.int64)
+    n = d.shape[0]
+    if p.shape[0] != n or n < max(nr, int(csr.num_cols)):
+        raise ValueError("validate_sssp_tree: %d distances and %d parents for a %d x %d matrix" % (n, p.shape[0], nr, csr.num_cols))
+
+    def first(bad):
+        return int(np.flatnonzero(bad)[0])
+
+    source = int(source)
+    if d[source] != 0 or p[source] != source:
+        raise ValueError("validate_sssp_tree: source %d has distance %g and parent %d (rule 1)" % (source, d[source], p[source]))
+    reached, has_parent = d < np.float32(unreached), p != NO_PARENT
+    if np.any(reached != has_parent):
+        v = first(reached != has_parent)
+        raise ValueError("validate_sssp_tree: vertex %d has distance %g and parent %s (rule 2)" % (v, d[v], "none" if p[v] == NO_PARENT else p[v]))
+    child = reached.copy()
+    child[source] = False
+    if np.any(child & ((p < 0) | (p >= n))):
+        v = first(child & ((p < 0) | (p >= n)))
+        raise ValueError("validate_sssp_tree: vertex %d has parent %d, which is no vertex (rule 3)" % (v, p[v]))
+    pc = np.where(child, p, 0)
+    is_entry = np.zeros(n, dtype=bool)
+    tight = np.zeros(n, dtype=bool)
+    step = 1 << 18                       # rows per block: bounds the temporaries on matrices of 1e8 entries
+    for r0 in range(0, nr, step):
+        r1 = min(nr, r0 + step)
+        lo, hi = indptr[r0], indptr[r1]
+        if hi == lo:
+            continue
+        cols = np.asarray(csr.adj_indices[lo:hi]).astype(np.int64)
+        through = d[cols] + np.asarray(csr.adj_data[lo:hi], dtype=np.float32)      # float32 + float32
+        rows = np.repeat(np.arange(r0, r1, dtype=np.int64), np.diff(indptr[r0:r1 + 1]))
+        to_parent = cols == p[rows]
+        is_entry[rows[to_parent]] = True
+        tight[rows[to_parent & (through == d[rows])]] = True
+        if converged:
+            bad = reached[cols] & (through < d[rows])
+            if np.any(bad):
+                k = first(bad)
+                raise ValueError("validate_sssp_tree: entry A[%d, %d] gives %d the distance %r, it has %r (rule 4)"
+                                 % (rows[k], cols[k], rows[k], float(through[k]), float(d[rows[k]])))
+    if np.any(child & ~is_entry):
+        v = first(child & ~is_entry)
+        raise ValueError("validate_sssp_tree: vertex %d has parent %d, but the matrix has no entry A[%d, %d] (rule 3)" % (v, p[v], v, p[v]))
+    if np.any(child & ~tight):
+        v = first(child & ~tight)
+        raise ValueError("validate_sssp_tree: vertex %d at distance %r has parent %d at %r, and no entry A[%d, %d] makes up the difference (rule 3)"
+                         % (v, float(d[v]), p[v], float(d[p[v]]), v, p[v]))
+    if np.any(child & ~(d[pc] < d)):
+        v = first(child & ~(d[pc] < d))
+        raise ValueError("validate_sssp_tree: vertex %d at distance %r has parent %d at distance %r, which is not smaller (rule 3)"
+                         % (v, float(d[v]), p[v], float(d[p[v]])))
+    return int(reached.sum())
+
+
 class HipBackend:
     """Allocation / transfer hooks of the drivers.  The CPU tests substitute a stand-in with the
     same methods to exercise the distributed control flow over gloo."""
@@ -904,10 +973,17 @@ class SSSP(_GraphApp):
         self.eWiseAdd_ = B.eWiseAddModule()
         for m in (self.SpMV_, self.SpMSpV_, self.SparseAssign_, self.eWiseAdd_):
             self.add_module(m)
+        self.distance_ = None           # SSSP.parents(): (the last run's distances on the device, its source)
+        self.orphans_ = 0
 
-    def load_and_format_matrix(self, csr_float_npz_path, skip_empty_rows=True):
+    def load_and_format_matrix(self, csr_float_npz_path, skip_empty_rows=True, weighted=False):
+        """`weighted=False` is the reference's preparation (app/sssp.h:132: every weight becomes 1).  `weighted=True` (an
+        extension) keeps the matrix's weights and gives every row a weight-0 diagonal entry (io.sssp_zero_diagonal)."""
         csr = self._load(csr_float_npz_path)
-        io.sssp_add_self_edges(csr)                  # app/sssp.h:132 (_preprocess)
+        if weighted:
+            io.sssp_zero_diagonal(csr)
+        else:
+            io.sssp_add_self_edges(csr)              # app/sssp.h:132 (_preprocess)
         self._pad(csr)
         csc = io.csr2csc(csr)
         self._shard(csr)
@@ -917,6 +993,7 @@ class SSSP(_GraphApp):
         self.SpMSpV_.load_and_format_matrix(csc)
         self.n_ = self.SpMV_.get_num_rows()
         assert self.n_ == self.SpMV_.get_num_cols()
+        self.distance_ = None
 
     def _initial_distance(self, source):
         return self._new_dense(self.n_, self.semiring_.zero, source, 0.0)
@@ -937,10 +1014,12 @@ class SSSP(_GraphApp):
         finally:
             if chained:
                 self.SpMV_.chain(False)
+        self.distance_ = (vector, self.source_)     # SSSP.parents(): this run's distances, whole on every rank
         B.sync()
         return B.download_result(vector, n)
 
     def pull(self, source, num_iterations):
+        self.source_ = int(source)
         return self._pull_loop(self._initial_distance(source), 1, num_iterations)
 
     def _start_push(self, source):
@@ -973,6 +1052,7 @@ class SSSP(_GraphApp):
         for _ in range(num_iterations):
             self._push_iteration(frontier, local)
         self._gather(distance)
+        self.distance_ = (distance, int(source))
         self.backend.sync()
         return self.backend.download_result(distance, self.n_)
 
@@ -990,6 +1070,7 @@ class SSSP(_GraphApp):
         same-box it lost on five of six stand-ins, 3.60 against 3.18 ms on ogbn-products' 23 slots,
         profiles/r04_ab_schedules.txt -- retired in round 4.)"""
         n = self.n_
+        self.source_ = int(source)
         frontier, distance, candidates, local = self._start_push(source)
         it = 1
         while True:
@@ -1009,3 +1090,39 @@ class SSSP(_GraphApp):
         self.push_iterations_ = it - 1
         self._gather(distance)
         return self._pull_loop(distance, it, num_iterations)   # app/sssp.h:227-242
+
+    # -- predecessor tree (an extension: the reference's drivers return distances only) ---------------------------------------
+    def parents(self, distance=None, source=None):
+        """The shortest-path predecessor tree as uint32[n]: parent[source] = source, NO_PARENT (0xffffffff) where d[v] >= the
+        semiring's zero (unreached), otherwise the SMALLEST u with a stored entry A[v, u] of weight w, d[u] < d[v] and
+        (float)(d[u] + w) == d[v] -- unique, whichever mix of push / pull steps found the distances.  One pass over the CSC of
+        the SpMSpV module from the finished distance vector (gl_sssp_parents): `distance=None` takes the distances and the
+        source of this object's last pull / push / pull_push, which are still on the device; an array (n floats) is uploaded
+        and used instead, and needs its `source`.  Row shards compute their own rows from the whole vector and all-gather the
+        slices.  `orphans_` = reached vertices other than the source without such a u among this rank's rows: 0 for a
+        converged result with positive weights, usually not for one cut short or for the default preparation, some of whose
+        rows lack the self edge."""
+        B, n = self.backend, self.n_
+        if distance is None:
+            if self.distance_ is None:
+                raise RuntimeError("SSSP.parents(): no pull / push / pull_push has run on this object; pass the distance array and the source")
+            dist, last_source = self.distance_
+            source = last_source if source is None else source
+        else:
+            if source is None:
+                raise ValueError("SSSP.parents(): a distance array needs its source")
+            arr = np.ascontiguousarray(distance, dtype=np.float32)
+            if arr.shape != (n,):
+                raise ValueError("SSSP.parents(): the distance array has shape %s, the (padded) matrix has %d rows" % (arr.shape, n))
+            dist = B.alloc(n, np.float32)
+            B.upload(dist, arr)
+        source = int(source)
+        if not 0 <= source < n:
+            raise ValueError("SSSP.parents(): source %d of %d vertices" % (source, n))
+        par = B.alloc(n + 1, np.float32)      # (32-bit words: vertex numbers, then the orphan count)
+        self.SpMSpV_.sssp_parents(dist, self.semiring_.zero, source, self._own(par), B.view(par, n, 1, 4))
+        self._gather(par)
+        B.sync()
+        out = B.download(par, np.uint32, n + 1)
+        self.orphans_ = int(out[n])
+        return out[:n]

@@ -42,6 +42,7 @@ EXPORTS = [
     "gl_spmv_plan_bits_words", "gl_pack_bits", "gl_unpack_bits", "gl_bfs_bits_begin_from", "gl_spmv_run_bits", "gl_bfs_pull_step",
     "gl_bfs_parents", "gl_bfs_parents_entries", "gl_spmv_plan_rows_sorted",
     "gl_prof_begin", "gl_prof_end", "gl_span_begin", "gl_span_end",
+    "gl_sssp_parents", "gl_sssp_parents_entries",
     "gl_spmspv_plan_create", "gl_spmspv_plan_destroy", "gl_spmspv_plan_info", "gl_spmspv_run", "gl_spmspv_run_assign",
     "gl_spmspv_plan_attach_pull", "gl_spmspv_plan_hint", "gl_spmspv_plan_hint_work", "gl_spmspv_last_direction", "gl_spmspv_wait", "gl_spmspv_failed_runs",
     "gl_sparse_nnz", "gl_ewise_add", "gl_assign_dense", "gl_assign_sparse",
@@ -113,6 +114,7 @@ def lib():
         "gl_bfs_parents": [vp, vp, vp, vp], "gl_bfs_parents_entries": [vp, vp, vp, P(u64)], "gl_spmv_plan_rows_sorted": [vp, P(i32)],
         "gl_spmv_run": [vp, vp, vp, vp, i32, f32, i32],
         "gl_prof_begin": [u32, u32], "gl_prof_end": [P(ctypes.c_double), P(u32)], "gl_span_begin": [], "gl_span_end": [P(ctypes.c_double)],
+        "gl_sssp_parents": [vp, vp, f32, u32, vp, vp], "gl_sssp_parents_entries": [vp, vp, f32, u32, vp, P(u64)],
         "gl_spmspv_plan_create": [P(vp), u32, u32, vp, vp, vp, u32, u32],
         "gl_spmspv_plan_destroy": [vp], "gl_spmspv_plan_info": [vp, P(u64), P(u64)],
         "gl_spmspv_run": [vp, vp, vp, vp, i32, f32, i32],
@@ -486,6 +488,19 @@ class SpMSpVPlan:
     def run(self, vector, mask, result, op, zero, mask_type):
         check(lib().gl_spmspv_run(ctypes.c_void_p(self.handle), _p(vector), _p(mask), _p(result), int(op),
                                   float(zero), int(mask_type)))
+
+    def sssp_parents(self, distance, unreached, source, parent, orphans=None):
+        """gl_sssp_parents: the shortest-path predecessor tree of the distance vector `distance` (num_cols floats; `unreached` =
+        the semiring's zero) from `source`, for this plan's rows into `parent` (uint32 words); `orphans`: an optional device
+        word for the count of reached vertices without a predecessor."""
+        check(lib().gl_sssp_parents(ctypes.c_void_p(self.handle), _p(distance), float(unreached), int(source), _p(parent), _p(orphans)))
+
+    def sssp_parents_entries(self, distance, unreached, source, parent):
+        """gl_sssp_parents_entries: the same pass, returning the number of column entries it read (waits)."""
+        v = ctypes.c_uint64(0)
+        check(lib().gl_sssp_parents_entries(ctypes.c_void_p(self.handle), _p(distance), float(unreached), int(source), _p(parent),
+                                            ctypes.byref(v)))
+        return v.value
 
     def wait(self):
         """gl_spmspv_wait: block until the last run on this plan has written its results; returns the result count (None

@@ -69,6 +69,7 @@ struct gl_spmspv_plan_s {
     uint32_t longest_hint = 0;
     const void *bfs_rows_plan = nullptr;   // the SpMV plan whose rows the last gl_bfs_bits_push_step could scan bottom-up (or null)
     uint32_t *d_bfs_acc = nullptr;   // kBfsAccSlots x 32 words: the push step's totals, spread over 64 lines (see bfs_push_bits_kernel)
+    uint32_t *d_parents_ctl = nullptr;   // gl_sssp_parents: {orphans, -, entries read (64 bit)}, allocated by its first call
     uint64_t device_bytes = 0;
 };
 
@@ -897,6 +898,7 @@ int gl_spmspv_plan_destroy(gl_spmspv_plan p) {
     (void)hipFree(p->d_mode);
     (void)hipFree(p->d_long_chunks);
     (void)hipFree(p->d_bfs_acc);
+    (void)hipFree(p->d_parents_ctl);
     (void)hipFree(p->d_xdense);
     delete p;
     return GL_OK;
@@ -1403,6 +1405,7 @@ const void *spmspv_plan_bfs_rows(gl_spmspv_plan p) { return p->bfs_rows_plan; }
 const uint32_t *spmspv_plan_indptr(gl_spmspv_plan p) { return p->d_indptr; }
 uint32_t spmspv_plan_num_cols(gl_spmspv_plan p) { return p->num_cols; }
 uint32_t *spmspv_plan_bfs_acc(gl_spmspv_plan p) { return p->d_bfs_acc; }
+SpmspvCsc spmspv_plan_csc(gl_spmspv_plan p) { return SpmspvCsc{p->d_indptr, p->d_stream, p->num_cols, p->row_begin, p->row_end, &p->d_parents_ctl}; }
 bool spmspv_plan_whole(gl_spmspv_plan p, uint32_t num_rows) { return p->row_begin == 0 && p->row_end == p->num_rows && p->num_rows == num_rows; }
 
 int preload_spmspv() {

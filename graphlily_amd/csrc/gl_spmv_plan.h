@@ -343,6 +343,15 @@ const uint32_t *spmspv_plan_indptr(gl_spmspv_plan p);
 uint32_t spmspv_plan_num_cols(gl_spmspv_plan p);
 uint32_t *spmspv_plan_bfs_acc(gl_spmspv_plan p);   // 64 lines of 32 words: {new vertices, -, column lengths (64 bits)} of a push step
 bool spmspv_plan_whole(gl_spmspv_plan p, uint32_t num_rows);
+// gl_spmspv.hip: the shard's CSC as gl_sssp_parents (gl_sssp_parents.hip) walks it -- num_cols + 1 offsets into the stream of
+// {row, value bits}, rows global -- and the slot of that pass's 32 bytes of control words (allocated by its first call)
+struct SpmspvCsc {
+    const uint32_t *indptr;
+    const uint2 *stream;
+    uint32_t num_cols, row_begin, row_end;
+    uint32_t **ctl;
+};
+SpmspvCsc spmspv_plan_csc(gl_spmspv_plan p);
 // gl_spmspv.hip: forget `dying` wherever gl_spmspv_plan_attach_pull attached it
 void spmspv_detach_everywhere(gl_spmv_plan dying);
 // gl_spmv.hip: y initialisation for plans whose units fold into y

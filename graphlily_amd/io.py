@@ -129,3 +129,60 @@ def sssp_add_self_edges(csr_matrix):
     csr_matrix.adj_indptr = new_indptr.astype(np.uint32)
     csr_matrix.adj_indices = out_idx
     csr_matrix.adj_data = out_val
+
+
+def sssp_zero_diagonal(csr_matrix):
+    """The WEIGHTED preparation of SSSP (an extension: SSSP.load_and_format_matrix(weighted=True); sssp_add_self_edges above is
+    the reference's, which sets every weight to 1).  Weights are kept, and every one of the num_rows rows ends up with exactly
+    one diagonal entry of value 0, so that a (min,+) SpMV keeps the previous distance: an existing diagonal entry is set to 0
+    (further duplicates of it are dropped), otherwise the entry is inserted before the row's first column above the diagonal
+    -- in ascending position where the row's columns ascend.  In place.  Raises ValueError for a weight that is negative, NaN
+    or >= FLOAT_INF (the semiring's "unreached"), and for a matrix with more rows than columns (no diagonal to hold)."""
+    n = int(csr_matrix.num_rows)
+    if n > csr_matrix.num_cols:
+        raise ValueError("sssp_zero_diagonal: %d rows but %d columns: row %d has no diagonal" % (n, csr_matrix.num_cols, csr_matrix.num_cols))
+    indptr = csr_matrix.adj_indptr.astype(np.int64)[:n + 1]
+    nnz = int(indptr[n])
+    cols = csr_matrix.adj_indices[:nnz]
+    data = np.asarray(csr_matrix.adj_data[:nnz], dtype=np.float32)
+    bad = ~((data >= 0) & (data < np.float32(999999999.0)))          # (NaN fails both comparisons)
+    if np.any(bad):
+        k = int(np.flatnonzero(bad)[0])
+        raise ValueError("sssp_zero_diagonal: entry %d (row %d, column %d) has weight %r: weights must be >= 0 and < FLOAT_INF"
+                         % (k, int(np.searchsorted(indptr, k, side="right")) - 1, int(cols[k]), float(data[k])))
+    lens = np.diff(indptr)
+    row_of = np.repeat(np.arange(n, dtype=np.int64), lens)
+    diag = np.flatnonzero(cols == row_of)
+    rows_diag, first = np.unique(row_of[diag], return_index=True)    # (row_of ascends: the first hit of every row)
+    has = np.zeros(n, dtype=bool)
+    has[rows_diag] = True
+    keep = np.ones(nnz, dtype=bool)
+    keep[diag] = False
+    keep[diag[first]] = True
+    data = data.copy()
+    data[diag[first]] = 0.0
+    if not keep.all():
+        cols, data, row_of = cols[keep], data[keep], row_of[keep]
+        lens = np.bincount(row_of, minlength=n).astype(np.int64)
+        indptr = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(lens, out=indptr[1:])
+    pos_in_row = np.arange(cols.shape[0], dtype=np.int64) - indptr[row_of]
+    insert_at = lens.copy()                                          # after the last entry unless a larger column comes first
+    above = np.flatnonzero(cols > row_of)
+    rows_above, first = np.unique(row_of[above], return_index=True)
+    insert_at[rows_above] = pos_in_row[above[first]]
+    new_indptr = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(lens + ~has, out=new_indptr[1:])
+    if int(new_indptr[n]) > 0xFFFFFFFF:
+        raise ValueError("sssp_zero_diagonal: %d entries do not fit 32-bit offsets" % int(new_indptr[n]))
+    out_idx = np.empty(int(new_indptr[n]), dtype=np.uint32)
+    out_val = np.empty(int(new_indptr[n]), dtype=np.float32)
+    dest = new_indptr[row_of] + pos_in_row + (~has[row_of] & (pos_in_row >= insert_at[row_of]))
+    out_idx[dest] = cols
+    out_val[dest] = data
+    rows_ins = np.flatnonzero(~has)
+    out_idx[new_indptr[rows_ins] + insert_at[rows_ins]] = rows_ins.astype(np.uint32)
+    out_val[new_indptr[rows_ins] + insert_at[rows_ins]] = 0.0
+    csr_matrix.adj_indptr = new_indptr.astype(np.uint32)
+    csr_matrix.adj_indices = out_idx
+    csr_matrix.adj_data = out_val

@@ -336,6 +336,15 @@ class SpMSpVModule(BaseModule):
             spmv_module.pull_clients_.append(self)
         self._attach(spmv_module)
 
+    def sssp_parents(self, distance_buf, unreached, source, parent_buf, orphans_buf=None):
+        """Extension (gl_sssp_parents): the shortest-path predecessor tree of the distance vector in `distance_buf`
+        (get_num_cols() floats, `unreached` = the semiring's zero) from `source`, for this module's rows, into `parent_buf`
+        (uint32 words; 0xffffffff = none).  One pass over the CSC this module's plan keeps."""
+        if self.plan_ is None:
+            _fatal("SpMSpVModule.sssp_parents: send_matrix_host_to_device first")
+        self.plan_.sssp_parents(distance_buf, unreached, source, parent_buf, orphans_buf)
+        self._finish(parent_buf)
+
     def hint_vector_nnz(self, nnz):
         """Extension: the caller knows the next run's vector holds at most `nnz` entries (gl_spmspv_plan_hint)."""
         if self.plan_ is not None:

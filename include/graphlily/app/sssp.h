@@ -28,7 +28,12 @@
 #include "graphlily/io/data_loader.h"
 #include "graphlily/io/data_formatter.h"
 
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
 #include <iostream>
+#include <type_traits>
+#include <vector>
 
 namespace graphlily {
 namespace app {
@@ -89,6 +94,59 @@ inline void sssp_preprocess(CSRMatrix<float> &m) {
     m.adj_indptr[n] = out;
 }
 
+// The WEIGHTED preparation (an extension: load_and_format_matrix(path, skip_empty_rows, true)): weights are kept and every row
+// ends up with exactly one diagonal entry of value 0 -- an existing one is set to 0 (further duplicates of it are dropped),
+// otherwise it is inserted before the row's first column above the diagonal, in ascending position where the row's columns
+// ascend.  A weight that is negative, NaN or >= FLOAT_INF is refused.
+inline void sssp_zero_diagonal(CSRMatrix<float> &m) {
+    const uint32_t n = m.num_rows;
+    if (n > m.num_cols) {
+        printf("SSSP: %u rows but %u columns: row %u has no diagonal\n", n, m.num_cols, m.num_cols);
+        exit(EXIT_FAILURE);
+    }
+    const std::vector<uint32_t> old_ptr(m.adj_indptr.begin(), m.adj_indptr.end());
+    const std::vector<uint32_t> old_idx(m.adj_indices.begin(), m.adj_indices.end());
+    const std::vector<float> old_val(m.adj_data.begin(), m.adj_data.end());
+    std::vector<uint32_t> idx;
+    std::vector<float> val;
+    idx.reserve(old_idx.size() + n);
+    val.reserve(old_idx.size() + n);
+    for (uint32_t r = 0; r < n; r++) {
+        m.adj_indptr[r] = (uint32_t)idx.size();
+        bool has = false;
+        for (uint32_t i = old_ptr[r]; i < old_ptr[r + 1]; i++) has |= old_idx[i] == r;
+        bool placed = has, seen = false;
+        for (uint32_t i = old_ptr[r]; i < old_ptr[r + 1]; i++) {
+            const float w = old_val[i];
+            if (!(w >= 0.0f && w < 999999999.0f)) {
+                printf("SSSP: entry (%u, %u) has weight %g: weights must be >= 0 and < FLOAT_INF\n", r, old_idx[i], w);
+                exit(EXIT_FAILURE);
+            }
+            if (old_idx[i] == r) {
+                if (seen) continue;                // a duplicate of the diagonal
+                seen = true;                       // (the first one: kept, with weight 0)
+                idx.push_back(r);
+                val.push_back(0.0f);
+                continue;
+            }
+            if (!placed && old_idx[i] > r) {
+                idx.push_back(r);
+                val.push_back(0.0f);
+                placed = true;
+            }
+            idx.push_back(old_idx[i]);
+            val.push_back(w);
+        }
+        if (!placed) {
+            idx.push_back(r);
+            val.push_back(0.0f);
+        }
+    }
+    m.adj_indptr[n] = (uint32_t)idx.size();
+    m.adj_indices.assign(idx.begin(), idx.end());
+    m.adj_data.assign(val.begin(), val.end());
+}
+
 }  // namespace detail
 
 class SSSP : public app::ModuleCollection {
@@ -104,6 +162,10 @@ private:
     using aligned_sparse_vec_t = graphlily::aligned_sparse_vec_t;
     using aligned_dense_float_vec_t = graphlily::aligned_dense_float_vec_t;
     typedef graphlily::value_kind<graphlily::val_t> VK;
+    static constexpr bool kFloat = std::is_same<graphlily::val_t, float>::value;
+    DeviceBuffer last_distance_;   // parents(): the distance vector of the last pull / push / pull_push, still on the device
+    uint32_t last_source_ = 0;
+    uint32_t orphans_ = 0;
 
     // an n-element vector that holds `fill` everywhere and `at_source` at the source, made on the device
     // (a fresh DeviceBuffer per call is a block of the library's device POOL -- gl_buf_alloc hands back the block the previous call
@@ -158,9 +220,12 @@ public:
 
     uint32_t get_nnz() { return SpMV_->get_nnz(); }
 
-    void load_and_format_matrix(std::string csr_float_npz_path, bool skip_empty_rows) {
+    // weighted = false: the reference's preparation (every weight becomes 1).  weighted = true (an extension): the matrix's
+    // weights are kept and every row gets a weight-0 diagonal entry (detail::sssp_zero_diagonal).
+    void load_and_format_matrix(std::string csr_float_npz_path, bool skip_empty_rows = true, bool weighted = false) {
         CSRMatrix<float> csr_matrix = graphlily::io::load_csr_matrix_from_float_npz(csr_float_npz_path);
-        detail::sssp_preprocess(csr_matrix);
+        if (weighted) detail::sssp_zero_diagonal(csr_matrix);
+        else detail::sssp_preprocess(csr_matrix);
         graphlily::io::util_round_csr_matrix_dim(csr_matrix, num_channels_ * graphlily::pack_size, num_channels_ * graphlily::pack_size);
         CSCMatrix<float> csc_matrix = graphlily::io::csr2csc(csr_matrix);
         SpMV_->load_and_format_matrix(csr_matrix, skip_empty_rows);
@@ -168,6 +233,7 @@ public:
         matrix_num_rows_ = SpMV_->get_num_rows();
         matrix_num_cols_ = SpMV_->get_num_cols();
         assert(matrix_num_rows_ == matrix_num_cols_);
+        last_distance_ = DeviceBuffer();
     }
 
     void send_matrix_host_to_device() {
@@ -180,6 +246,8 @@ public:
         pull_loop_(1, num_iterations);
         aligned_dense_vec_t distance = SpMV_->send_vector_device_to_host();
         SpMV_->chain(false);
+        last_distance_ = SpMV_->vector_buf;
+        last_source_ = source;
         return distance;
     }
 
@@ -189,6 +257,8 @@ public:
             SpMSpV_->run();          // candidate distances of the frontier's neighbours
             SparseAssign_->run();    // relax: distance = min, the improved vertices are the next frontier
         }
+        last_distance_ = SpMSpV_->mask_buf;
+        last_source_ = source;
         return SpMSpV_->send_mask_device_to_host();
     }
 
@@ -207,8 +277,58 @@ public:
         pull_loop_(iter, num_iterations);
         aligned_dense_vec_t distance = SpMV_->send_vector_device_to_host();
         SpMV_->chain(false);
+        last_distance_ = SpMV_->vector_buf;
+        last_source_ = source;
         return distance;
     }
+
+    // ---- extension: the predecessor tree (the reference's drivers return distances only).  parent[source] = source, 0xffffffff
+    // where d[v] >= the semiring's zero (unreached), otherwise the SMALLEST u with a stored entry A[v, u] of weight w,
+    // d[u] < d[v] and (float)(d[u] + w) == d[v]: unique, whichever steps found the distances.  One pass over the CSC of the
+    // SpMSpV module from the finished distance vector (gl_sssp_parents).  parents(): the distances and source of this object's
+    // last pull / push / pull_push, still on the device; parents(distance, source): the given ones.
+    typedef std::vector<uint32_t, aligned_allocator<uint32_t>> aligned_parent_vec_t;
+    aligned_parent_vec_t parents() {
+        if (!last_distance_.valid()) {
+            printf("SSSP::parents(): no pull / push / pull_push has run on this object; pass the distance vector and the source\n");
+            exit(EXIT_FAILURE);
+        }
+        return parents_(last_distance_, last_source_);
+    }
+    aligned_parent_vec_t parents(const aligned_dense_vec_t &distance, uint32_t source) {
+        if (distance.size() != matrix_num_rows_) {
+            printf("SSSP::parents(): %zu distances for a matrix of %u rows\n", distance.size(), matrix_num_rows_);
+            exit(EXIT_FAILURE);
+        }
+        DeviceBuffer d(sizeof(graphlily::val_t) * std::max<size_t>(distance.size(), 1));
+        if (!distance.empty()) d.upload(distance.data(), sizeof(graphlily::val_t) * distance.size());
+        return parents_(d, source);
+    }
+    // reached vertices other than the source without a predecessor in the last parents(): 0 for a converged result with
+    // positive weights
+    uint32_t orphans() const { return orphans_; }
+
+private:
+    aligned_parent_vec_t parents_(DeviceBuffer distance, uint32_t source) {
+        const uint32_t n = matrix_num_rows_;
+        if (!kFloat) {
+            printf("SSSP::parents(): needs float distances (val_t = float)\n");
+            exit(EXIT_FAILURE);
+        }
+        if (source >= n) {
+            printf("SSSP::parents(): source %u of %u vertices\n", source, n);
+            exit(EXIT_FAILURE);
+        }
+        DeviceBuffer par(sizeof(uint32_t) * ((size_t)n + 1));    // vertex numbers, then the orphan count
+        SpMSpV_->sssp_parents(distance, (float)semiring_.zero, source, par, (uint32_t *)par.ptr() + n);
+        aligned_parent_vec_t out((size_t)n + 1);
+        par.download(out.data(), sizeof(uint32_t) * ((size_t)n + 1));
+        orphans_ = out[n];
+        out.resize(n);
+        return out;
+    }
+
+public:
 
     aligned_dense_float_vec_t compute_reference_results(uint32_t source, uint32_t num_iterations) {
         aligned_dense_float_vec_t input(matrix_num_rows_, semiring_.zero);

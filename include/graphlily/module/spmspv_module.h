@@ -179,6 +179,15 @@ public:
     void hint_vector_nnz(uint32_t nnz) {
         if (plan_) GRAPHLILY_CHECK(gl_spmspv_plan_hint(plan_, nnz));
     }
+    // extension (gl_sssp_parents): the shortest-path predecessor tree of the distance vector in `distance` (get_num_cols()
+    // floats; `unreached` = the semiring's zero) from `source` for this module's rows into `parent` (32-bit words, 0xffffffff
+    // = none); `orphans`: an optional device word for the number of reached vertices without a predecessor.  One pass over the
+    // CSC this module's plan keeps.
+    void sssp_parents(DeviceBuffer distance, float unreached, uint32_t source, DeviceBuffer parent, uint32_t *orphans = nullptr) {
+        barrier_();
+        GRAPHLILY_CHECK(gl_sssp_parents(plan_, (const float *)distance.ptr(), unreached, source, (uint32_t *)parent.ptr(), orphans));
+        finish_();
+    }
 
     void run() {
         barrier_();

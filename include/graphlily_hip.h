@@ -357,6 +357,27 @@ int gl_spmspv_failed_runs(gl_spmspv_plan plan, uint32_t *count);
  * own row is written and no other entry touches it.  d_inout == NULL is gl_spmspv_run. */
 int gl_spmspv_run_assign(gl_spmspv_plan plan, const gl_idx_val *d_vector, const float *d_mask,
                          gl_idx_val *d_result, int op, float zero, int mask_type, float *d_inout, float val);
+/* Extension: the SHORTEST-PATH PREDECESSOR TREE of a finished distance array (the SSSP drivers return distances only,
+ * app/sssp.h:141-243).  The plan's row v lists the vertices v is pulled from; `unreached` is the semiring's zero (FLOAT_INF
+ * in the drivers).  For the rows [row_begin,row_end) of the plan:
+ *   parent[source] = source,
+ *   parent[v] = 0xffffffff  where d[v] >= unreached,
+ *   parent[v] = min { u : A[v,u] is a stored entry with weight w, d[u] < d[v] and (float)(d[u] + w) == d[v] }  otherwise;
+ *               if there is no such u 0xffffffff, and the vertex counts as an ORPHAN.
+ * d[u] < d[v] is strict, so the result is a tree: weight-0 entries (the self edges among them) and absorbed ones
+ * (d + w == d) are never tree edges.  Duplicate entries are allowed.  A converged result with positive weights has no
+ * orphans, an unconverged one (too few iterations) usually has: *d_orphans (a device word, may be NULL) is an output, not an
+ * error.  d_distance is the whole vector (num_cols floats), d_parent covers the plan's rows (row_end - row_begin words).
+ * One pass over the CSC stream the plan keeps: reached columns scatter atomicMin(parent[v], u) for their tight entries, so the
+ * result does not depend on the order of arrival.  Needs num_rows <= num_cols (GL_ERR_UNSUPPORTED otherwise); source >=
+ * num_cols is GL_ERR_INVALID_ARG; an empty shard is GL_OK.  A plan's first call allocates 32 bytes of control words; no call
+ * synchronises: everything is enqueued on the library's stream. */
+int gl_sssp_parents(gl_spmspv_plan plan, const float *d_distance, float unreached, uint32_t source,
+                    uint32_t *d_parent, uint32_t *d_orphans /* may be NULL */);
+/* Measurement hook: the same pass, counting the column entries it reads (every entry of every reached column); waits for the
+ * result. */
+int gl_sssp_parents_entries(gl_spmspv_plan plan, const float *d_distance, float unreached, uint32_t source,
+                            uint32_t *d_parent, uint64_t *entries_read);   /* waits; for tests and the bench */
 
 /* Extensions that take the host out of the BFS loop (the reference reads the result count back every push
  * iteration to decide the direction, app/bfs.h:180-190, and converts the frontier on the host at the switch, :195-205).
