@@ -865,6 +865,7 @@ class PageRank(_GraphApp):
 
     def load_and_format_matrix(self, csr_float_npz_path, damping, skip_empty_rows=True):
         csr = self._load(csr_float_npz_path)
+        n_real = csr.num_rows
         self._pad(csr)
         io.util_normalize_csr_matrix_by_outdegree(csr)
         csr.adj_data = (csr.adj_data * np.float32(damping)).astype(np.float32)   # app/pagerank.h:67
@@ -873,6 +874,8 @@ class PageRank(_GraphApp):
         self.SpMV_.load_and_format_matrix(csr, skip_empty_rows)
         self.n_ = self.SpMV_.get_num_rows()
         assert self.n_ == self.SpMV_.get_num_cols()
+        self.n_real_, self.damping_ = n_real, float(damping)     # (solve: the vertices that are not padding; the damping in M)
+        self.dangling_bits_ = None
 
     def send_matrix_host_to_device(self):
         self.SpMV_.send_matrix_host_to_device()
@@ -919,6 +922,97 @@ class PageRank(_GraphApp):
         B.sync()
         return B.download_result(vector, n)
 
+
+    def _personalization(self, personalization):
+        """-> p of solve(): float32[n_], >= 0, 0 on the padding vertices, normalised in f64 to sum 1 before the cast"""
+        n, n0 = self.n_, self.n_real_
+        p = np.zeros(n, dtype=np.float64)
+        if personalization is None:
+            p[:n0] = 1.0 / n0
+            return p.astype(np.float32)
+        given = np.asarray(personalization, dtype=np.float64)
+        if given.ndim != 1 or given.shape[0] not in (n0, n):
+            raise ValueError("PageRank.solve: personalization has shape %r, expected (%d,) or (%d,)" % (given.shape, n0, n))
+        if not np.all(np.isfinite(given)) or np.any(given < 0):
+            raise ValueError("PageRank.solve: personalization has a negative or non-finite entry")
+        if np.any(given[n0:] != 0):
+            raise ValueError("PageRank.solve: personalization is not 0 on the padding vertices %d..%d" % (n0, n - 1))
+        total = float(np.cumsum(given[:n0])[-1])      # (in index order, like the C++ driver's loop: the same words in both)
+        if not (total > 0 and np.isfinite(total)):
+            raise ValueError("PageRank.solve: personalization has zero sum")
+        p[:n0] = given[:n0] / total
+        return p.astype(np.float32)
+
+    def _dangling_bits(self):
+        """The columns of the prepared (padded) matrix without a stored entry, one bit each: bit v % 32 of word v / 32.  From
+        the column indices kept since load; built on the first solve() after a load."""
+        if self.dangling_bits_ is None:
+            n = self.n_
+            dangling = np.bincount(self.SpMV_.csr_matrix_.adj_indices, minlength=n)[:n] == 0
+            self.dangling_bits_ = np.packbits(dangling, bitorder="little").view(np.uint8)
+            pad = (-self.dangling_bits_.shape[0]) % 4
+            self.dangling_bits_ = np.concatenate([self.dangling_bits_, np.zeros(pad, np.uint8)]).view("<u4")
+        return self.dangling_bits_
+
+    def solve(self, damping, tol=1e-6, max_iterations=100, personalization=None, check_every=4):
+        """PageRank proper (networkx's pagerank with dangling = personalization and the plain L1 change as the
+        stopping rule): personalised teleport, the rank of vertices without out-edges handed back through the teleport term, and
+        a residual stop.  With M the prepared matrix, D the columns of the padded matrix without an entry and p the
+        personalisation (default 1 / n0 on the n0 real vertices, 0 on padding):
+            x_0 = p;   c_k = float((1 - d) + d * sum_{u in D} x_k[u]);   x_{k+1} = fl32(M x_k + fl32(c_k * p));
+            r_{k+1} = sum_v |x_{k+1}[v] - x_k[v]|   (sums in f64, d = float32(damping))
+        until r <= tol or max_iterations.  Each iteration is the (+,x) SpMV and gl_pagerank_update; both sums stay on the
+        device, `check_every` iterations are enqueued between two read-backs of the control block, and iterations enqueued
+        past convergence leave the vector alone, so the result does not depend on check_every.  Leaves iterations_, converged_
+        and residuals_ (float64, one per iteration run); -> float32[n_].
+        ValueError: a damping other than the one the matrix was prepared with, tol < 0, check_every < 1, max_iterations
+        outside [1, capi.GL_PAGERANK_MAX_SLOTS] (65536: the control block holds one residual per iteration), a personalisation
+        of another length than n0 or n_, with a negative or non-finite entry, with zero sum, or non-zero on a padding vertex.
+        NotImplementedError on row shards; RuntimeError before send_matrix_host_to_device."""
+        if np.float32(damping) != np.float32(self.damping_):
+            raise ValueError("PageRank.solve: damping %r, but the matrix was prepared with %r (load_and_format_matrix)"
+                             % (damping, self.damping_))
+        if not tol >= 0:
+            raise ValueError("PageRank.solve: tol %r < 0" % (tol,))
+        max_iterations, check_every = int(max_iterations), int(check_every)
+        if max_iterations < 1 or max_iterations > capi.GL_PAGERANK_MAX_SLOTS:
+            raise ValueError("PageRank.solve: max_iterations %d is not in [1, %d]" % (max_iterations, capi.GL_PAGERANK_MAX_SLOTS))
+        if check_every < 1:
+            raise ValueError("PageRank.solve: check_every %d < 1" % check_every)
+        p = self._personalization(personalization)
+        if self.comm.distributed:
+            raise NotImplementedError("PageRank.solve: row shards are not supported yet (the residual and the dangling mass "
+                                      "would have to be summed across ranks); use one device")
+        if getattr(self.SpMV_, "plan_", None) is None:
+            raise RuntimeError("PageRank.solve: the matrix is not on the device yet (send_matrix_host_to_device)")
+        B, n = self.backend, self.n_
+        slots = max_iterations
+        p_buf = capi.DeviceBuffer.from_host(p)
+        bits_buf = capi.DeviceBuffer.from_host(self._dangling_bits())
+        ctl = capi.DeviceBuffer(capi.pagerank_ctl_bytes(slots))
+        vector, results = B.alloc(n, np.float32), B.alloc(n, np.float32)
+        capi.pagerank_begin(p_buf, n, bits_buf, vector, ctl, slots)
+        saved = (self.SpMV_.semiring_, self.SpMV_.vector_buf, self.SpMV_.results_buf)
+        self.SpMV_.set_semiring(self.semiring_)         # (+,x) with zero = 0; no chaining: the update rewrites every result
+        done, k = False, 0
+        try:
+            while k < max_iterations and not done:
+                for _ in range(min(check_every, max_iterations - k)):
+                    k += 1
+                    self.SpMV_.bind_vector_buf(vector)
+                    self.SpMV_.bind_results_buf(results)
+                    self.SpMV_.run()
+                    capi.pagerank_update(results, vector, p_buf, bits_buf, n, damping, tol, ctl, k)
+                    vector, results = results, vector
+                done = bool(ctl.read(np.uint32, 1)[0])
+        finally:
+            self.SpMV_.set_semiring(saved[0])
+            self.SpMV_.bind_vector_buf(saved[1])
+            self.SpMV_.bind_results_buf(saved[2])
+        done, ran, _, r = capi.pagerank_ctl_unpack(ctl.read(np.uint8, capi.pagerank_ctl_head_bytes(slots)), slots)
+        self.converged_, self.iterations_ = done, ran
+        self.residuals_ = r[1:ran + 1]
+        return B.download_result(vector, n)
 
     def pull_time_breakdown(self, damping, num_iterations):
         """app/pagerank.h:93-147: pull with per-iteration wall-clock buckets (spmv, ewise, data transfer); every

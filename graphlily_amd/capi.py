@@ -43,6 +43,7 @@ EXPORTS = [
     "gl_bfs_parents", "gl_bfs_parents_entries", "gl_spmv_plan_rows_sorted",
     "gl_prof_begin", "gl_prof_end", "gl_span_begin", "gl_span_end",
     "gl_sssp_parents", "gl_sssp_parents_entries",
+    "gl_pagerank_ctl_bytes", "gl_pagerank_begin", "gl_pagerank_update",
     "gl_spmspv_plan_create", "gl_spmspv_plan_destroy", "gl_spmspv_plan_info", "gl_spmspv_run", "gl_spmspv_run_assign",
     "gl_spmspv_plan_attach_pull", "gl_spmspv_plan_hint", "gl_spmspv_plan_hint_work", "gl_spmspv_last_direction", "gl_spmspv_wait", "gl_spmspv_failed_runs",
     "gl_sparse_nnz", "gl_ewise_add", "gl_assign_dense", "gl_assign_sparse",
@@ -115,6 +116,8 @@ def lib():
         "gl_spmv_run": [vp, vp, vp, vp, i32, f32, i32],
         "gl_prof_begin": [u32, u32], "gl_prof_end": [P(ctypes.c_double), P(u32)], "gl_span_begin": [], "gl_span_end": [P(ctypes.c_double)],
         "gl_sssp_parents": [vp, vp, f32, u32, vp, vp], "gl_sssp_parents_entries": [vp, vp, f32, u32, vp, P(u64)],
+        "gl_pagerank_ctl_bytes": [u32, P(ctypes.c_size_t)], "gl_pagerank_begin": [vp, u32, vp, vp, vp, u32],
+        "gl_pagerank_update": [vp, vp, vp, vp, u32, f32, ctypes.c_double, vp, u32],
         "gl_spmspv_plan_create": [P(vp), u32, u32, vp, vp, vp, u32, u32],
         "gl_spmspv_plan_destroy": [vp], "gl_spmspv_plan_info": [vp, P(u64), P(u64)],
         "gl_spmspv_run": [vp, vp, vp, vp, i32, f32, i32],
@@ -336,6 +339,8 @@ def copy_d2d(dst, src, nbytes):
 def _p(buf):
     return ctypes.c_void_p(buf.ptr if buf is not None else 0)
 
+
+GL_PAGERANK_MAX_SLOTS = 65536     # graphlily_hip.h
 
 GL_PLAN_NO_MULADD = 1
 GL_PLAN_BOOLEAN = 2
@@ -803,6 +808,40 @@ def sparse_nnz(buf):
 
 def ewise_add(inp, out, length, val):
     check(lib().gl_ewise_add(_p(inp), _p(out), int(length), float(val)))
+
+
+def pagerank_ctl_bytes(slots):
+    """gl_pagerank_ctl_bytes: the size of the control block of a PageRank iteration with `slots` update slots (layout:
+    include/graphlily_hip.h; pagerank_ctl_head_bytes(slots) of it are what a driver reads back).  Needs no device."""
+    v = ctypes.c_size_t(0)
+    check(lib().gl_pagerank_ctl_bytes(int(slots), ctypes.byref(v)))
+    return v.value
+
+
+def pagerank_ctl_head_bytes(slots):
+    """{done, iterations, slots, 0} and the two histories dangle[0..slots], r[0..slots]"""
+    return 16 + 16 * (int(slots) + 1)
+
+
+def pagerank_ctl_unpack(raw, slots):
+    """The head of a control block (uint8 array) -> (done, iterations, dangle[slots + 1], r[slots + 1])"""
+    raw = np.ascontiguousarray(raw, dtype=np.uint8)[:pagerank_ctl_head_bytes(slots)]
+    words = raw[:16].view(np.uint32)
+    hist = raw[16:].view(np.float64)
+    return bool(words[0]), int(words[1]), hist[:slots + 1].copy(), hist[slots + 1:2 * (slots + 1)].copy()
+
+
+def pagerank_begin(p, n, dangling_bits, x, ctl, slots):
+    """gl_pagerank_begin: x = p (n floats), dangle[0] = the sum of p over the vertices marked in `dangling_bits`
+    (ceil(n / 32) words), the rest of the control block's head cleared.  Enqueued, no wait."""
+    check(lib().gl_pagerank_begin(_p(p), int(n), _p(dangling_bits), _p(x), _p(ctl), int(slots)))
+
+
+def pagerank_update(y_inout, x, p, dangling_bits, n, damping, tol, ctl, slot):
+    """gl_pagerank_update: x_new = y + c * p over y, with c from dangle[slot - 1]; r[slot] and dangle[slot] into the control
+    block; r[slot] <= tol sets done, and an update that finds done set copies x to its output.  Enqueued, no wait."""
+    check(lib().gl_pagerank_update(_p(y_inout), _p(x), _p(p), _p(dangling_bits), int(n), float(damping), float(tol), _p(ctl),
+                                   int(slot)))
 
 
 def assign_dense(mask, inout, length, val, mask_type):

@@ -113,6 +113,7 @@ int preload_spmv_bool();
 int preload_spmspv();
 int preload_apply();
 int preload_format();
+int preload_pagerank();
 
 #define GL_REQUIRE_INIT()                                                           \
     do {                                                                            \

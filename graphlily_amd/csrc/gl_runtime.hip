@@ -391,7 +391,7 @@ int gl_init(int device) {
     c.initialized = true;
     int rc;
     if ((rc = gl::preload_spmv()) != GL_OK || (rc = gl::preload_spmv_bool()) != GL_OK || (rc = gl::preload_spmspv()) != GL_OK ||
-        (rc = gl::preload_apply()) != GL_OK || (rc = gl::preload_format()) != GL_OK) {
+        (rc = gl::preload_apply()) != GL_OK || (rc = gl::preload_format()) != GL_OK || (rc = gl::preload_pagerank()) != GL_OK) {
         c.initialized = false;
         return rc;
     }

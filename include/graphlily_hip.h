@@ -482,6 +482,34 @@ int gl_sparse_nnz(const gl_idx_val *d_sparse, uint32_t *nnz);
  * hw/kernel_add_scalar_vector_dense_impl.h:6-27): out[i] = in[i] + val. */
 int gl_ewise_add(const float *d_in, float *d_out, uint32_t len, float val);
 
+/* Extension: the outer iteration of PageRank.solve -- the pass that follows each (+,x) SpMV y = M x:
+ *   c            = (float)((1.0 - (double)damping) + (double)damping * dangle[slot - 1])
+ *   x_new[v]     = (float)(y[v] + (float)(c * p[v]))        a float multiply, then a float add (never fused); written over y
+ *   r[slot]      = sum over v of |(double)x_new[v] - (double)x[v]|
+ *   dangle[slot] = sum over the dangling v of (double)x_new[v]
+ * d_dangling_bits marks the dangling vertices: ceil(n / 32) words, bit v % 32 of word v / 32; bits past n are ignored.
+ * Both sums stay on the device, in the CONTROL BLOCK (gl_pagerank_ctl_bytes(slots) bytes, 8-byte aligned):
+ *   byte  0  uint32 done         1 once an update's residual was <= tol
+ *   byte  4  uint32 iterations   the slot of the last update that ran (the converging one once done is set)
+ *   byte  8  uint32 slots        as given to gl_pagerank_begin
+ *   byte 12  uint32 0
+ *   byte 16  double dangle[slots + 1]     dangle[0] is the start vector's
+ *   then     double r[slots + 1]          r[0] = 0
+ *   then     GL_PAGERANK_MAX_GROUPS pairs of doubles: the workgroups' partial sums {r, dangle} of the last pass
+ * The head up to r[slots] (16 + 16 * (slots + 1) bytes) is all a driver reads back.
+ * gl_pagerank_begin: x = p, dangle[0], everything else of the head cleared.  gl_pagerank_update(slot), slot in [1, slots]: the
+ * pass above; r[slot] <= tol sets done.  An update that finds done set (or whose slot is past `slots`) copies x to its output
+ * and changes nothing else, so updates enqueued past convergence leave the converged vector in place.  The sums are
+ * deterministic: the number of workgroups depends on n alone, each stores one pair, and a one-workgroup launch adds the pairs
+ * in workgroup-index order; no floating-point atomics.  Any n >= 1; y must not be x or p.  No call synchronises with the host;
+ * everything is enqueued on the library's stream. */
+#define GL_PAGERANK_MAX_GROUPS 1024u
+#define GL_PAGERANK_MAX_SLOTS 65536u
+int gl_pagerank_ctl_bytes(uint32_t slots, size_t *bytes);
+int gl_pagerank_begin(const float *d_p, uint32_t n, const uint32_t *d_dangling_bits, float *d_x, void *d_ctl, uint32_t slots);
+int gl_pagerank_update(float *d_y_inout, const float *d_x, const float *d_p, const uint32_t *d_dangling_bits, uint32_t n,
+                       float damping, double tol, void *d_ctl, uint32_t slot);
+
 /* mode 4, AssignVectorDenseModule::run (module/assign_vector_dense_module.h:208-220,
  * hw/kernel_assign_vector_dense_impl.h:8-47): WriteToZero: mask[i]==0 -> inout[i]=val;
  * WriteToOne: mask[i]!=0 -> inout[i]=val; NOMASK is GL_ERR_INVALID_ARG. */
