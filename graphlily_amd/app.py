@@ -169,6 +169,85 @@ def validate_sssp_tree(csr, source, distance, parent, unreached=M.FLOAT_INF, con
     return int(reached.sum())
 
 
+def _components_of(indptr, indices, data, n):
+    """Min-vertex labels of the weak components of a CSR over n vertices: a union-find in numpy, whole rounds at a time (kept
+    apart from the device's: validate_components checks one with the other).  An entry (v, u) is an edge unless its value is
+    0 (data None: every entry counts) or u >= n.  Between rounds lab[v] is the root of v's tree and the smallest vertex in it."""
+    indptr = np.asarray(indptr).astype(np.int64)
+    nr = indptr.shape[0] - 1
+    rows = np.repeat(np.arange(nr, dtype=np.int64), np.diff(indptr))
+    cols = np.asarray(indices[:indptr[nr]]).astype(np.int64)
+    live = (cols < n) & (rows < n)
+    if data is not None:
+        live &= np.asarray(data[:indptr[nr]]) != 0
+    rows, cols = rows[live], cols[live]
+    lab = np.arange(n, dtype=np.int64)
+    while True:
+        ra, rb = lab[rows], lab[cols]
+        cross = ra != rb
+        if not np.any(cross):
+            return lab
+        ra, rb = ra[cross], rb[cross]
+        nxt = lab.copy()
+        np.minimum.at(nxt, np.maximum(ra, rb), np.minimum(ra, rb))      # hook: the larger root under the smaller (trees descend) ...
+        while True:                                                     # ... and compress: every vertex to its root
+            hop = nxt[nxt]
+            if np.array_equal(hop, nxt):
+                break
+            nxt = hop
+        lab = nxt
+
+
+def validate_components(csr, labels):
+    """Host-side check (numpy) that `labels` are the weakly connected components of `csr` -- row v lists the vertices v is pulled
+    from, entries with value 0 are no edges, direction is ignored -- each vertex labelled with the SMALLEST vertex of its
+    component.  Raises ValueError naming the first offender and the rule; returns the number of components among the vertices
+    `labels` covers.  The rules:
+      1. labels[labels[v]] == labels[v] and labels[v] <= v;
+      2. every stored non-zero entry (v, u) has labels[v] == labels[u];
+      3. no two label classes are joined and every class is connected: the classes are exactly the components an independent
+         numpy pass finds (with rules 1 and 2 a class is a union of whole components named by its smallest vertex, so what is
+         left to refute is a class that falls apart).
+    `labels` may be longer than the matrix (the drivers pad it): the extra vertices have empty rows."""
+    nr, nc = int(csr.num_rows), int(csr.num_cols)
+    lab = np.asarray(labels).astype(np.int64)
+    n = lab.shape[0]
+    if lab.ndim != 1 or n < max(nr, nc):
+        raise ValueError("validate_components: %d labels for a %d x %d matrix" % (n, nr, nc))
+
+    def first(bad):
+        return int(np.flatnonzero(bad)[0])
+
+    v = np.arange(n, dtype=np.int64)
+    if np.any((lab < 0) | (lab > v)):
+        k = first((lab < 0) | (lab > v))
+        raise ValueError("validate_components: vertex %d has label %d, which is above it (rule 1)" % (k, lab[k]))
+    if np.any(lab[lab] != lab):
+        k = first(lab[lab] != lab)
+        raise ValueError("validate_components: vertex %d has label %d, whose own label is %d (rule 1)" % (k, lab[k], lab[lab[k]]))
+    indptr = np.asarray(csr.adj_indptr).astype(np.int64)
+    step = 1 << 18                       # rows per block: bounds the temporaries on matrices of 1e8 entries
+    for r0 in range(0, nr, step):
+        r1 = min(nr, r0 + step)
+        lo, hi = indptr[r0], indptr[r1]
+        if hi == lo:
+            continue
+        cols = np.asarray(csr.adj_indices[lo:hi]).astype(np.int64)
+        live = np.asarray(csr.adj_data[lo:hi]) != 0
+        rows = np.repeat(np.arange(r0, r1, dtype=np.int64), np.diff(indptr[r0:r1 + 1]))
+        bad = live & (lab[rows] != lab[cols])
+        if np.any(bad):
+            k = first(bad)
+            raise ValueError("validate_components: entry A[%d, %d] joins label %d and label %d (rule 2)"
+                             % (rows[k], cols[k], lab[rows[k]], lab[cols[k]]))
+    own = _components_of(indptr, csr.adj_indices, csr.adj_data, n)
+    if np.any(own != lab):
+        k = first(own != lab)
+        raise ValueError("validate_components: vertex %d has label %d, but no chain of entries joins the two: its component's smallest "
+                         "vertex is %d (rule 3)" % (k, lab[k], own[k]))
+    return int(np.count_nonzero(lab == v))
+
+
 class HipBackend:
     """Allocation / transfer hooks of the drivers.  The CPU tests substitute a stand-in with the
     same methods to exercise the distributed control flow over gloo."""
@@ -849,6 +928,60 @@ class BFS(_GraphApp):
         for k in ("total", "spmv_spmspv", "assign", "data_transfer", "overhead"):
             print("%s_time_ms: %.4f" % (k, tb[k]))
         return result
+
+
+class ConnectedComponents(_GraphApp):
+    """Weakly connected components (an extension: the reference has no such driver).  One SpMVModule with the (||,&&) semiring,
+    so that the plan is the boolean layout, whose plain row copy gl_cc_labels walks: lock-free union-find over
+    the rows, then pointer doubling.  run() labels every vertex with the smallest vertex of its component."""
+
+    def __init__(self, num_channels=M.num_hbm_channels, spmv_out_buf_len=0, vec_buf_len=0, comm=None, backend=None):
+        super().__init__(num_channels, comm, backend)
+        if self.comm.distributed:
+            # (before anything touches the device)
+            raise NotImplementedError("ConnectedComponents: row shards are not supported -- every rank would hold the forest of its own "
+                                      "rows and the forests would have to be merged.  On ONE device gl_cc_hook composes: cc_begin, "
+                                      "cc_hook on every shard's plan, cc_finish (capi.cc_begin / SpMVPlan.cc_hook / capi.cc_finish)")
+        self.semiring_ = M.LogicalSemiring
+        self.SpMV_ = self.backend.SpMVModule(num_channels, spmv_out_buf_len, vec_buf_len)
+        self.SpMV_.set_semiring(self.semiring_)
+        self.SpMV_.set_mask_type(M.kNoMask)
+        self.add_module(self.SpMV_)
+        self.sent_ = False
+        self.num_components_ = self.largest_component_ = None
+
+    def load_and_format_matrix(self, csr_float_npz_path, skip_empty_rows=True):
+        csr = self._load(csr_float_npz_path)
+        n_real = csr.num_rows
+        self._pad(csr)
+        csr.adj_data = np.ones(csr.nnz, dtype=np.float32)       # every stored entry is an edge, as in BFS (app/bfs.h:90)
+        self._shard(csr)
+        self.SpMV_.set_row_shard(self.r0_, self.r1_)
+        self.SpMV_.load_and_format_matrix(csr, skip_empty_rows)
+        self.n_ = self.SpMV_.get_num_rows()
+        assert self.n_ == self.SpMV_.get_num_cols()
+        self.n_real_ = n_real
+        self.sent_ = False
+
+    def send_matrix_host_to_device(self):
+        self.SpMV_.send_matrix_host_to_device()
+        self.sent_ = True
+
+    def run(self):
+        """-> uint32[n_]: labels[v] = the smallest vertex joined to v by a chain of stored entries taken in either direction
+        (padding vertices are singletons).  Leaves num_components_ (over the n_real_ real vertices) and largest_component_
+        (vertices in the largest one)."""
+        if not self.sent_:
+            raise RuntimeError("ConnectedComponents.run(): send_matrix_host_to_device first")
+        B, n = self.backend, self.n_
+        out = B.alloc(n + 1, np.float32)      # (32-bit words: vertex numbers, then the component count)
+        self.SpMV_.cc_labels(out, B.view(out, n, 1, 4))
+        B.sync()
+        words = B.download(out, np.uint32, n + 1)
+        labels = words[:n]
+        self.num_components_ = int(words[n]) - (n - self.n_real_)
+        self.largest_component_ = int(np.bincount(labels, minlength=1).max()) if n else 0
+        return labels
 
 
 class PageRank(_GraphApp):

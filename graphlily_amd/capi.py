@@ -41,6 +41,7 @@ EXPORTS = [
     "gl_spmv_plan_create", "gl_spmv_plan_create_ex", "gl_spmv_plan_destroy", "gl_spmv_plan_describe", "gl_spmv_plan_export", "gl_spmv_run", "gl_spmv_plan_chain",
     "gl_spmv_plan_bits_words", "gl_pack_bits", "gl_unpack_bits", "gl_bfs_bits_begin_from", "gl_spmv_run_bits", "gl_bfs_pull_step",
     "gl_bfs_parents", "gl_bfs_parents_entries", "gl_spmv_plan_rows_sorted",
+    "gl_cc_begin", "gl_cc_hook", "gl_cc_finish", "gl_cc_labels",
     "gl_prof_begin", "gl_prof_end", "gl_span_begin", "gl_span_end",
     "gl_sssp_parents", "gl_sssp_parents_entries",
     "gl_pagerank_ctl_bytes", "gl_pagerank_begin", "gl_pagerank_update",
@@ -113,6 +114,7 @@ def lib():
         "gl_spmv_plan_bits_words": [vp, P(u64)], "gl_pack_bits": [vp, u32, vp], "gl_unpack_bits": [vp, u32, vp], "gl_bfs_bits_begin_from": [vp, u32, vp, u32, vp, u32, vp, vp], "gl_spmv_run_bits": [vp, vp, vp, vp, f32, i32],
         "gl_bfs_pull_step": [vp, vp, vp, vp, f32],
         "gl_bfs_parents": [vp, vp, vp, vp], "gl_bfs_parents_entries": [vp, vp, vp, P(u64)], "gl_spmv_plan_rows_sorted": [vp, P(i32)],
+        "gl_cc_begin": [vp, u32], "gl_cc_hook": [vp, vp], "gl_cc_finish": [vp, u32, vp, vp], "gl_cc_labels": [vp, vp, vp],
         "gl_spmv_run": [vp, vp, vp, vp, i32, f32, i32],
         "gl_prof_begin": [u32, u32], "gl_prof_end": [P(ctypes.c_double), P(u32)], "gl_span_begin": [], "gl_span_end": [P(ctypes.c_double)],
         "gl_sssp_parents": [vp, vp, f32, u32, vp, vp], "gl_sssp_parents_entries": [vp, vp, f32, u32, vp, P(u64)],
@@ -432,6 +434,17 @@ class SpMVPlan:
         v = ctypes.c_uint64(0)
         check(lib().gl_bfs_parents_entries(ctypes.c_void_p(self.handle), _p(distance), _p(parent), ctypes.byref(v)))
         return v.value
+
+    def cc_labels(self, labels, count=None):
+        """gl_cc_labels: the weakly connected components of this plan's rows over num_cols vertices into `labels` (num_cols uint32
+        words: the smallest vertex of each vertex's component); `count`: an optional device word for the number of components.
+        Enqueued, no wait."""
+        check(lib().gl_cc_labels(ctypes.c_void_p(self.handle), _p(labels), _p(count)))
+
+    def cc_hook(self, parent):
+        """gl_cc_hook: unite the endpoints of every edge of this plan's rows in `parent` (num_cols uint32 words that cc_begin
+        has initialised); several plans may be hooked into one array before cc_finish."""
+        check(lib().gl_cc_hook(ctypes.c_void_p(self.handle), _p(parent)))
 
     def rows_sorted(self):
         """gl_spmv_plan_rows_sorted: do the columns of every row of the plan's CSR copy ascend?"""
@@ -808,6 +821,18 @@ def sparse_nnz(buf):
 
 def ewise_add(inp, out, length, val):
     check(lib().gl_ewise_add(_p(inp), _p(out), int(length), float(val)))
+
+
+def cc_begin(parent, n):
+    """gl_cc_begin: parent[v] = v for v < n (uint32 words): every vertex its own component.  Enqueued, no wait."""
+    check(lib().gl_cc_begin(_p(parent), int(n)))
+
+
+def cc_finish(parent, n, labels, count=None):
+    """gl_cc_finish: labels[v] = the root of v in the union-find forest `parent` (which is overwritten) -- the smallest vertex
+    of v's component once every edge is hooked; `count`: an optional device word for the number of roots.  `labels` must not
+    be `parent`.  Enqueued, no wait."""
+    check(lib().gl_cc_finish(_p(parent), int(n), _p(labels), _p(count)))
 
 
 def pagerank_ctl_bytes(slots):

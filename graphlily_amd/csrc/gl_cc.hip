@@ -1,0 +1,271 @@
+// Weakly connected components (gl_cc_begin / gl_cc_hook / gl_cc_finish / gl_cc_labels): lock-free union-find over the plain
+// CSR copy that every GL_PLAN_BOOLEAN plan keeps for the bottom-up BFS step (gl_spmv_plan.h: d_csr_indptr / d_csr_indices /
+// csr_nz_base), over n = num_cols vertices.
+//
+//   an entry (v, u) of row v is an edge unless u == 0xffffffff (zero-valued) or u >= n; direction is ignored
+//   labels[v] = min { x : x is joined to v by a chain of such edges, taken in either direction }
+//   count     = number of v with labels[v] == v
+//
+// The minimum makes the answer unique: it depends neither on the order of a row's entries nor on the order in which rows,
+// shards or plans are hooked, nor on timing.  Begin, hook and finish are separate so that several plans -- the row shards of
+// one matrix, two matrices over the same vertices -- can be hooked into ONE parent array before it is finished.
+//
+// THE INVARIANT: parent[x] <= x at all times, and parent[x] lies in x's component.  Chains strictly descend, so they cannot
+// cycle; once every edge is united each component has exactly one root (parent[r] == r), its minimum.
+//
+// Hook, in the launch shape of gl_bfs_parents.hip: 64 rows per wavefront, a thread per row, four entries
+// per step; a row longer than `cut` entries is taken over by the whole wavefront, 256 entries per step with coalesced index
+// loads; shards index through row_begin and csr_nz_base.  For an edge (v, u): find both roots; if they differ,
+// atomicCAS(&parent[hi], hi, lo) with hi = max, lo = min.
+// MEMORY RULES inside the hook launch (gfx950: eight XCDs with private L2s -- a plain store is not seen across them within a
+// launch):
+//   * every access to parent[] is an agent-scope atomic on a global pointer: a relaxed atomic load, an atomic min or a
+//     compare-and-swap; there is no plain load or store of that array;
+//   * a failed compare-and-swap continues from the value it RETURNED (never a re-read): that value is below hi, so every
+//     retry strictly descends and progress rests on atomic return values alone -- a stale load can at worst name a vertex
+//     that is no longer a root, which the compare-and-swap then refuses;
+//   * path shortening is atomicMin(&parent[x], grandparent) only, which keeps the invariant;
+//   * no spin-waits, no tickets, no hand-offs between workgroups: the only loops are the descending find and the retry.
+// Finish runs behind a launch boundary (plain loads): pointer doubling, ping-pong between parent and labels with one device
+// "changed" word per round.  A round at least halves the depth, so ceil(log2 n) + 1 rounds suffice; that many are enqueued
+// and a round returns at once when its predecessor changed nothing (both arrays then hold the result).  A thread-per-vertex
+// walk to the root would not do: a path hooked in index order leaves a chain of length n.  One more pass counts the roots,
+// one ballot and one atomic add per wavefront.  No call synchronises with the host.
+// NO ROW SKIPPING: entries are stored one way only (row v lists the vertices v is pulled from), so a row skipped because its
+// vertex already sits in the giant component (Afforest's shortcut) may hold the only copy of an edge that leaves it.
+#include "gl_spmv_plan.h"
+
+namespace gl {
+
+constexpr uint32_t kCcMaxRounds = 36;      // ceil(log2 2^32) + 1, made odd, with room
+constexpr uint32_t kCcCtlBytes = 256;      // one "changed" word per finish round
+
+typedef __attribute__((address_space(1))) uint32_t cc_gu32;
+
+__device__ __forceinline__ uint32_t cc_load(uint32_t *parent, uint32_t x) {
+    return __hip_atomic_load((cc_gu32 *)parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void cc_min(uint32_t *parent, uint32_t x, uint32_t v) {
+    (void)__hip_atomic_fetch_min((cc_gu32 *)parent + x, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// -> the value found at parent[x]: `expect` if the swap took place
+__device__ __forceinline__ uint32_t cc_cas(uint32_t *parent, uint32_t x, uint32_t expect, uint32_t desired) {
+    __hip_atomic_compare_exchange_strong((cc_gu32 *)parent + x, &expect, desired, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                         __HIP_MEMORY_SCOPE_AGENT);
+    return expect;
+}
+
+// the root below x (as far as this thread's loads can tell); every vertex passed on the way is pointed at its grandparent
+__device__ __forceinline__ uint32_t cc_find(uint32_t *parent, uint32_t x) {
+    uint32_t p = cc_load(parent, x);
+    while (p < x) {
+        const uint32_t g = cc_load(parent, p);
+        if (g < p) cc_min(parent, x, g);
+        x = p;
+        p = g;
+    }
+    return x;
+}
+
+// unite the components of a and b (a is an ancestor-or-self of the row's vertex); -> the row's new ancestor
+__device__ __forceinline__ uint32_t cc_unite(uint32_t *parent, uint32_t a, uint32_t b) {
+    for (;;) {
+        a = cc_find(parent, a);
+        b = cc_find(parent, b);
+        if (a == b) return a;
+        const uint32_t hi = max(a, b), lo = min(a, b);
+        const uint32_t seen = cc_cas(parent, hi, hi, lo);
+        if (seen == hi) return lo;
+        // hi was hooked by somebody else meanwhile: go on from where it points now (seen < hi)
+        if (a == hi) a = seen;
+        else b = seen;
+    }
+}
+
+struct CcHookArgs {
+    const uint32_t *row_ptr, *row_idx;
+    uint32_t *parent;
+    uint32_t row_begin, rows, n, nz_base, cut_steps;
+};
+
+__global__ __launch_bounds__(256) void cc_hook_kernel(CcHookArgs a) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t nwords = (a.rows + 63u) >> 6;
+    for (uint32_t wd = blockIdx.x * 4u + wave; wd < nwords; wd += gridDim.x * 4u) {
+        const uint32_t local = wd * 64u + lane;
+        const bool in = local < a.rows;
+        const uint32_t row = a.row_begin + local;     // < n: the plan has row_end <= num_cols
+        uint32_t beg = 0, end = 0;
+        if (in) {
+            beg = a.row_ptr[local] - a.nz_base;
+            end = a.row_ptr[local + 1u] - a.nz_base;
+        }
+        uint32_t anc = row;                           // an ancestor-or-self of `row`: only ever descends
+        for (uint32_t step = 0; step < a.cut_steps && __any(beg < end); step++) {
+            if (beg < end) {
+                uint32_t c[4];
+#pragma unroll
+                for (int u = 0; u < 4; u++) c[u] = beg + u < end ? a.row_idx[beg + u] : 0xffffffffu;
+#pragma unroll
+                for (int u = 0; u < 4; u++)
+                    if (c[u] < a.n && c[u] != row) anc = cc_unite(a.parent, anc, c[u]);
+                beg += 4u;
+            }
+        }
+        // rows still unfinished are taken over by the whole wavefront, 256 entries per step (coalesced index loads)
+        for (uint64_t pending = __ballot(beg < end); pending; pending &= pending - 1ull) {
+            const int src = __ffsll((unsigned long long)pending) - 1;
+            const uint32_t b = __shfl(beg, src), e = __shfl(end, src), v = __shfl(row, src);
+            uint32_t av = __shfl(anc, src);
+            for (uint32_t base = b; base < e; base += 256u) {
+                uint32_t c[4];
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    const uint32_t k = base + 64u * u + lane;
+                    c[u] = k < e ? a.row_idx[k] : 0xffffffffu;
+                }
+#pragma unroll
+                for (int u = 0; u < 4; u++)
+                    if (c[u] < a.n && c[u] != v) av = cc_unite(a.parent, av, c[u]);
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void cc_begin_kernel(uint32_t *__restrict__ parent, uint32_t n) {
+    for (uint32_t v = blockIdx.x * 256u + threadIdx.x; v < n; v += gridDim.x * 256u) parent[v] = v;
+}
+
+// one round of pointer doubling: out[v] = in[in[v]]; changed[round] != 0 if some vertex moved.  A round whose predecessor
+// changed nothing returns at once: in == out already, element for element.
+__global__ __launch_bounds__(256) void cc_jump_kernel(const uint32_t *__restrict__ in, uint32_t *__restrict__ out, uint32_t n,
+                                                      uint32_t *__restrict__ changed, uint32_t round) {
+    if (round != 0u && changed[round - 1u] == 0u) return;
+    bool moved = false;
+    for (uint32_t v = blockIdx.x * 256u + threadIdx.x; v < n; v += gridDim.x * 256u) {
+        const uint32_t p = in[v], g = in[p];
+        out[v] = g;
+        moved |= g != p;
+    }
+    if (__any(moved) && (threadIdx.x & 63u) == 0u) atomicOr(changed + round, 1u);
+}
+
+__global__ __launch_bounds__(256) void cc_count_kernel(const uint32_t *__restrict__ labels, uint32_t n, uint32_t *__restrict__ count) {
+    uint32_t roots = 0;   // per wavefront
+    const uint32_t nround = (n + 255u) & ~255u;
+    for (uint32_t v = blockIdx.x * 256u + threadIdx.x; v < nround; v += gridDim.x * 256u)
+        roots += (uint32_t)__popcll(__ballot(v < n && labels[v] == v));
+    if ((threadIdx.x & 63u) == 0u && roots != 0u) atomicAdd(count, roots);
+}
+
+static unsigned cc_stream_grid(uint32_t n) { return std::max(1u, std::min<unsigned>((n + 255u) / 256u, (unsigned)ctx().num_cus * 8u)); }
+
+static int cc_check_plan(gl_spmv_plan p, const char *who) {
+    if (!p->d_csr_indptr || !p->d_csr_indices)
+        return set_error(GL_ERR_UNSUPPORTED, "%s: the plan keeps no row copy (a GL_PLAN_BOOLEAN plan in the (||,&&) layout does)", who);
+    if (p->row_end > p->num_cols)
+        return set_error(GL_ERR_UNSUPPORTED, "%s: the parent array is indexed by row and by column: needs num_rows <= num_cols", who);
+    return GL_OK;
+}
+
+static int cc_begin(uint32_t *d_parent, uint32_t n) {
+    if (!n) return GL_OK;
+    cc_begin_kernel<<<cc_stream_grid(n), 256, 0, ctx().stream>>>(d_parent, n);
+    GL_LAUNCH_CHECK();
+    return GL_OK;
+}
+
+static int cc_hook(gl_spmv_plan p, uint32_t *d_parent) {
+    const uint32_t rows = p->row_end - p->row_begin;
+    if (!rows) return GL_OK;
+    // A/B knobs (GRAPHLILY_DEBUG, read per call): cc_cut = entries a thread reads before the wavefront takes the row over,
+    // cc_grid = workgroups per compute unit
+    const long cut = debug_knob("cc_cut", 32);
+    CcHookArgs a;
+    a.row_ptr = p->d_csr_indptr;
+    a.row_idx = p->d_csr_indices;
+    a.parent = d_parent;
+    a.row_begin = p->row_begin;
+    a.rows = rows;
+    a.n = p->num_cols;
+    a.nz_base = p->csr_nz_base;
+    a.cut_steps = (uint32_t)std::max<long>(0, std::min<long>(cut, 1l << 30)) / 4u;
+    const unsigned per_cu = (unsigned)std::max<long>(1, std::min<long>(debug_knob("cc_grid", 64), 1024));
+    const unsigned nwords = (rows + 63u) / 64u;
+    const unsigned grid = std::max(1u, std::min<unsigned>((nwords + 3u) / 4u, (unsigned)ctx().num_cus * per_cu));
+    cc_hook_kernel<<<grid, 256, 0, ctx().stream>>>(a);
+    GL_LAUNCH_CHECK();
+    return GL_OK;
+}
+
+static int cc_finish(uint32_t *d_parent, uint32_t n, uint32_t *d_labels, uint32_t *d_count, const char *who) {
+    hipStream_t s = ctx().stream;
+    if (d_count) GL_HIP(hipMemsetAsync(d_count, 0, 4, s));
+    if (!n) return GL_OK;
+    uint32_t *&ctl = ctx().cc_ctl;
+    if (!ctl) {
+        hipError_t e = hipMalloc((void **)&ctl, kCcCtlBytes);
+        if (e != hipSuccess) return set_error(GL_ERR_HIP, "%s: hipMalloc(%u bytes of control words): %s", who, kCcCtlBytes, hipGetErrorString(e));
+    }
+    GL_HIP(hipMemsetAsync(ctl, 0, kCcCtlBytes, s));
+    uint32_t rounds = 1;                      // ceil(log2 n) + 1 ...
+    while ((1ull << (rounds - 1u)) < n) rounds++;
+    rounds |= 1u;                             // ... made odd: the last round writes d_labels
+    static_assert(kCcMaxRounds * 4u <= kCcCtlBytes && kCcMaxRounds >= 33u, "one word per round");
+    const unsigned grid = cc_stream_grid(n);
+    uint32_t *in = d_parent, *out = d_labels;
+    for (uint32_t r = 0; r < rounds; r++) {
+        cc_jump_kernel<<<grid, 256, 0, s>>>(in, out, n, ctl, r);
+        GL_LAUNCH_CHECK();
+        std::swap(in, out);
+    }
+    if (d_count) {
+        cc_count_kernel<<<grid, 256, 0, s>>>(d_labels, n, d_count);
+        GL_LAUNCH_CHECK();
+    }
+    return GL_OK;
+}
+
+}  // namespace gl
+
+int gl_cc_begin(uint32_t *d_parent, uint32_t n) {
+    GL_TRACE();
+    GL_REQUIRE_INIT();
+    GL_ARG(d_parent != nullptr);
+    return gl::cc_begin(d_parent, n);
+}
+
+int gl_cc_hook(gl_spmv_plan plan, uint32_t *d_parent) {
+    GL_TRACE();
+    GL_REQUIRE_INIT();
+    GL_ARG(plan != nullptr && d_parent != nullptr);
+    int rc = gl::cc_check_plan(plan, "gl_cc_hook");
+    if (rc != GL_OK) return rc;
+    return gl::cc_hook(plan, d_parent);
+}
+
+int gl_cc_finish(uint32_t *d_parent, uint32_t n, uint32_t *d_labels, uint32_t *d_count) {
+    GL_TRACE();
+    GL_REQUIRE_INIT();
+    GL_ARG(d_parent != nullptr && d_labels != nullptr);
+    GL_ARG(d_labels != d_parent);
+    return gl::cc_finish(d_parent, n, d_labels, d_count, "gl_cc_finish");
+}
+
+int gl_cc_labels(gl_spmv_plan plan, uint32_t *d_labels, uint32_t *d_count) {
+    GL_TRACE();
+    GL_REQUIRE_INIT();
+    GL_ARG(plan != nullptr && d_labels != nullptr);
+    int rc = gl::cc_check_plan(plan, "gl_cc_labels");
+    if (rc != GL_OK) return rc;
+    const uint32_t n = plan->num_cols;
+    if (!plan->d_cc_scratch) {
+        const size_t bytes = 4u * (size_t)std::max(n, 4u);
+        hipError_t e = hipMalloc((void **)&plan->d_cc_scratch, bytes);
+        if (e != hipSuccess) return gl::set_error(GL_ERR_HIP, "gl_cc_labels: hipMalloc(%zu bytes of parent scratch): %s", bytes, hipGetErrorString(e));
+    }
+    if ((rc = gl::cc_begin(plan->d_cc_scratch, n)) != GL_OK) return rc;
+    if ((rc = gl::cc_hook(plan, plan->d_cc_scratch)) != GL_OK) return rc;
+    return gl::cc_finish(plan->d_cc_scratch, n, d_labels, d_count, "gl_cc_labels");
+}

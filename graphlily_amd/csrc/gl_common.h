@@ -60,6 +60,7 @@ struct Context {
     hipStream_t stream = nullptr;  // current stream (own or adopted)
     int num_cus = 256;
     uint32_t *pinned_word = nullptr;   // page-locked staging word for small device->host control reads
+    uint32_t *cc_ctl = nullptr;        // gl_cc_finish (gl_cc.hip): one "changed" word per pointer-doubling round, on first use
     // gl_graph_begin_capture .. gl_graph_end_capture: the communicators (their counters of recorded graphs) whose exchanges
     // were recorded -- RCCL's communicator destroy WAITS for every graph holding its operations, so gl_dist_destroy refuses
     // while such a graph is alive instead of hanging

@@ -226,6 +226,8 @@ struct gl_spmv_plan_s {
     // ascend (-1: not established yet), and the pass's scratch -- 256 bytes of control words + one byte per column
     int rows_sorted = -1;
     unsigned char *d_parents_scratch = nullptr;
+    // gl_cc_labels (gl_cc.hip): num_cols words of parent scratch, allocated by the first call
+    uint32_t *d_cc_scratch = nullptr;
     // GL_PLAN_REFERENCE_ORDER: the shard's plain CSR (indptr rebased to 0, values kept), evaluated a thread per row in
     // the reference's own order -- a diagnostic layout, not a fast one
     bool reference_order = false;

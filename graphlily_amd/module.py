@@ -262,6 +262,16 @@ class SpMVModule(BaseModule):
         self.plan_.bfs_parents(distance_buf, parent_buf, orphans_buf)
         self._finish(parent_buf)
 
+    def cc_labels(self, labels_buf, count_buf=None):
+        """Extension (gl_cc_labels): the weakly connected components of this module's rows over get_num_cols() vertices, into
+        `labels_buf` (uint32 words: the smallest vertex of each vertex's component); `count_buf`: an optional device word for
+        the number of components.  Raises GraphLilyError (GL_ERR_UNSUPPORTED) when the plan keeps no row copy (only the
+        (||,&&) layout does)."""
+        if self.plan_ is None:
+            _fatal("SpMVModule.cc_labels: send_matrix_host_to_device first")
+        self.plan_.cc_labels(labels_buf, count_buf)
+        self._finish(labels_buf, count_buf)
+
     def fused_bfs_ok(self):
         if self.plan_ is None or not self._plan_serves(self.semiring_.op) or self.semiring_.zero != 0.0:
             return False

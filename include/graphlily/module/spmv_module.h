@@ -173,6 +173,14 @@ public:
         GRAPHLILY_CHECK(gl_bfs_parents(plan_, (const float *)distance.ptr(), (uint32_t *)parent.ptr(), orphans));
         finish_();
     }
+    // extension (gl_cc_labels): the weakly connected components of this module's rows over get_num_cols() vertices into `labels`
+    // (32-bit words: the smallest vertex of each vertex's component); `count`: an optional device word for the number of
+    // components.  Only the (||,&&) layout keeps the rows this pass walks.
+    void cc_labels(DeviceBuffer labels, uint32_t *count = nullptr) {
+        barrier_();
+        GRAPHLILY_CHECK(gl_cc_labels(plan_, (uint32_t *)labels.ptr(), count));
+        finish_();
+    }
     uint32_t get_num_rows() { return csr_matrix_float_.num_rows; }
     uint32_t get_num_cols() { return csr_matrix_float_.num_cols; }
     uint32_t get_nnz() { return csr_matrix_float_.adj_indptr[csr_matrix_float_.num_rows]; }

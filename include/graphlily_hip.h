@@ -281,6 +281,29 @@ int gl_bfs_parents_entries(gl_spmv_plan plan, const float *d_distance, uint32_t 
  * not (it reads every entry).  Established on first use, then cached.  (gl_spmv_plan_desc keeps its size: callers compiled
  * against an older header hold one.) */
 int gl_spmv_plan_rows_sorted(gl_spmv_plan plan, int *sorted);
+/* Extension: WEAKLY CONNECTED COMPONENTS over the plain CSR copy a GL_PLAN_BOOLEAN plan keeps (gl_cc.hip), on
+ * n = num_cols vertices.  An entry (v, u) of row v is an edge unless u == 0xffffffff (a zero-valued entry) or u >= n;
+ * direction is ignored, self entries and duplicates are harmless.
+ *   labels[v] = min { x : x is joined to v by a chain of such edges, taken in either direction }
+ *   count     = number of v with labels[v] == v
+ * The minimum makes the result unique: it depends neither on the order of a row's entries, nor on the order in which rows,
+ * shards or plans are processed, nor on timing.  labels are 32-bit words: no float ceiling at 2^24.
+ *   gl_cc_begin   parent[v] = v for v < n.
+ *   gl_cc_hook    unites the endpoints of every edge of the plan's rows [row_begin,row_end) in d_parent (num_cols words that
+ *                 gl_cc_begin, and possibly earlier hooks, have written): lock-free union-find, parent[x] <= x throughout.
+ *                 Several plans -- the row shards of one matrix, two matrices over the same vertices -- may be hooked into one
+ *                 array, one after the other, in any order; the finished result equals that of the union of their entries.
+ *   gl_cc_finish  d_labels[v] = the root of v, by pointer doubling between d_parent (which it overwrites) and d_labels: at most
+ *                 ceil(log2 n) + 1 rounds, each a no-op once its predecessor changed nothing; *d_count (a device word, may be
+ *                 NULL: not wanted) receives the number of roots.  d_labels == d_parent is GL_ERR_INVALID_ARG.
+ *   gl_cc_labels  begin + hook + finish for one plan, on num_cols words of scratch the plan allocates on first use and frees
+ *                 with itself; d_labels holds num_cols words.
+ * A plan without the row copy, or with row_end > num_cols, is GL_ERR_UNSUPPORTED.  No call synchronises: everything is enqueued
+ * on the library's stream. */
+int gl_cc_begin(uint32_t *d_parent, uint32_t n);
+int gl_cc_hook(gl_spmv_plan plan, uint32_t *d_parent);
+int gl_cc_finish(uint32_t *d_parent, uint32_t n, uint32_t *d_labels, uint32_t *d_count /* may be NULL */);
+int gl_cc_labels(gl_spmv_plan plan, uint32_t *d_labels, uint32_t *d_count /* may be NULL */);
 /* gl_spmv_run replaces enqueueTask(overlay, mode = 1) (module/spmv_module.h:471-475,
  * hw/overlay.cpp:308-330 -> hw/kernel_spmv_impl.h:392-819):
  *   y[r] = mask_r ? ( zero (+) sum_{i in row r} A_i (x) x[col_i] ) : 0
