@@ -248,6 +248,36 @@ def validate_components(csr, labels):
     return int(np.count_nonzero(lab == v))
 
 
+def validate_triangles(csr, triangles):
+    """Host-side check (scipy) that triangles[v] is the number of triangles through v in the undirected simple graph of `csr`
+    -- an edge {u, v} iff u != v and a stored non-zero entry A[v, u] or A[u, v] exists; duplicates, the diagonal, zero values and
+    direction are ignored.  An independent statement, on the symmetrised pattern S (no orientation): triangles[v] = ((S S) o S)
+    row sum / 2.  Raises ValueError naming the first offending vertex and both values; returns the number of triangles.
+    `triangles` may be longer than the matrix (the drivers pad it): the extra vertices are in no triangle."""
+    import scipy.sparse as sp
+    nr, nc = int(csr.num_rows), int(csr.num_cols)
+    t = np.asarray(triangles)
+    n = t.shape[0] if t.ndim == 1 else -1
+    if n < max(nr, nc):
+        raise ValueError("validate_triangles: %d counts for a %d x %d matrix" % (n, nr, nc))
+    indptr = np.asarray(csr.adj_indptr).astype(np.int64)[:nr + 1]
+    nnz = int(indptr[-1])
+    A = sp.csr_matrix((np.asarray(csr.adj_data[:nnz]) != 0, np.asarray(csr.adj_indices[:nnz]).astype(np.int64), indptr), shape=(nr, nc))
+    A.resize((n, n))
+    A.eliminate_zeros()
+    S = (A + A.T).tocsr()
+    S.setdiag(0)
+    S.eliminate_zeros()
+    S.data = np.ones(S.nnz, dtype=np.int64)
+    twice = np.asarray((S @ S).multiply(S).sum(axis=1)).ravel().astype(np.int64)
+    want = twice // 2
+    bad = np.flatnonzero(want != t.astype(np.int64))
+    if bad.size:
+        k = int(bad[0])
+        raise ValueError("validate_triangles: vertex %d is given %d triangles, it lies in %d" % (k, int(t[k]), int(want[k])))
+    return int(want.sum()) // 3
+
+
 class HipBackend:
     """Allocation / transfer hooks of the drivers.  The CPU tests substitute a stand-in with the
     same methods to exercise the distributed control flow over gloo."""
@@ -982,6 +1012,75 @@ class ConnectedComponents(_GraphApp):
         self.num_components_ = int(words[n]) - (n - self.n_real_)
         self.largest_component_ = int(np.bincount(labels, minlength=1).max()) if n else 0
         return labels
+
+
+class TriangleCount(_GraphApp):
+    """Triangle counting (an extension: the reference has no such driver).  One SpMVModule with the (||,&&) semiring, so that
+    the plan is the boolean layout, whose plain row copy gl_tc_count walks.  The matrix is read as an undirected
+    simple graph -- duplicates, the diagonal, zero-valued entries and direction are ignored, as in ConnectedComponents -- and
+    oriented by degree on the host (io.triangle_orient), so that every triangle is found exactly once and hub rows are short."""
+
+    def __init__(self, num_channels=M.num_hbm_channels, spmv_out_buf_len=0, vec_buf_len=0, comm=None, backend=None):
+        super().__init__(num_channels, comm, backend)
+        if self.comm.distributed:
+            # (before anything touches the device)
+            raise NotImplementedError("TriangleCount: row shards are not supported -- gl_tc_count reads row u for every column u "
+                                      "of a row, so every rank would need the whole oriented matrix")
+        self.semiring_ = M.LogicalSemiring
+        self.SpMV_ = self.backend.SpMVModule(num_channels, spmv_out_buf_len, vec_buf_len)
+        self.SpMV_.set_semiring(self.semiring_)
+        self.SpMV_.set_mask_type(M.kNoMask)
+        self.add_module(self.SpMV_)
+        self.sent_ = False
+        self.degrees_ = None
+        self.num_triangles_ = self.triangles_ = self.num_wedges_ = self.transitivity_ = None
+
+    def load_and_format_matrix(self, csr_float_npz_path, skip_empty_rows=True):
+        csr = self._load(csr_float_npz_path)
+        n_real = csr.num_rows
+        self._pad(csr)
+        csr, self.degrees_ = io.triangle_orient(csr)            # (after padding: padding vertices have empty rows)
+        self._shard(csr)
+        self.SpMV_.set_row_shard(self.r0_, self.r1_)
+        self.SpMV_.load_and_format_matrix(csr, skip_empty_rows)
+        self.n_ = self.SpMV_.get_num_rows()
+        assert self.n_ == self.SpMV_.get_num_cols()
+        self.n_real_ = n_real
+        self.sent_ = False
+
+    def send_matrix_host_to_device(self):
+        self.SpMV_.send_matrix_host_to_device()
+        self.sent_ = True
+
+    def run(self, per_vertex=True):
+        """-> uint64[n_]: triangles[v] = triangles through v (padding vertices: 0); with per_vertex=False -> the number of
+        triangles as an int (a kernel without the per-vertex bookkeeping).  Leaves num_triangles_, triangles_ (None for a
+        total-only run), num_wedges_ = sum of deg (deg - 1) / 2 and transitivity_ = 3 triangles / wedges (0.0 without wedges)."""
+        if not self.sent_:
+            raise RuntimeError("TriangleCount.run(): send_matrix_host_to_device first")
+        B, n = self.backend, self.n_
+        words = n + 1 if per_vertex else 1
+        out = B.alloc(2 * words, np.float32)      # (64-bit words: the total, then the per-vertex counts)
+        self.SpMV_.tc_count(B.view(out, 0, 1, 8), B.view(out, 1, n, 8) if per_vertex else None)
+        B.sync()
+        got = B.download(out, np.uint64, words)
+        self.num_triangles_ = int(got[0])         # (the orientation gives every triangle once)
+        self.triangles_ = got[1:] if per_vertex else None
+        deg = self.degrees_.astype(np.int64)
+        self.num_wedges_ = sum(int(d) * (int(d) - 1) // 2 * int(c) for d, c in zip(*np.unique(deg, return_counts=True)))
+        self.transitivity_ = 3.0 * self.num_triangles_ / self.num_wedges_ if self.num_wedges_ else 0.0
+        return self.triangles_ if per_vertex else self.num_triangles_
+
+    def clustering(self):
+        """-> float64[n_]: the local clustering coefficient 2 t[v] / (deg[v] (deg[v] - 1)) of the last per-vertex run, 0 where
+        deg[v] < 2"""
+        if self.triangles_ is None:
+            raise RuntimeError("TriangleCount.clustering(): run(per_vertex=True) first")
+        deg = self.degrees_.astype(np.float64)
+        pairs = deg * (deg - 1.0)
+        out = np.zeros(self.n_, dtype=np.float64)
+        np.divide(2.0 * self.triangles_.astype(np.float64), pairs, out=out, where=pairs > 0)
+        return out
 
 
 class PageRank(_GraphApp):

@@ -228,6 +228,13 @@ struct gl_spmv_plan_s {
     unsigned char *d_parents_scratch = nullptr;
     // gl_cc_labels (gl_cc.hip): num_cols words of parent scratch, allocated by the first call
     uint32_t *d_cc_scratch = nullptr;
+    // gl_tc_count (gl_tc.hip), all set up by the first call: are the rows strictly ascending sets of columns below num_cols
+    // (-1: not established yet), and the rows binned by length -- row numbers of the short bin (tc_items[0] rows, the longest of
+    // tc_cap[0] entries rounded up to 4), of the wave bin (tc_items[1], tc_cap[1]) and of the wide bin (tc_items[2], tc_cap[2]),
+    // then tc_items[3] pairs {row, first entry} of the long rows' chunks
+    int tc_rows_ok = -1;
+    unsigned char *d_tc_scratch = nullptr;
+    uint32_t tc_items[4] = {0, 0, 0, 0}, tc_cap[3] = {0, 0, 0};
     // GL_PLAN_REFERENCE_ORDER: the shard's plain CSR (indptr rebased to 0, values kept), evaluated a thread per row in
     // the reference's own order -- a diagnostic layout, not a fast one
     bool reference_order = false;

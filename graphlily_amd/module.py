@@ -272,6 +272,17 @@ class SpMVModule(BaseModule):
         self.plan_.cc_labels(labels_buf, count_buf)
         self._finish(labels_buf, count_buf)
 
+    def tc_count(self, total_buf, per_vertex_buf=None):
+        """Extension (gl_tc_count): the triangle count of this module's matrix -- rows as strictly ascending sets N(v), total =
+        sum over v, u in N(v) of |N(v) & N(u)| -- into the 64-bit word `total_buf`; `per_vertex_buf` (optional, get_num_rows()
+        64-bit words) gets one credit for each of v, u, w per triple.  Raises GraphLilyError (GL_ERR_UNSUPPORTED) when the plan
+        keeps no row copy (only the (||,&&) layout does), is not square, is a row shard, or its rows are no such sets
+        (io.triangle_orient prepares them)."""
+        if self.plan_ is None:
+            _fatal("SpMVModule.tc_count: send_matrix_host_to_device first")
+        self.plan_.tc_count(total_buf, per_vertex_buf)
+        self._finish(total_buf, per_vertex_buf)
+
     def fused_bfs_ok(self):
         if self.plan_ is None or not self._plan_serves(self.semiring_.op) or self.semiring_.zero != 0.0:
             return False

@@ -4,6 +4,7 @@
 #ifndef GRAPHLILY_IO_DATA_FORMATTER_H_
 #define GRAPHLILY_IO_DATA_FORMATTER_H_
 
+#include <algorithm>
 #include <cstdint>
 #include <type_traits>
 #include <vector>
@@ -37,6 +38,41 @@ void util_normalize_csr_matrix_by_outdegree(CSRMatrix<data_type> &m) {
     for (uint32_t c : m.adj_indices) per_col[c]++;
     const size_t nnz = m.adj_indptr[m.num_rows];
     for (size_t i = 0; i < nnz; i++) m.adj_data[i] = 1.0 / per_col[m.adj_indices[i]];
+}
+
+// The matrix preparation of app::TriangleCount (an extension): the undirected simple graph of m -- an edge {u, v} iff u != v and
+// a stored non-zero entry A[v,u] or A[u,v] exists -- oriented by degree.  Row v of the result keeps exactly the neighbours u
+// with (deg[u], u) > (deg[v], v), columns ascending, every value 1; `degrees` receives the undirected degrees.  Every triangle
+// then appears once in gl_tc_count's set formula and a hub's row is short.  n = max(num_rows, num_cols); apply after padding.
+template <typename data_type>
+CSRMatrix<data_type> util_triangle_orient(CSRMatrix<data_type> const &m, std::vector<uint32_t> &degrees) {
+    const uint64_t n = std::max(m.num_rows, m.num_cols);
+    std::vector<uint64_t> key;
+    key.reserve(2 * (size_t)m.adj_indptr[m.num_rows]);
+    for (uint32_t v = 0; v < m.num_rows; v++)
+        for (uint32_t i = m.adj_indptr[v]; i < m.adj_indptr[v + 1]; i++) {
+            const uint64_t u = m.adj_indices[i];
+            if (u == v || m.adj_data[i] == data_type(0)) continue;
+            key.push_back(v * n + u);
+            key.push_back(u * n + v);
+        }
+    std::sort(key.begin(), key.end());
+    key.erase(std::unique(key.begin(), key.end()), key.end());
+    degrees.assign(n, 0);
+    for (uint64_t k : key) degrees[k / n]++;
+    CSRMatrix<data_type> out;
+    out.num_rows = out.num_cols = (uint32_t)n;
+    out.adj_indptr.assign(n + 1, 0);
+    for (uint64_t k : key) {      // (sorted by (row, column): the kept columns of a row ascend)
+        const uint64_t a = k / n, b = k % n;
+        if (degrees[b] > degrees[a] || (degrees[b] == degrees[a] && b > a)) {
+            out.adj_indices.push_back((uint32_t)b);
+            out.adj_indptr[a + 1]++;
+        }
+    }
+    for (uint64_t v = 0; v < n; v++) out.adj_indptr[v + 1] += out.adj_indptr[v];
+    out.adj_data.assign(out.adj_indices.size(), data_type(1));
+    return out;
 }
 
 }  // namespace io

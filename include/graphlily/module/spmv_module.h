@@ -181,6 +181,15 @@ public:
         GRAPHLILY_CHECK(gl_cc_labels(plan_, (uint32_t *)labels.ptr(), count));
         finish_();
     }
+    // extension (gl_tc_count): the triangle count of this module's matrix -- rows as strictly ascending sets N(v), total = sum
+    // over v, u in N(v) of |N(v) & N(u)| -- into the 64-bit word `total`; `per_vertex` (optional, get_num_rows() 64-bit device
+    // words) gets one credit for each of v, u, w per triple.  Only the (||,&&) layout keeps the rows this pass walks; the matrix
+    // is square and whole (graphlily::io::util_triangle_orient prepares it).
+    void tc_count(DeviceBuffer total, uint64_t *per_vertex = nullptr) {
+        barrier_();
+        GRAPHLILY_CHECK(gl_tc_count(plan_, (uint64_t *)total.ptr(), per_vertex));
+        finish_();
+    }
     uint32_t get_num_rows() { return csr_matrix_float_.num_rows; }
     uint32_t get_num_cols() { return csr_matrix_float_.num_cols; }
     uint32_t get_nnz() { return csr_matrix_float_.adj_indptr[csr_matrix_float_.num_rows]; }

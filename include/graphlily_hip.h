@@ -304,6 +304,20 @@ int gl_cc_begin(uint32_t *d_parent, uint32_t n);
 int gl_cc_hook(gl_spmv_plan plan, uint32_t *d_parent);
 int gl_cc_finish(uint32_t *d_parent, uint32_t n, uint32_t *d_labels, uint32_t *d_count /* may be NULL */);
 int gl_cc_labels(gl_spmv_plan plan, uint32_t *d_labels, uint32_t *d_count /* may be NULL */);
+/* Extension: TRIANGLE COUNTING over the plain CSR copy a GL_PLAN_BOOLEAN plan keeps (gl_tc.hip), on a square
+ * whole-matrix plan whose rows are strictly ascending sets N(v) of columns below num_cols:
+ *   total  = sum over v, over u in N(v), of |N(v) & N(u)|                                          (one 64-bit word)
+ *   per[x] = number of triples (v, u, w) with u in N(v), w in N(v) & N(u), in which x is v, u or w  (num_rows 64-bit words)
+ * A formula about sets, exact whatever the order of the adds: an acyclic orientation (io.triangle_orient) gives every triangle
+ * once, a full symmetric pattern six times, a diagonal entry simply takes part.  Both outputs are zeroed by the call itself;
+ * d_per_vertex may be NULL (total only: a kernel without the per-vertex bookkeeping).  Sorted-set intersection: N(v) staged in
+ * LDS, the entries of every N(u) looked up in it by binary search; rows longer than the LDS budget are searched in global memory.
+ * GL_ERR_UNSUPPORTED for a plan without the row copy, with num_rows != num_cols, for a row shard (row u must be readable for
+ * every column u), and for rows that are not strictly ascending or hold a column >= num_cols (a zero-valued entry is stored
+ * as 0xffffffff).  A plan without entries (planned in the general layout whatever its flags) counts as an empty graph: zeros.
+ * A plan's first call establishes that the rows are such sets with one kernel, bins the rows by length and caches both in the
+ * plan, so it synchronises once; later calls only enqueue, on the library's stream. */
+int gl_tc_count(gl_spmv_plan plan, uint64_t *d_total, uint64_t *d_per_vertex /* may be NULL */);
 /* gl_spmv_run replaces enqueueTask(overlay, mode = 1) (module/spmv_module.h:471-475,
  * hw/overlay.cpp:308-330 -> hw/kernel_spmv_impl.h:392-819):
  *   y[r] = mask_r ? ( zero (+) sum_{i in row r} A_i (x) x[col_i] ) : 0
