@@ -278,6 +278,95 @@ def validate_triangles(csr, triangles):
     return int(want.sum()) // 3
 
 
+def _core_numbers_of(indptr, indices, n):
+    """Core numbers of a symmetric simple CSR over n vertices: a peel by whole SETS in numpy (kept apart from the device's queue:
+    validate_cores checks one with the other).  At level k every live vertex of degree <= k is removed at once, gets core k, and
+    the degrees of its neighbours drop by a bincount; when nobody qualifies k jumps to the smallest live degree."""
+    indptr = np.asarray(indptr).astype(np.int64)
+    indices = np.asarray(indices)
+    deg = np.diff(indptr)
+    core = np.zeros(n, dtype=np.int64)
+    alive = np.ones(n, dtype=bool)
+    left, k = n, 0
+    while left:
+        cand = np.flatnonzero(alive & (deg <= k))
+        if cand.size == 0:
+            k = int(deg[alive].min())
+            continue
+        core[cand] = k
+        alive[cand] = False
+        left -= cand.size
+        starts, lens = indptr[cand], indptr[cand + 1] - indptr[cand]
+        total = int(lens.sum())
+        if total:
+            at = np.repeat(starts - (np.cumsum(lens) - lens), lens) + np.arange(total, dtype=np.int64)
+            deg = deg - np.bincount(indices[at].astype(np.int64), minlength=n)      # (dead vertices' words go on sinking: never read)
+    return core
+
+
+def validate_cores(csr, core, order=None):
+    """Host-side check (numpy) that `core` are the core numbers of the undirected simple graph of `csr` -- an edge {u, v} iff
+    u != v and a stored non-zero entry A[v, u] or A[u, v] exists; duplicates, the diagonal, zero values and direction are
+    ignored -- and, when given, that `order` is a degeneracy ordering.  Raises ValueError naming the first offender and the
+    rule; returns the degeneracy.  The rules:
+      1. 0 <= core[v] <= deg[v], and at least core[v] neighbours u of v have core[u] >= core[v] (v's core holds together);
+      2. the array equals an independent host computation, a peel by whole sets (what is left to refute after rule 1 is a
+         value that is too LOW);
+      3. order is a permutation of the vertices, core[order[i]] never descends, and every vertex v has at most core[v]
+         neighbours behind it in the order.
+    `core` and `order` may be longer than the matrix (the drivers pad them): the extra vertices are isolated."""
+    nr, nc = int(csr.num_rows), int(csr.num_cols)
+    c = np.asarray(core)
+    n = c.shape[0] if c.ndim == 1 else -1
+    if n < max(nr, nc):
+        raise ValueError("validate_cores: %d core numbers for a %d x %d matrix" % (n, nr, nc))
+    c = c.astype(np.int64)
+    sym, deg = io.symmetrize_simple(csr)
+    m = sym.num_rows
+    indptr = np.concatenate([sym.adj_indptr.astype(np.int64), np.full(n - m, sym.nnz, dtype=np.int64)])
+    deg = np.diff(indptr)
+    rows = np.repeat(np.arange(n, dtype=np.int64), deg)
+    cols = sym.adj_indices.astype(np.int64)
+
+    def first(bad):
+        return int(np.flatnonzero(bad)[0])
+
+    if np.any((c < 0) | (c > deg)):
+        v = first((c < 0) | (c > deg))
+        raise ValueError("validate_cores: vertex %d of degree %d is given core number %d (rule 1)" % (v, deg[v], c[v]))
+    support = np.bincount(rows[c[cols] >= c[rows]], minlength=n)
+    if np.any(support < c):
+        v = first(support < c)
+        raise ValueError("validate_cores: vertex %d is given core number %d, but only %d of its neighbours have one that high (rule 1)"
+                         % (v, c[v], support[v]))
+    own = _core_numbers_of(indptr, cols, n)
+    if np.any(own != c):
+        v = first(own != c)
+        raise ValueError("validate_cores: vertex %d is given core number %d, its core number is %d (rule 2)" % (v, c[v], own[v]))
+    if order is not None:
+        o = np.asarray(order)
+        if o.ndim != 1 or o.shape[0] != n:
+            raise ValueError("validate_cores: an order of %d vertices for %d core numbers (rule 3)" % (o.shape[0] if o.ndim == 1 else -1, n))
+        o = o.astype(np.int64)
+        seen = np.bincount(o[(o >= 0) & (o < n)], minlength=n)
+        if np.any((o < 0) | (o >= n)) or np.any(seen != 1):
+            v = first((o < 0) | (o >= n)) if np.any((o < 0) | (o >= n)) else first(seen != 1)
+            raise ValueError("validate_cores: the order is no permutation: %s (rule 3)"
+                             % ("position %d holds %d" % (v, o[v]) if np.any((o < 0) | (o >= n)) else "vertex %d occurs %d times" % (v, seen[v])))
+        if np.any(np.diff(c[o]) < 0):
+            i = first(np.diff(c[o]) < 0)
+            raise ValueError("validate_cores: the order puts vertex %d (core number %d) before vertex %d (core number %d) (rule 3)"
+                             % (o[i], c[o[i]], o[i + 1], c[o[i + 1]]))
+        pos = np.empty(n, dtype=np.int64)
+        pos[o] = np.arange(n, dtype=np.int64)
+        behind = np.bincount(rows[pos[cols] > pos[rows]], minlength=n)
+        if np.any(behind > c):
+            v = first(behind > c)
+            raise ValueError("validate_cores: vertex %d with core number %d has %d neighbours behind it in the order (rule 3)"
+                             % (v, c[v], behind[v]))
+    return int(c.max()) if n else 0
+
+
 class HipBackend:
     """Allocation / transfer hooks of the drivers.  The CPU tests substitute a stand-in with the
     same methods to exercise the distributed control flow over gloo."""
@@ -1081,6 +1170,72 @@ class TriangleCount(_GraphApp):
         out = np.zeros(self.n_, dtype=np.float64)
         np.divide(2.0 * self.triangles_.astype(np.float64), pairs, out=out, where=pairs > 0)
         return out
+
+
+class KCore(_GraphApp):
+    """k-core decomposition (an extension: the reference has no such driver).  One SpMVModule with the (||,&&) semiring, so that
+    the plan is the boolean layout, whose plain row copy gl_kcore peels.  The matrix is read as an undirected
+    simple graph -- duplicates, the diagonal, zero-valued entries and direction are ignored, as in TriangleCount -- and stored
+    in both directions by the host (io.symmetrize_simple): peeling v must reach every neighbour of v through row v."""
+
+    def __init__(self, num_channels=M.num_hbm_channels, spmv_out_buf_len=0, vec_buf_len=0, comm=None, backend=None):
+        super().__init__(num_channels, comm, backend)
+        if self.comm.distributed:
+            # (before anything touches the device)
+            raise NotImplementedError("KCore: row shards are not supported -- gl_kcore reads row u for every column u of a row, "
+                                      "so every rank would need the whole symmetric matrix")
+        self.semiring_ = M.LogicalSemiring
+        self.SpMV_ = self.backend.SpMVModule(num_channels, spmv_out_buf_len, vec_buf_len)
+        self.SpMV_.set_semiring(self.semiring_)
+        self.SpMV_.set_mask_type(M.kNoMask)
+        self.add_module(self.SpMV_)
+        self.sent_ = False
+        self.degrees_ = None
+        self.core_ = self.order_ = self.degeneracy_ = self.levels_ = self.sub_rounds_ = self.launches_ = self.core_sizes_ = None
+
+    def load_and_format_matrix(self, csr_float_npz_path, skip_empty_rows=True):
+        csr = self._load(csr_float_npz_path)
+        n_real = csr.num_rows
+        self._pad(csr)
+        csr, self.degrees_ = io.symmetrize_simple(csr)          # (after padding: padding vertices have empty rows)
+        self._shard(csr)
+        self.SpMV_.set_row_shard(self.r0_, self.r1_)
+        self.SpMV_.load_and_format_matrix(csr, skip_empty_rows)
+        self.n_ = self.SpMV_.get_num_rows()
+        assert self.n_ == self.SpMV_.get_num_cols()
+        self.n_real_ = n_real
+        self.sent_ = False
+
+    def send_matrix_host_to_device(self):
+        self.SpMV_.send_matrix_host_to_device()
+        self.sent_ = True
+
+    def run(self, order=False):
+        """-> uint32[n_]: core[v] = the core number of v (padding vertices: 0).  Leaves core_, degeneracy_ = max core, order_
+        (uint32[n_], a degeneracy ordering -- not unique -- or None without order=True), levels_ (levels that peeled a vertex,
+        padding vertices included), sub_rounds_, launches_ and core_sizes_[k] = real vertices with core >= k, k = 0 ..
+        degeneracy_.  The call waits for the device."""
+        if not self.sent_:
+            raise RuntimeError("KCore.run(): send_matrix_host_to_device first")
+        B, n = self.backend, self.n_
+        out = B.alloc(2 * n if order else n, np.float32)          # (32-bit words: the core numbers, then the order)
+        stats = self.SpMV_.kcore(B.view(out, 0, n, 4), B.view(out, n, n, 4) if order else None)
+        B.sync()
+        got = B.download(out, np.uint32, 2 * n if order else n)
+        self.core_ = got[:n]
+        self.order_ = got[n:] if order else None
+        self.degeneracy_, self.levels_, self.sub_rounds_, self.launches_ = stats
+        counts = np.bincount(self.core_[:self.n_real_], minlength=self.degeneracy_ + 1)
+        self.core_sizes_ = np.cumsum(counts[::-1])[::-1].astype(np.int64)
+        return self.core_
+
+    def k_core(self, k):
+        """-> bool[n_]: the vertices of the k-core of the last run (core number >= k); padding vertices are in none"""
+        if self.core_ is None:
+            raise RuntimeError("KCore.k_core(): run() first")
+        mask = self.core_ >= k
+        mask[self.n_real_:] = False
+        return mask
 
 
 class PageRank(_GraphApp):

@@ -41,7 +41,7 @@ EXPORTS = [
     "gl_spmv_plan_create", "gl_spmv_plan_create_ex", "gl_spmv_plan_destroy", "gl_spmv_plan_describe", "gl_spmv_plan_export", "gl_spmv_run", "gl_spmv_plan_chain",
     "gl_spmv_plan_bits_words", "gl_pack_bits", "gl_unpack_bits", "gl_bfs_bits_begin_from", "gl_spmv_run_bits", "gl_bfs_pull_step",
     "gl_bfs_parents", "gl_bfs_parents_entries", "gl_spmv_plan_rows_sorted",
-    "gl_cc_begin", "gl_cc_hook", "gl_cc_finish", "gl_cc_labels", "gl_tc_count",
+    "gl_cc_begin", "gl_cc_hook", "gl_cc_finish", "gl_cc_labels", "gl_tc_count", "gl_kcore",
     "gl_prof_begin", "gl_prof_end", "gl_span_begin", "gl_span_end",
     "gl_sssp_parents", "gl_sssp_parents_entries",
     "gl_pagerank_ctl_bytes", "gl_pagerank_begin", "gl_pagerank_update",
@@ -116,6 +116,7 @@ def lib():
         "gl_bfs_parents": [vp, vp, vp, vp], "gl_bfs_parents_entries": [vp, vp, vp, P(u64)], "gl_spmv_plan_rows_sorted": [vp, P(i32)],
         "gl_cc_begin": [vp, u32], "gl_cc_hook": [vp, vp], "gl_cc_finish": [vp, u32, vp, vp], "gl_cc_labels": [vp, vp, vp],
         "gl_tc_count": [vp, vp, vp],
+        "gl_kcore": [vp, vp, vp, P(u32)],
         "gl_spmv_run": [vp, vp, vp, vp, i32, f32, i32],
         "gl_prof_begin": [u32, u32], "gl_prof_end": [P(ctypes.c_double), P(u32)], "gl_span_begin": [], "gl_span_end": [P(ctypes.c_double)],
         "gl_sssp_parents": [vp, vp, f32, u32, vp, vp], "gl_sssp_parents_entries": [vp, vp, f32, u32, vp, P(u64)],
@@ -453,6 +454,16 @@ class SpMVPlan:
         whole, its rows strictly ascending (io.triangle_orient gives each triangle once).  Both are zeroed by the call.  Enqueued;
         the plan's first call waits once."""
         check(lib().gl_tc_count(ctypes.c_void_p(self.handle), _p(total), _p(per_vertex)))
+
+    def kcore(self, core, order=None):
+        """gl_kcore: the core numbers of this plan's graph into `core` (num_rows device words) and, optionally, a peeling order
+        into `order` (num_rows device words: core[order[i]] never descends, every vertex has at most core[v] neighbours behind
+        it; not unique) -> (degeneracy, levels that peeled a vertex, sub-rounds, launches enqueued).  The plan is square, whole,
+        its rows strictly ascending sets, its pattern symmetric (io.symmetrize_simple prepares it).  Both arrays are fully
+        written by the call, which SYNCHRONISES (it reads a control record back between batches of launches)."""
+        stats = (ctypes.c_uint32 * 4)(0xdeadbeef, 0xdeadbeef, 0xdeadbeef, 0xdeadbeef)
+        check(lib().gl_kcore(ctypes.c_void_p(self.handle), _p(core), _p(order), stats))
+        return tuple(int(x) for x in stats)
 
     def rows_sorted(self):
         """gl_spmv_plan_rows_sorted: do the columns of every row of the plan's CSR copy ascend?"""

@@ -1,0 +1,329 @@
+// k-core decomposition (gl_kcore): level-synchronous peeling (PKC-style, after Kabir & Madduri) over the plain CSR copy
+// that every GL_PLAN_BOOLEAN plan keeps (gl_spmv_plan.h: d_csr_indptr / d_csr_indices / csr_nz_base), on a square, whole-matrix
+// plan whose rows are strictly ascending sets N(v) of columns below num_cols and whose pattern is SYMMETRIC, over n = num_rows
+// vertices.  An entry (v, v) is ignored.
+//
+//   core[v]  = the largest k such that v lies in a subgraph in which every vertex has degree >= k (isolated vertices: 0)
+//   order    = (optional) a permutation of the vertices in which core[order[i]] never descends and every vertex has at most
+//              core[v] neighbours behind it: the order in which the vertices were peeled.  Not unique.
+//
+// STATE: deg[n], which IS d_core -- a vertex's degree is frozen at the level it is peeled at, so the array ends
+// up as the core numbers; a QUEUE of n words (d_order, or plan-owned scratch), which every vertex enters exactly once; and a
+// CONTROL RECORD {k, lo, hi, phase, counters} + tail (a line of its own).  No "alive" array: peeled vertices have deg <= k - 1,
+// or == k once they are queued at this level.
+//   scan   (phase "scan")  appends every v with deg[v] == k: one ballot and one atomic add to tail per wavefront
+//   peel   (phase "peel")  one SUB-ROUND over the queue slice [lo, hi) fixed at launch: for every entry u != v of row v,
+//                            if atomic load deg[u] > k:  old = fetch_sub(deg[u], 1)
+//                               old == k + 1: append u at tail           (exactly once per vertex: see below)
+//                               old <= k:     fetch_add(deg[u], 1) back  (somebody else took it to k first)
+//   turn   (one thread)    lo = hi, hi = tail; an empty slice ends the level: k += 1, phase = scan; otherwise phase = peel;
+//                          tail == n: done (everything still queued has only queued neighbours)
+// The transient dip below k is harmless: a vertex's word never rises above k again -- it is raised only by the restore that is
+// paired with a dip -- so `old == k + 1` is seen once, and it never wraps: a vertex is decremented at most once per neighbour.
+// The peel takes the launch shape of cc_hook_kernel (gl_cc.hip): a thread per queued vertex, four entries per step; a row
+// still unfinished after kcore_cut = 8 entries is taken over by the whole wavefront, 256 entries per step with coalesced index
+// loads (late levels consist of hub rows).  A slice shorter than the launch has wavefronts gives every wavefront fewer vertices.
+// MEMORY RULES inside a peel launch (gfx950: eight XCDs with private L2s), as in gl_cc.hip: every access to deg[] and to tail is
+// an agent-scope atomic on a global pointer; plain loads and stores only behind a launch boundary (the queue slice and the
+// control record were written by earlier launches; queue words written now are read by later ones).  No spin-waits, no tickets,
+// no hand-offs between workgroups.
+// GATING: every launch is correct whatever the previous one left in the control record -- a scan that finds the phase "peel"
+// returns at once and vice versa, everything returns once the phase is "done" -- so the host enqueues (scan, peel, turn) x
+// kcore_batch blindly, of which exactly one of scan / peel runs per triple, copies the record to page-locked memory and waits
+// ONCE per batch.  The result does not depend on kcore_batch.  At most n sub-rounds and n + 1 levels exist, so the loop is capped.
+#include "gl_spmv_plan.h"
+
+namespace gl {
+
+constexpr uint32_t kKcCtlBytes = 256;
+// the control record (words); the tail sits in the second 128-byte line: it is the only word a scan or peel launch writes
+enum : uint32_t { kKcK = 0, kKcLo = 1, kKcHi = 2, kKcPhase = 3, kKcLevels = 4, kKcSubRounds = 5, kKcLevelStart = 6, kKcDegeneracy = 7,
+                  kKcRecordWords = 8, kKcTail = 32 };
+enum : uint32_t { kKcScan = 0, kKcPeel = 1, kKcDone = 2 };
+
+typedef __attribute__((address_space(1))) uint32_t kc_gu32;
+
+__device__ __forceinline__ uint32_t kc_load(uint32_t *p) { return __hip_atomic_load((kc_gu32 *)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ uint32_t kc_add(uint32_t *p, uint32_t v) {
+    return __hip_atomic_fetch_add((kc_gu32 *)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ uint32_t kc_sub(uint32_t *p, uint32_t v) {
+    return __hip_atomic_fetch_sub((kc_gu32 *)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// position of the first entry >= w in the ascending s[0 .. n), n >= 1; the result is < n
+__device__ __forceinline__ uint32_t kc_lower_bound(const uint32_t *s, uint32_t n, uint32_t w) {
+    uint32_t lo = 0;
+    while (n > 1u) {
+        const uint32_t half = n >> 1;
+        lo += s[lo + half - 1u] < w ? half : 0u;
+        n -= half;
+    }
+    return lo;
+}
+
+// the plan's first call, behind the row check (every column is < n): is (u, v) stored for every (v, u)?  A wavefront per row.
+__global__ __launch_bounds__(256) void kcore_symmetric_kernel(const uint32_t *__restrict__ row_ptr, const uint32_t *__restrict__ row_idx,
+                                                              uint32_t n, uint32_t nz_base, uint32_t *__restrict__ verdict) {
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    bool bad = false;
+    for (uint64_t v = blockIdx.x * 4u + wave; v < n; v += gridDim.x * 4u) {
+        const uint32_t b = row_ptr[v] - nz_base, e = row_ptr[v + 1u] - nz_base;
+        for (uint64_t j = (uint64_t)b + lane; j < e; j += 64u) {
+            const uint32_t u = row_idx[j];
+            if (u == (uint32_t)v) continue;
+            const uint32_t ub = row_ptr[u] - nz_base, lu = row_ptr[u + 1u] - nz_base - ub;
+            bad |= lu == 0u || row_idx[ub + kc_lower_bound(row_idx + ub, lu, (uint32_t)v)] != (uint32_t)v;
+        }
+    }
+    if (bad) atomicOr(verdict, 1u);
+}
+
+// deg[v] = entries of row v other than v itself (the rows are sets of columns < n), the control record of level 0
+__global__ __launch_bounds__(256) void kcore_init_kernel(const uint32_t *__restrict__ row_ptr, const uint32_t *__restrict__ row_idx,
+                                                         uint32_t n, uint32_t nz_base, uint32_t *__restrict__ deg, uint32_t *__restrict__ ctl) {
+    if (blockIdx.x == 0u && threadIdx.x < 64u) ctl[threadIdx.x] = 0u;      // k = 0, an empty slice at 0, phase scan, tail 0
+    for (uint64_t v = blockIdx.x * 256u + threadIdx.x; v < n; v += gridDim.x * 256u) {
+        const uint32_t b = row_ptr[v] - nz_base, len = row_ptr[v + 1u] - nz_base - b;
+        uint32_t d = len;
+        if (len != 0u && row_idx[b + kc_lower_bound(row_idx + b, len, (uint32_t)v)] == (uint32_t)v) d -= 1u;
+        deg[v] = d;
+    }
+}
+
+__global__ __launch_bounds__(256) void kcore_iota_kernel(uint32_t *__restrict__ out, uint32_t n) {
+    for (uint64_t v = blockIdx.x * 256u + threadIdx.x; v < n; v += gridDim.x * 256u) out[v] = (uint32_t)v;
+}
+
+__global__ __launch_bounds__(256) void kcore_scan_kernel(const uint32_t *__restrict__ deg, uint32_t *__restrict__ queue, uint32_t *ctl,
+                                                         uint32_t n) {
+    if (ctl[kKcPhase] != kKcScan) return;
+    const uint32_t k = ctl[kKcK], lane = threadIdx.x & 63u;
+    const uint64_t nround = ((uint64_t)n + 255u) & ~255ull;       // whole wavefronts take every trip
+    for (uint64_t v = blockIdx.x * 256u + threadIdx.x; v < nround; v += gridDim.x * 256u) {
+        const bool hit = v < n && deg[v] == k;
+        const unsigned long long m = __ballot(hit);
+        if (m == 0ull) continue;
+        const int leader = __ffsll(m) - 1;
+        uint32_t base = 0;
+        if ((int)lane == leader) base = kc_add(ctl + kKcTail, (uint32_t)__popcll(m));
+        base = __shfl(base, leader);
+        const uint32_t pos = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+        if (hit && pos < n) queue[pos] = (uint32_t)v;             // (pos < n: every vertex is appended once)
+    }
+}
+
+struct KcPeelArgs {
+    const uint32_t *row_ptr, *row_idx;
+    uint32_t *deg, *queue, *ctl;
+    uint32_t n, nz_base, cut_steps;
+};
+
+// one neighbour u of a vertex peeled at level k
+__device__ __forceinline__ void kc_relax(const KcPeelArgs &a, uint32_t u, uint32_t k) {
+    if (kc_load(a.deg + u) <= k) return;                          // peeled before, or queued at this level
+    const uint32_t old = kc_sub(a.deg + u, 1u);
+    if (old == k + 1u) {
+        const uint32_t pos = kc_add(a.ctl + kKcTail, 1u);
+        if (pos < a.n) a.queue[pos] = u;
+    } else if (old <= k) {
+        (void)kc_add(a.deg + u, 1u);
+    }
+}
+
+__global__ __launch_bounds__(256) void kcore_peel_kernel(KcPeelArgs a) {
+    if (a.ctl[kKcPhase] != kKcPeel) return;
+    const uint32_t k = a.ctl[kKcK], lo = a.ctl[kKcLo], hi = a.ctl[kKcHi];
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t count = hi - lo, nwaves = gridDim.x * 4u;
+    // queued vertices per wavefront: 64, fewer when the slice is shorter than the launch (late levels: a few hub rows) -- a
+    // guess that was not measured against the plain 64 per wavefront
+    const uint32_t per = min(64u, max(1u, (uint32_t)(((uint64_t)count + nwaves - 1u) / nwaves)));
+    const uint32_t nwords = (uint32_t)(((uint64_t)count + per - 1u) / per);
+    for (uint32_t wd = blockIdx.x * 4u + wave; wd < nwords; wd += nwaves) {
+        const uint64_t item = (uint64_t)wd * per + lane;
+        const bool in = lane < per && item < count;
+        uint32_t v = 0, beg = 0, end = 0;
+        if (in) {
+            v = a.queue[lo + item];
+            beg = a.row_ptr[v] - a.nz_base;
+            end = a.row_ptr[v + 1u] - a.nz_base;
+        }
+        for (uint32_t step = 0; step < a.cut_steps && __any(beg < end); step++) {
+            if (beg < end) {
+                uint32_t c[4];
+#pragma unroll
+                for (int u = 0; u < 4; u++) c[u] = end - beg > (uint32_t)u ? a.row_idx[beg + u] : 0xffffffffu;   // (no wrap near 2^32 entries)
+#pragma unroll
+                for (int u = 0; u < 4; u++)
+                    if (c[u] < a.n && c[u] != v) kc_relax(a, c[u], k);
+                beg += min(4u, end - beg);
+            }
+        }
+        // rows still unfinished are taken over by the whole wavefront, 256 entries per step (coalesced index loads)
+        for (uint64_t pending = __ballot(beg < end); pending; pending &= pending - 1ull) {
+            const int src = __ffsll((unsigned long long)pending) - 1;
+            const uint32_t b = __shfl(beg, src), e = __shfl(end, src), row = __shfl(v, src);
+            for (uint64_t base = b; base < e; base += 256u) {
+                uint32_t c[4];
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    const uint64_t j = base + 64u * u + lane;
+                    c[u] = j < e ? a.row_idx[j] : 0xffffffffu;
+                }
+#pragma unroll
+                for (int u = 0; u < 4; u++)
+                    if (c[u] < a.n && c[u] != row) kc_relax(a, c[u], k);
+            }
+        }
+    }
+}
+
+// behind exactly one scan or peel that ran (plain loads and stores: a launch of its own)
+__global__ void kcore_turn_kernel(uint32_t *ctl, uint32_t n) {
+    if (threadIdx.x != 0u || blockIdx.x != 0u) return;
+    const uint32_t phase = ctl[kKcPhase];
+    if (phase == kKcDone) return;
+    const uint32_t k = ctl[kKcK], lo = ctl[kKcHi], hi = ctl[kKcTail];
+    if (phase == kKcPeel) ctl[kKcSubRounds] += 1u;
+    ctl[kKcLo] = lo;
+    ctl[kKcHi] = hi;
+    const bool done = hi >= n, over = lo == hi;
+    if ((done || over) && hi != ctl[kKcLevelStart]) {             // the level queued somebody: its vertices have core k
+        ctl[kKcLevels] += 1u;
+        ctl[kKcLevelStart] = hi;
+        ctl[kKcDegeneracy] = k;
+    }
+    if (done) {
+        ctl[kKcPhase] = kKcDone;
+    } else if (over) {
+        ctl[kKcK] = k + 1u;
+        ctl[kKcPhase] = kKcScan;
+    } else {
+        ctl[kKcPhase] = kKcPeel;
+    }
+}
+
+static unsigned kcore_stream_grid(uint32_t n) { return std::max(1u, std::min<unsigned>(cdiv(n, 256u), (unsigned)ctx().num_cus * 8u)); }
+
+// the refusals, the plan's two verdicts and its scratch, on first use (one synchronisation)
+static int kcore_prepare(gl_spmv_plan p, const char *who) {
+    // (a matrix without entries is planned in the general layout whatever the flags, and keeps no row copy: an empty graph)
+    if (p->nnz != 0 && (!p->d_csr_indptr || !p->d_csr_indices))
+        return set_error(GL_ERR_UNSUPPORTED, "%s: the plan keeps no row copy (a GL_PLAN_BOOLEAN plan in the (||,&&) layout does)", who);
+    if (p->num_rows != p->num_cols)
+        return set_error(GL_ERR_UNSUPPORTED, "%s: rows and columns name the same vertices: needs num_rows == num_cols (%u x %u)", who,
+                         p->num_rows, p->num_cols);
+    if (p->row_begin != 0u || p->row_end != p->num_rows)
+        return set_error(GL_ERR_UNSUPPORTED, "%s: a row shard [%u, %u) of %u rows: row u must be readable for every column u", who,
+                         p->row_begin, p->row_end, p->num_rows);
+    if (p->nnz > 0xffffffffull) return set_error(GL_ERR_UNSUPPORTED, "%s: %llu entries do not fit 32-bit offsets", who, (unsigned long long)p->nnz);
+    if (p->nnz == 0) return GL_OK;
+    int rc = tc_check_rows(p, who);
+    if (rc != GL_OK) return rc;
+    if (p->tc_rows_ok == 0)
+        return set_error(GL_ERR_UNSUPPORTED, "%s: the rows must be strictly ascending sets of columns below num_cols (no duplicate, no "
+                         "zero-valued entry, which the row copy stores as column 0xffffffff): io.symmetrize_simple prepares such a matrix", who);
+    const uint32_t n = p->num_rows;
+    if (!p->d_kcore_scratch) {
+        const size_t bytes = kKcCtlBytes + 4u * (size_t)n;       // the control record, then the queue of a call without d_order
+        hipError_t e = hipMalloc((void **)&p->d_kcore_scratch, bytes);
+        if (e != hipSuccess) return set_error(GL_ERR_HIP, "%s: hipMalloc(%zu bytes of control record and queue): %s", who, bytes, hipGetErrorString(e));
+    }
+    if (p->kcore_symmetric < 0) {
+        hipStream_t s = ctx().stream;
+        uint32_t *ctl = reinterpret_cast<uint32_t *>(p->d_kcore_scratch);
+        uint32_t h = 1;
+        hipError_t e = hipMemsetAsync(ctl, 0, kKcCtlBytes, s);
+        if (e == hipSuccess) {
+            const unsigned grid = std::max(1u, std::min<unsigned>(cdiv(n, 4u), (unsigned)ctx().num_cus * 16u));
+            kcore_symmetric_kernel<<<grid, 256, 0, s>>>(p->d_csr_indptr, p->d_csr_indices, n, p->csr_nz_base, ctl);
+            e = hipGetLastError();
+        }
+        GL_HIP(e != hipSuccess ? e : d2h_word_sync(&h, ctl, s));
+        p->kcore_symmetric = h == 0u ? 1 : 0;
+    }
+    if (p->kcore_symmetric == 0)
+        return set_error(GL_ERR_UNSUPPORTED, "%s: the pattern is not symmetric (an entry (v, u) without (u, v)): peeling v must reach u "
+                         "through row v; io.symmetrize_simple prepares such a matrix", who);
+    return GL_OK;
+}
+
+static int kcore(gl_spmv_plan p, uint32_t *d_core, uint32_t *d_order, uint32_t *h_stats, const char *who) {
+    int rc = kcore_prepare(p, who);
+    if (rc != GL_OK) return rc;
+    hipStream_t s = ctx().stream;
+    const uint32_t n = p->num_rows;
+    if (h_stats) h_stats[0] = h_stats[1] = h_stats[2] = h_stats[3] = 0u;
+    if (n == 0u) return GL_OK;
+    if (p->nnz == 0) {                                            // an empty graph: nobody has a neighbour, any order will do
+        GL_HIP(hipMemsetAsync(d_core, 0, 4u * (size_t)n, s));
+        if (d_order) {
+            kcore_iota_kernel<<<kcore_stream_grid(n), 256, 0, s>>>(d_order, n);
+            GL_LAUNCH_CHECK();
+        }
+        return GL_OK;
+    }
+    // A/B knobs (GRAPHLILY_DEBUG, read per call): kcore_cut = entries a thread reads before the wavefront takes the row over,
+    // kcore_batch = (scan, peel, turn) triples enqueued between two read-backs of the control record (8 and 64: the best of
+    // 8 / 32 / 128 and of 1 / 4 / 16 / 64, EXPERIMENTS.md Round 13), kcore_grid = workgroups per compute unit of a peel launch
+    // (4: an unmeasured guess, no A/B was run)
+    const long cut = debug_knob("kcore_cut", 8);
+    const uint32_t batch = (uint32_t)std::max<long>(1, std::min<long>(debug_knob("kcore_batch", 64), 4096));
+    const unsigned per_cu = (unsigned)std::max<long>(1, std::min<long>(debug_knob("kcore_grid", 4), 1024));
+    uint32_t *ctl = reinterpret_cast<uint32_t *>(p->d_kcore_scratch);
+    KcPeelArgs a;
+    a.row_ptr = p->d_csr_indptr;
+    a.row_idx = p->d_csr_indices;
+    a.deg = d_core;
+    a.queue = d_order ? d_order : ctl + kKcCtlBytes / 4u;
+    a.ctl = ctl;
+    a.n = n;
+    a.nz_base = p->csr_nz_base;
+    a.cut_steps = (uint32_t)std::max<long>(0, std::min<long>(cut, 1l << 30)) / 4u;
+    const unsigned stream_grid = kcore_stream_grid(n);
+    const unsigned peel_grid = std::max(1u, std::min<unsigned>(cdiv(n, 256u), (unsigned)ctx().num_cus * per_cu));
+    uint32_t *&w = ctx().pinned_word;
+    if (!w) GL_HIP(hipHostMalloc((void **)&w, 64, hipHostMallocDefault));
+    static_assert(kKcRecordWords * 4u <= 64u, "the record fits the page-locked staging words");
+    kcore_init_kernel<<<stream_grid, 256, 0, s>>>(a.row_ptr, a.row_idx, n, a.nz_base, d_core, ctl);
+    GL_LAUNCH_CHECK();
+    uint64_t launches = 1, steps = 0;
+    // every step that runs is a scan (one per level, and k never passes the degeneracy < n) or a sub-round over a slice that is
+    // not empty (every vertex is in one slice): at most 2 n + 1 steps
+    const uint64_t max_steps = 2ull * n + 1ull;
+    for (;;) {
+        for (uint32_t i = 0; i < batch; i++) {
+            kcore_scan_kernel<<<stream_grid, 256, 0, s>>>(d_core, a.queue, ctl, n);
+            kcore_peel_kernel<<<peel_grid, 256, 0, s>>>(a);
+            kcore_turn_kernel<<<1, 64, 0, s>>>(ctl, n);
+        }
+        GL_LAUNCH_CHECK();
+        launches += 3ull * batch;
+        steps += batch;
+        GL_HIP(hipMemcpyAsync(w, ctl, kKcRecordWords * 4u, hipMemcpyDeviceToHost, s));
+        GL_HIP(hipStreamSynchronize(s));
+        if (w[kKcPhase] == kKcDone) break;
+        if (steps >= max_steps)
+            return set_error(GL_ERR_HIP, "%s: internal error: not done after %llu steps on %u vertices (level %u, %u sub-rounds)", who,
+                             (unsigned long long)steps, n, w[kKcK], w[kKcSubRounds]);
+    }
+    if (h_stats) {
+        h_stats[0] = w[kKcDegeneracy];
+        h_stats[1] = w[kKcLevels];
+        h_stats[2] = w[kKcSubRounds];
+        h_stats[3] = (uint32_t)std::min<uint64_t>(launches, 0xffffffffull);
+    }
+    return GL_OK;
+}
+
+}  // namespace gl
+
+int gl_kcore(gl_spmv_plan plan, uint32_t *d_core, uint32_t *d_order, uint32_t *h_stats) {
+    GL_TRACE();
+    GL_REQUIRE_INIT();
+    GL_ARG(plan != nullptr && d_core != nullptr);
+    GL_ARG(d_order != d_core);
+    return gl::kcore(plan, d_core, d_order, h_stats, "gl_kcore");
+}

@@ -235,6 +235,10 @@ struct gl_spmv_plan_s {
     int tc_rows_ok = -1;
     unsigned char *d_tc_scratch = nullptr;
     uint32_t tc_items[4] = {0, 0, 0, 0}, tc_cap[3] = {0, 0, 0};
+    // gl_kcore (gl_kcore.hip), set up by the first call: is the pattern symmetric (-1: not established yet; the rows' verdict is
+    // tc_rows_ok above), and the pass's scratch -- 256 bytes of control record + num_rows words of queue
+    int kcore_symmetric = -1;
+    unsigned char *d_kcore_scratch = nullptr;
     // GL_PLAN_REFERENCE_ORDER: the shard's plain CSR (indptr rebased to 0, values kept), evaluated a thread per row in
     // the reference's own order -- a diagnostic layout, not a fast one
     bool reference_order = false;
@@ -363,6 +367,9 @@ struct SpmspvCsc {
 SpmspvCsc spmspv_plan_csc(gl_spmspv_plan p);
 // gl_spmspv.hip: forget `dying` wherever gl_spmspv_plan_attach_pull attached it
 void spmspv_detach_everywhere(gl_spmv_plan dying);
+// gl_tc.hip: establish p->tc_rows_ok (are the rows strictly ascending sets of columns below num_cols?) on first use, with one
+// kernel and one synchronisation; for a plan that keeps the row copy.  Shared by gl_tc_count and gl_kcore.
+int tc_check_rows(gl_spmv_plan p, const char *who);
 // gl_spmv.hip: y initialisation for plans whose units fold into y
 int spmv_init_rows(int op, int mask_type, uint32_t r0, uint32_t r1, const float *mask, float *y, float zero, hipStream_t s);
 }  // namespace gl

@@ -186,6 +186,30 @@ static void tc_launch(const TcArgs &a, bool per, unsigned threads, unsigned grid
     else tc_count_kernel<G, false, LDS><<<grid, threads, lds, s>>>(a);
 }
 
+// are the rows strictly ascending sets of columns below num_cols?  -> p->tc_rows_ok, established by one kernel and one
+// synchronisation on first use (a plan with a row copy and entries that fit 32-bit offsets; shared with gl_kcore.hip)
+int tc_check_rows(gl_spmv_plan p, const char *who) {
+    if (p->tc_rows_ok >= 0) return GL_OK;
+    hipStream_t s = ctx().stream;
+    const uint32_t rows = p->num_rows, nnz = (uint32_t)p->nnz;
+    uint32_t *ctl = nullptr;
+    hipError_t e = hipMalloc((void **)&ctl, kTcCtlBytes);
+    if (e != hipSuccess) return set_error(GL_ERR_HIP, "%s: hipMalloc(%u bytes of control words): %s", who, kTcCtlBytes, hipGetErrorString(e));
+    uint32_t h[4] = {0, 0, 0, 0};
+    e = hipMemsetAsync(ctl, 0, kTcCtlBytes, s);
+    if (e == hipSuccess && rows) {
+        const unsigned grid = std::max(1u, std::min<unsigned>(cdiv(std::max(nnz, rows), 256u), (unsigned)ctx().num_cus * 16u));
+        tc_check_kernel<<<grid, 256, 0, s>>>(p->d_csr_indptr, p->d_csr_indices, rows, nnz, p->csr_nz_base, p->num_cols, ctl);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(h, ctl, sizeof(h), hipMemcpyDeviceToHost, s);
+    const hipError_t w = hipStreamSynchronize(s);     // (waited for whether or not the copy could be enqueued: h is on the stack)
+    (void)hipFree(ctl);
+    GL_HIP(e != hipSuccess ? e : w);
+    p->tc_rows_ok = (h[0] == 0u && h[1] == h[2]) ? 1 : 0;
+    return GL_OK;
+}
+
 // the plan's verdict and bins, on first use (one synchronisation)
 static int tc_prepare(gl_spmv_plan p, const char *who) {
     // (a matrix without entries is planned in the general layout whatever the flags, and keeps no row copy: it has no triangles)
@@ -200,24 +224,9 @@ static int tc_prepare(gl_spmv_plan p, const char *who) {
     if (p->nnz > 0xffffffffull) return set_error(GL_ERR_UNSUPPORTED, "%s: %llu entries do not fit 32-bit offsets", who, (unsigned long long)p->nnz);
     if (p->nnz == 0) return GL_OK;      // nothing to check or to bin: tc_items stay 0, the call only zeroes its outputs
     hipStream_t s = ctx().stream;
-    const uint32_t rows = p->num_rows, nnz = (uint32_t)p->nnz;
-    if (p->tc_rows_ok < 0) {
-        uint32_t *ctl = nullptr;
-        hipError_t e = hipMalloc((void **)&ctl, kTcCtlBytes);
-        if (e != hipSuccess) return set_error(GL_ERR_HIP, "%s: hipMalloc(%u bytes of control words): %s", who, kTcCtlBytes, hipGetErrorString(e));
-        uint32_t h[4] = {0, 0, 0, 0};
-        e = hipMemsetAsync(ctl, 0, kTcCtlBytes, s);
-        if (e == hipSuccess && rows) {
-            const unsigned grid = std::max(1u, std::min<unsigned>(cdiv(std::max(nnz, rows), 256u), (unsigned)ctx().num_cus * 16u));
-            tc_check_kernel<<<grid, 256, 0, s>>>(p->d_csr_indptr, p->d_csr_indices, rows, nnz, p->csr_nz_base, p->num_cols, ctl);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(h, ctl, sizeof(h), hipMemcpyDeviceToHost, s);
-        const hipError_t w = hipStreamSynchronize(s);     // (waited for whether or not the copy could be enqueued: h is on the stack)
-        (void)hipFree(ctl);
-        GL_HIP(e != hipSuccess ? e : w);
-        p->tc_rows_ok = (h[0] == 0u && h[1] == h[2]) ? 1 : 0;
-    }
+    const uint32_t rows = p->num_rows;
+    int rc = tc_check_rows(p, who);
+    if (rc != GL_OK) return rc;
     if (p->tc_rows_ok == 0)
         return set_error(GL_ERR_UNSUPPORTED, "%s: the rows must be strictly ascending sets of columns below num_cols (no duplicate, no "
                          "zero-valued entry, which the row copy stores as column 0xffffffff): io.triangle_orient prepares such a matrix", who);

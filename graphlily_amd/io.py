@@ -8,6 +8,7 @@ Mirrors (names, argument meaning, in-place behaviour):
   util_round_csr_matrix_dim                      io/data_formatter.h:18-33
   util_normalize_csr_matrix_by_outdegree         io/data_formatter.h:36-51
   triangle_orient                                io/data_formatter.h (util_triangle_orient: an extension, no reference counterpart)
+  symmetrize_simple                              io/data_formatter.h (util_symmetrize_simple: an extension, no reference counterpart)
 The FPGA-only formatters (csr2cpsr, formatCSC: io/data_formatter.h:54-721) have no counterpart here:
 the device layout is produced inside gl_spmv_plan_create / gl_spmspv_plan_create.
 """
@@ -100,6 +101,30 @@ def triangle_orient(csr_matrix):
         raise ValueError("triangle_orient: %d entries do not fit 32-bit offsets" % int(out_indptr[n]))
     oriented = CSRMatrix(n, n, np.ones(b.shape[0], dtype=np.float32), b.astype(np.uint32), out_indptr.astype(np.uint32))
     return oriented, deg.astype(np.uint32)
+
+
+def symmetrize_simple(csr_matrix):
+    """The matrix preparation of KCore (an extension) -> (symmetric CSRMatrix with every value 1, degrees as uint32[n]),
+    n = max(num_rows, num_cols).  The undirected simple graph of the matrix has an edge {u, v} iff u != v and a stored non-zero
+    entry A[v, u] or A[u, v] exists: zero values and the diagonal are dropped, the rest is kept in BOTH directions, once each.
+    Row v of the result lists the neighbours of v, columns ascending -- the strictly ascending sets with a symmetric pattern
+    that gl_kcore asks for -- and deg[v] is its length.  Applied after padding: padding vertices have empty rows."""
+    n = max(int(csr_matrix.num_rows), int(csr_matrix.num_cols))
+    indptr = csr_matrix.adj_indptr.astype(np.int64)[:csr_matrix.num_rows + 1]
+    nnz = int(indptr[-1])
+    rows = np.repeat(np.arange(csr_matrix.num_rows, dtype=np.int64), np.diff(indptr))
+    cols = csr_matrix.adj_indices[:nnz].astype(np.int64)
+    keep = (np.asarray(csr_matrix.adj_data[:nnz]) != 0) & (rows != cols)
+    rows, cols = rows[keep], cols[keep]
+    key = np.unique(np.concatenate([rows * n + cols, cols * n + rows]))       # both directions, once each, sorted by (row, column)
+    a, b = key // n, key % n
+    deg = np.bincount(a, minlength=n).astype(np.int64)
+    out_indptr = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(deg, out=out_indptr[1:])
+    if int(out_indptr[n]) > 0xFFFFFFFF:
+        raise ValueError("symmetrize_simple: %d entries do not fit 32-bit offsets" % int(out_indptr[n]))
+    sym = CSRMatrix(n, n, np.ones(b.shape[0], dtype=np.float32), b.astype(np.uint32), out_indptr.astype(np.uint32))
+    return sym, deg.astype(np.uint32)
 
 
 def sssp_add_self_edges(csr_matrix):

@@ -283,6 +283,18 @@ class SpMVModule(BaseModule):
         self.plan_.tc_count(total_buf, per_vertex_buf)
         self._finish(total_buf, per_vertex_buf)
 
+    def kcore(self, core_buf, order_buf=None):
+        """Extension (gl_kcore): the core numbers of this module's matrix, read as a graph -- rows as strictly ascending sets
+        N(v), the pattern symmetric -- into `core_buf` (get_num_rows() words) and, optionally, a peeling order into `order_buf`
+        -> (degeneracy, levels, sub-rounds, launches).  The call synchronises.  Raises GraphLilyError (GL_ERR_UNSUPPORTED) when
+        the plan keeps no row copy (only the (||,&&) layout does), is not square, is a row shard, its rows are no such sets or
+        its pattern is not symmetric (io.symmetrize_simple prepares it)."""
+        if self.plan_ is None:
+            _fatal("SpMVModule.kcore: send_matrix_host_to_device first")
+        stats = self.plan_.kcore(core_buf, order_buf)
+        self._finish(core_buf, order_buf)
+        return stats
+
     def fused_bfs_ok(self):
         if self.plan_ is None or not self._plan_serves(self.semiring_.op) or self.semiring_.zero != 0.0:
             return False

@@ -6,6 +6,8 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <cstdio>
+#include <cstdlib>
 #include <type_traits>
 #include <vector>
 
@@ -71,6 +73,42 @@ CSRMatrix<data_type> util_triangle_orient(CSRMatrix<data_type> const &m, std::ve
         }
     }
     for (uint64_t v = 0; v < n; v++) out.adj_indptr[v + 1] += out.adj_indptr[v];
+    out.adj_data.assign(out.adj_indices.size(), data_type(1));
+    return out;
+}
+
+// The matrix preparation of app::KCore (an extension): the undirected simple graph of m -- an edge {u, v} iff u != v and a
+// stored non-zero entry A[v,u] or A[u,v] exists -- stored in BOTH directions, once each: row v of the result lists the
+// neighbours of v, columns ascending, every value 1; `degrees` receives the row lengths.  n = max(num_rows, num_cols); apply
+// after padding.
+template <typename data_type>
+CSRMatrix<data_type> util_symmetrize_simple(CSRMatrix<data_type> const &m, std::vector<uint32_t> &degrees) {
+    const uint64_t n = std::max(m.num_rows, m.num_cols);
+    std::vector<uint64_t> key;
+    key.reserve(2 * (size_t)m.adj_indptr[m.num_rows]);
+    for (uint32_t v = 0; v < m.num_rows; v++)
+        for (uint32_t i = m.adj_indptr[v]; i < m.adj_indptr[v + 1]; i++) {
+            const uint64_t u = m.adj_indices[i];
+            if (u == v || m.adj_data[i] == data_type(0)) continue;
+            key.push_back(v * n + u);
+            key.push_back(u * n + v);
+        }
+    std::sort(key.begin(), key.end());
+    key.erase(std::unique(key.begin(), key.end()), key.end());
+    if (key.size() > 0xffffffffull) {
+        printf("util_symmetrize_simple: %zu entries do not fit 32-bit offsets\n", key.size());
+        exit(EXIT_FAILURE);
+    }
+    degrees.assign(n, 0);
+    CSRMatrix<data_type> out;
+    out.num_rows = out.num_cols = (uint32_t)n;
+    out.adj_indptr.assign(n + 1, 0);
+    out.adj_indices.reserve(key.size());
+    for (uint64_t k : key) {      // (sorted by (row, column): the columns of a row ascend)
+        degrees[k / n]++;
+        out.adj_indices.push_back((uint32_t)(k % n));
+    }
+    for (uint64_t v = 0; v < n; v++) out.adj_indptr[v + 1] = out.adj_indptr[v] + degrees[v];
     out.adj_data.assign(out.adj_indices.size(), data_type(1));
     return out;
 }

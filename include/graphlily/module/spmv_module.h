@@ -190,6 +190,15 @@ public:
         GRAPHLILY_CHECK(gl_tc_count(plan_, (uint64_t *)total.ptr(), per_vertex));
         finish_();
     }
+    // extension (gl_kcore): the core numbers of this module's matrix, read as a graph -- rows as strictly ascending sets N(v),
+    // the pattern symmetric (graphlily::io::util_symmetrize_simple prepares it) -- into `core` (get_num_rows() words) and,
+    // optionally, a peeling order into `order` (as many device words); stats (optional, 4 host words) receives {degeneracy,
+    // levels, sub-rounds, launches}.  Only the (||,&&) layout keeps the rows this pass walks.  The call synchronises.
+    void kcore(DeviceBuffer core, uint32_t *order = nullptr, uint32_t *stats = nullptr) {
+        barrier_();
+        GRAPHLILY_CHECK(gl_kcore(plan_, (uint32_t *)core.ptr(), order, stats));
+        finish_();
+    }
     uint32_t get_num_rows() { return csr_matrix_float_.num_rows; }
     uint32_t get_num_cols() { return csr_matrix_float_.num_cols; }
     uint32_t get_nnz() { return csr_matrix_float_.adj_indptr[csr_matrix_float_.num_rows]; }

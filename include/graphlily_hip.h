@@ -318,6 +318,26 @@ int gl_cc_labels(gl_spmv_plan plan, uint32_t *d_labels, uint32_t *d_count /* may
  * A plan's first call establishes that the rows are such sets with one kernel, bins the rows by length and caches both in the
  * plan, so it synchronises once; later calls only enqueue, on the library's stream. */
 int gl_tc_count(gl_spmv_plan plan, uint64_t *d_total, uint64_t *d_per_vertex /* may be NULL */);
+/* Extension: K-CORE DECOMPOSITION over the plain CSR copy a GL_PLAN_BOOLEAN plan keeps (gl_kcore.hip), on a
+ * square whole-matrix plan whose rows are strictly ascending sets N(v) of columns below num_cols and whose pattern is symmetric
+ * (io.symmetrize_simple prepares it); an entry (v, v) is ignored.  n = num_rows:
+ *   d_core[v]  = the largest k such that v lies in a subgraph in which every vertex has degree >= k     (n words; isolated: 0)
+ *   d_order    = a permutation of the vertices in which d_core[d_order[i]] never descends and every vertex has at most
+ *                d_core[v] neighbours behind it -- the peeling order, NOT unique                         (n words, may be NULL)
+ *   h_stats    = {degeneracy = max core, levels that peeled a vertex, sub-rounds, launches enqueued}     (4 HOST words, may be NULL)
+ * All three are fully written by the call itself.  Level-synchronous peeling: d_core holds the remaining degrees, a device-
+ * resident queue (d_order, or scratch of the plan) grows while it is consumed, one launch per sub-round, each gated by a
+ * control record on the device, so the result does not depend on how many launches are enqueued at a time.
+ * GL_ERR_UNSUPPORTED for a plan without the row copy, with num_rows != num_cols, for a row shard (row u must be readable for
+ * every column u), for rows that are not strictly ascending or hold a column >= num_cols (a zero-valued entry is stored as
+ * 0xffffffff), and for a pattern that is not symmetric.  d_order == d_core is GL_ERR_INVALID_ARG.  A plan without entries
+ * (planned in the general layout whatever its flags) is an empty graph: d_core zero, d_order the identity, h_stats zero.
+ * THE CALL SYNCHRONISES: the host enqueues a fixed batch of gated launches, copies the control record to page-locked memory
+ * and waits, once per batch, until the record says done (at most 2 n + 1 launches do work; GL_ERR_HIP should the cap ever be
+ * hit).  A plan's first call also establishes with one kernel each that the rows are such sets (the verdict gl_tc_count
+ * caches) and that the pattern is symmetric, caches both in the plan and allocates 256 + 4 n bytes of scratch, which
+ * gl_spmv_plan_destroy frees. */
+int gl_kcore(gl_spmv_plan plan, uint32_t *d_core, uint32_t *d_order /* may be NULL */, uint32_t *h_stats /* may be NULL, 4 words */);
 /* gl_spmv_run replaces enqueueTask(overlay, mode = 1) (module/spmv_module.h:471-475,
  * hw/overlay.cpp:308-330 -> hw/kernel_spmv_impl.h:392-819):
  *   y[r] = mask_r ? ( zero (+) sum_{i in row r} A_i (x) x[col_i] ) : 0
