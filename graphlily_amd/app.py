@@ -367,6 +367,148 @@ def validate_cores(csr, core, order=None):
     return int(c.max()) if n else 0
 
 
+def _pattern_as_scipy(csr, n):
+    """the entries of a CSRMatrix as an n x n scipy matrix of f64 ones (the matrix may have fewer rows and columns)"""
+    import scipy.sparse as sp
+    ip = np.asarray(csr.adj_indptr).astype(np.int64)[:csr.num_rows + 1]
+    ip = np.concatenate([ip, np.full(n - csr.num_rows, ip[-1], dtype=np.int64)])
+    nnz = int(ip[-1])
+    return sp.csr_matrix((np.ones(nnz, dtype=np.float64), np.asarray(csr.adj_indices[:nnz]).astype(np.int64), ip), shape=(n, n))
+
+
+def _bfs_levels_of(A_out, sources, n):
+    """The drivers' level array (float32[n]: 1 on every source, it + 1 on a vertex reached in iteration it, 0 unreached) of a
+    complete search on the host; A_out is the scipy matrix whose row u holds the out-neighbours of u."""
+    level = np.zeros(n, dtype=np.float32)
+    frontier = np.unique(np.asarray(sources, dtype=np.int64))
+    level[frontier] = 1.0
+    it = 1
+    ip, idx = A_out.indptr, A_out.indices
+    while frontier.size:
+        starts, lens = ip[frontier], ip[frontier + 1] - ip[frontier]
+        total = int(lens.sum())
+        if not total:
+            break
+        at = np.repeat(starts - (np.cumsum(lens) - lens), lens) + np.arange(total, dtype=np.int64)
+        nxt = np.unique(idx[at])
+        frontier = nxt[level[nxt] == 0]
+        it += 1
+        level[frontier] = float(it)
+    return level
+
+
+def betweenness_by_levels(csr_in, csr_out, level):
+    """gl_bc_accumulate's definition on the host, in f64, one scipy SpMV per level -> (sigma, delta), float64[n] each, n =
+    len(level).  Row v of `csr_in` lists the vertices v is pulled from, row u of `csr_out` (None: the pattern is symmetric) the
+    out-neighbours of u; `level` are the drivers' levels (1 on every source, 0 unreached), D their maximum:
+      sigma[v] = 1 on level 1; the sum over u in row_in(v) with level[u] == level[v] - 1 of sigma[u] on level >= 2; 0 on level 0
+      delta[u] = sigma[u] * the sum over v in row_out(u) with level[v] == level[u] + 1 and sigma[v] > 0 of (1 + delta[v]) / sigma[v]
+    A vertex of level >= 2 without an in-neighbour one level up (not a BFS result) has sigma 0 and contributes nothing.  If a
+    sigma is not finite, delta is all zero: the device does not run the backward sweep then."""
+    lev = np.asarray(level).astype(np.int64)
+    n = lev.shape[0]
+    A_in = _pattern_as_scipy(csr_in, n)
+    A_out = A_in if csr_out is None else _pattern_as_scipy(csr_out, n)
+    D = int(lev.max()) if n else 0
+    sigma = (lev == 1).astype(np.float64)
+    delta = np.zeros(n, dtype=np.float64)
+    # the vertices bucketed by level, as the device buckets them: a level's SpMV multiplies that level's rows only, by a
+    # vector that holds the neighbouring level's values and zeros elsewhere
+    order = np.argsort(lev, kind="stable")
+    off = np.searchsorted(lev[order], np.arange(D + 3))
+    rows = [order[off[L]:off[L + 1]] for L in range(D + 2)]
+    x = np.zeros(n, dtype=np.float64)
+    with np.errstate(over="ignore", invalid="ignore"):
+        for L in range(2, D + 1):
+            x[rows[L - 1]] = sigma[rows[L - 1]]
+            if rows[L].size:
+                sigma[rows[L]] = A_in[rows[L]] @ x
+            x[rows[L - 1]] = 0.0
+        if not np.all(np.isfinite(sigma)):
+            return sigma, delta
+        coef = np.zeros(n, dtype=np.float64)
+        for L in range(D, 0, -1):
+            r = rows[L]
+            if L < D and r.size:
+                x[rows[L + 1]] = coef[rows[L + 1]]
+                delta[r] = sigma[r] * (A_out[r] @ x)
+                x[rows[L + 1]] = 0.0
+            live = r[sigma[r] > 0]
+            coef[live] = (1.0 + delta[live]) / sigma[live]
+    return sigma, delta
+
+
+def _bc_scale(n, k, normalized, directed):
+    """networkx's _rescale for endpoints=False (betweenness.py, 3.4.2) as one factor: n vertices, k sources.  Where networkx
+    does not rescale at all (directed and not normalised, or normalised with n <= 2) it does not apply n / k either."""
+    if normalized:
+        scale = 1.0 / ((n - 1) * (n - 2)) if n > 2 else None
+    else:
+        scale = None if directed else 0.5
+    if scale is None:
+        return 1.0
+    return scale * n / k if k < n else scale
+
+
+def _bc_patterns(csr, directed):
+    """-> (csr_in, csr_out or None, directed): what BetweennessCentrality.load_and_format_matrix loads for `directed`"""
+    cin, cout, symmetric = io.simple_pattern(csr)
+    if directed is None:
+        directed = not symmetric
+    if not directed and not symmetric:
+        cin, cout = io.symmetrize_simple(csr)[0], None
+    elif directed and symmetric:
+        cout = cin.copy()
+    return cin, cout, bool(directed)
+
+
+def validate_betweenness(csr, bc, sources=None, normalized=False, directed=None):
+    """Host-side check (numpy / scipy) that `bc` is the betweenness centrality of the simple graph of `csr` -- an edge u -> v
+    iff u != v and a stored non-zero entry A[v, u] exists; directed=None reads it as undirected iff that pattern is
+    symmetric, False takes every edge in both directions -- summed over `sources` (None: all csr.num_rows vertices) and scaled
+    as networkx.betweenness_centrality(endpoints=False) scales: recomputed from host BFS levels (betweenness_by_levels).  Raises
+    ValueError naming the first offender; returns the largest relative error.  The bound is derived, not measured: every term
+    is >= 0, so a value's relative error is at most the roundings on its longest chain times 2^-53:
+    4 (D (longest row + 4) + sources) 2^-53, D the deepest search -- device and host round independently.  Zeros must be zeros.
+    `bc` may be longer than the matrix (the drivers pad it): the extra vertices must hold 0."""
+    nr, nc = int(csr.num_rows), int(csr.num_cols)
+    got = np.asarray(bc, dtype=np.float64)
+    n = got.shape[0] if got.ndim == 1 else -1
+    if n < max(nr, nc):
+        raise ValueError("validate_betweenness: %d values for a %d x %d matrix" % (n, nr, nc))
+    cin, cout, directed = _bc_patterns(csr, directed)
+    A_in = _pattern_as_scipy(cin, n)
+    A_out = A_in if cout is None else _pattern_as_scipy(cout, n)
+    src = list(range(nr)) if sources is None else [int(s) for s in sources]
+    if any(s < 0 or s >= nr for s in src):
+        raise ValueError("validate_betweenness: a source outside 0 .. %d" % (nr - 1))
+    scale = _bc_scale(nr, len(src), normalized, directed)
+    want = np.zeros(n, dtype=np.float64)
+    depth = 1
+    for s in src:
+        level = _bfs_levels_of(A_out, [s], n)
+        sigma, delta = betweenness_by_levels(cin, cout, level)
+        if not np.all(np.isfinite(sigma)):
+            continue                                         # (the drivers skip such a source and say so)
+        want += np.where(level >= 2, scale * delta, 0.0)
+        depth = max(depth, int(level.max()))
+    longest = max(int(np.diff(A_in.indptr).max()), int(np.diff(A_out.indptr).max())) if n else 0
+    bound = 4.0 * (depth * (longest + 4) + len(src)) * 2.0 ** -53
+    if np.any(got[nr:] != 0):
+        v = nr + int(np.flatnonzero(got[nr:] != 0)[0])
+        raise ValueError("validate_betweenness: padding vertex %d is given %.17g" % (v, got[v]))
+    if not np.array_equal(got == 0, want == 0):
+        v = int(np.flatnonzero((got == 0) != (want == 0))[0])
+        raise ValueError("validate_betweenness: vertex %d is given %.17g, its betweenness is %.17g" % (v, got[v], want[v]))
+    miss = ~(np.abs(got - want) <= bound * want)
+    if np.any(miss):
+        v = int(np.flatnonzero(miss)[0])
+        raise ValueError("validate_betweenness: vertex %d is given %.17g, its betweenness is %.17g (relative bound %.3g)"
+                         % (v, got[v], want[v], bound))
+    live = want > 0
+    return float(np.max(np.abs(got[live] - want[live]) / want[live])) if np.any(live) else 0.0
+
+
 class HipBackend:
     """Allocation / transfer hooks of the drivers.  The CPU tests substitute a stand-in with the
     same methods to exercise the distributed control flow over gloo."""
@@ -1236,6 +1378,113 @@ class KCore(_GraphApp):
         mask = self.core_ >= k
         mask[self.n_real_:] = False
         return mask
+
+
+class BetweennessCentrality(_GraphApp):
+    """Betweenness centrality (an extension: the reference has no such driver): Brandes' algorithm, one search per source.  The
+    search is an app.BFS this object owns, loaded with the simple pattern of the matrix (io.simple_pattern: zero values, the
+    diagonal and duplicates dropped, rows ascending); its levels stay on the device, and gl_bc_accumulate
+    counts the shortest paths level by level through that BFS's SpMV plan and adds every vertex's dependency, pulled through
+    the transposed pattern's plan -- a second boolean SpMVModule, which exists only when the pattern is not symmetric."""
+
+    def __init__(self, num_channels=M.num_hbm_channels, spmv_out_buf_len=0, spmspv_out_buf_len=0, vec_buf_len=0, comm=None,
+                 backend=None):
+        super().__init__(num_channels, comm, backend)
+        if self.comm.distributed:
+            # (before anything touches the device)
+            raise NotImplementedError("BetweennessCentrality: row shards are not supported -- gl_bc_accumulate reads the level and "
+                                      "the path count of every column of a row, so every rank would need both whole matrices")
+        self.buf_lens_ = (spmv_out_buf_len, vec_buf_len)
+        self.bfs_ = BFS(num_channels, spmv_out_buf_len, spmspv_out_buf_len, vec_buf_len, backend=self.backend)
+        self.SpMV_ = self.bfs_.SpMV_
+        self.out_ = None                 # the transposed pattern's module (a pattern that is not symmetric, or directed=True)
+        for m in self.bfs_.modules_:
+            self.add_module(m)
+        self.sent_ = self.empty_ = False
+        self.directed_ = None
+        self.bc_ = self.sources_ = self.depths_ = self.reached_ = self.orphans_ = self.overflowed_ = None
+
+    def load_and_format_matrix(self, csr_float_npz_path, skip_empty_rows=True, directed=None):
+        """directed=None: undirected iff the pattern is symmetric; False on an asymmetric pattern takes every edge in both
+        directions (io.symmetrize_simple); True keeps two plans even when the pattern is symmetric."""
+        csr = self._load(csr_float_npz_path)
+        n_real = csr.num_rows
+        self._pad(csr)
+        cin, cout, self.directed_ = _bc_patterns(csr, directed)      # (after padding: padding vertices have empty rows)
+        self.n_, self.n_real_ = cin.num_rows, n_real
+        self.empty_ = cin.nnz == 0                                  # an empty graph: nothing is loaded, run() launches nothing
+        self.out_ = None
+        self.modules_ = list(self.bfs_.modules_)
+        if not self.empty_:
+            self.bfs_.load_and_format_matrix(cin, skip_empty_rows)
+            assert self.bfs_.n_ == self.n_
+            if cout is not None:
+                self.out_ = self.backend.SpMVModule(self.num_channels_, *self.buf_lens_)
+                self.out_.set_semiring(M.LogicalSemiring)
+                self.out_.set_mask_type(M.kNoMask)
+                self.out_.blocking = False
+                self.out_.load_and_format_matrix(cout, skip_empty_rows)
+                self.add_module(self.out_)
+        self.sent_ = False
+
+    def get_nnz(self):
+        return 0 if self.empty_ else self.SpMV_.get_nnz()
+
+    def send_matrix_host_to_device(self):
+        if not self.empty_:
+            self.bfs_.send_matrix_host_to_device()
+            if self.out_ is not None:
+                self.out_.send_matrix_host_to_device()
+        self.sent_ = True
+
+    def run(self, sources=None, normalized=False, depth_hint=16):
+        """-> float64[n_]: the betweenness centrality of every vertex (padding vertices: 0) summed over `sources` (an iterable of
+        real vertices; None: all of them) and scaled exactly as networkx.betweenness_centrality(k=len(sources),
+        endpoints=False) scales it -- 1 / ((n - 1)(n - 2)) when normalised and n > 2, otherwise 0.5 when undirected, times
+        n / k when k < n -- with the factor passed to the kernel, so that no extra pass runs.  Per source: bfs_.pull_push(s, N),
+        N = depth_hint, then gl_bc_accumulate on the levels still on the device.  A search whose deepest level is N + 1 may be
+        truncated (the last iteration still found vertices): N is doubled, capped at n_, the source is searched again before
+        anything is accumulated, and the larger N is kept for the later sources; a smaller depth proves the search finished.
+        Leaves bc_, sources_, depths_ and reached_ (per source: the deepest level, the vertices of level >= 1), orphans_ (0: the
+        levels are BFS results), overflowed_ (the sources whose path counts overflowed f64: they contribute nothing, a
+        RuntimeWarning names them) and directed_."""
+        if not self.sent_:
+            raise RuntimeError("BetweennessCentrality.run(): send_matrix_host_to_device first")
+        B, n, nr = self.backend, self.n_, self.n_real_
+        src = list(range(nr)) if sources is None else [int(s) for s in sources]
+        if any(s < 0 or s >= nr for s in src):
+            raise ValueError("BetweennessCentrality.run(): a source outside the real vertices 0 .. %d" % (nr - 1))
+        self.sources_, self.depths_, self.reached_, self.orphans_, self.overflowed_ = src, [], [], 0, []
+        if self.empty_ or not src:                                   # nobody lies between two others: nothing is launched
+            self.depths_, self.reached_ = [1] * len(src), [1] * len(src)
+            self.bc_ = np.zeros(n, dtype=np.float64)
+            return self.bc_
+        scale = _bc_scale(nr, len(src), normalized, self.directed_)
+        N = max(1, min(int(depth_hint), n))
+        bc = B.alloc(2 * n, np.float32)                              # (n doubles)
+        for i, s in enumerate(src):
+            while True:
+                deepest = int(self.bfs_.pull_push(s, N).max())
+                if deepest < N + 1 or N >= n:
+                    break
+                N = min(2 * N, n)
+            levels = self.bfs_.levels_[0]
+            depth, reached, orphans, nonfinite = self.SpMV_.bc_accumulate(self.out_, levels, bc, scale, i > 0)
+            if depth != deepest:
+                raise RuntimeError("BetweennessCentrality.run(): gl_bc_accumulate saw depth %d, the search from %d returned depth %d"
+                                   % (depth, s, deepest))
+            self.depths_.append(depth)
+            self.reached_.append(reached)
+            self.orphans_ += orphans
+            if nonfinite:
+                self.overflowed_.append(s)
+        B.sync()
+        self.bc_ = B.download(bc, np.float64, n)
+        if self.overflowed_:
+            import warnings
+            warnings.warn("BetweennessCentrality.run(): the shortest-path counts of the searches from %s overflowed f64; these sources "
+                          "contribute nothing" % self.overflowed_, RuntimeWarning, stacklevel=2)
+        return self.bc_
 
 
 class PageRank(_GraphApp):

@@ -41,7 +41,7 @@ EXPORTS = [
     "gl_spmv_plan_create", "gl_spmv_plan_create_ex", "gl_spmv_plan_destroy", "gl_spmv_plan_describe", "gl_spmv_plan_export", "gl_spmv_run", "gl_spmv_plan_chain",
     "gl_spmv_plan_bits_words", "gl_pack_bits", "gl_unpack_bits", "gl_bfs_bits_begin_from", "gl_spmv_run_bits", "gl_bfs_pull_step",
     "gl_bfs_parents", "gl_bfs_parents_entries", "gl_spmv_plan_rows_sorted",
-    "gl_cc_begin", "gl_cc_hook", "gl_cc_finish", "gl_cc_labels", "gl_tc_count", "gl_kcore",
+    "gl_cc_begin", "gl_cc_hook", "gl_cc_finish", "gl_cc_labels", "gl_tc_count", "gl_kcore", "gl_bc_accumulate",
     "gl_prof_begin", "gl_prof_end", "gl_span_begin", "gl_span_end",
     "gl_sssp_parents", "gl_sssp_parents_entries",
     "gl_pagerank_ctl_bytes", "gl_pagerank_begin", "gl_pagerank_update",
@@ -117,6 +117,7 @@ def lib():
         "gl_cc_begin": [vp, u32], "gl_cc_hook": [vp, vp], "gl_cc_finish": [vp, u32, vp, vp], "gl_cc_labels": [vp, vp, vp],
         "gl_tc_count": [vp, vp, vp],
         "gl_kcore": [vp, vp, vp, P(u32)],
+        "gl_bc_accumulate": [vp, vp, vp, vp, ctypes.c_double, i32, vp, P(u32)],
         "gl_spmv_run": [vp, vp, vp, vp, i32, f32, i32],
         "gl_prof_begin": [u32, u32], "gl_prof_end": [P(ctypes.c_double), P(u32)], "gl_span_begin": [], "gl_span_end": [P(ctypes.c_double)],
         "gl_sssp_parents": [vp, vp, f32, u32, vp, vp], "gl_sssp_parents_entries": [vp, vp, f32, u32, vp, P(u64)],
@@ -464,6 +465,21 @@ class SpMVPlan:
         stats = (ctypes.c_uint32 * 4)(0xdeadbeef, 0xdeadbeef, 0xdeadbeef, 0xdeadbeef)
         check(lib().gl_kcore(ctypes.c_void_p(self.handle), _p(core), _p(order), stats))
         return tuple(int(x) for x in stats)
+
+    def bc_accumulate(self, plan_out, level, bc, scale=1.0, accumulate=False, sigma=None, stats=True):
+        """gl_bc_accumulate with this plan as plan_in (row v: the vertices v is pulled from) and `plan_out` as the transposed
+        pattern's plan (None, or this plan: the pattern is symmetric): bc[u] = (accumulate ? bc[u] : 0) + scale * delta[u] on
+        the vertices of level >= 2 of `level` (num_rows device floats, the drivers' levels), delta = Brandes' dependency of the
+        search the levels describe, in f64.  `bc` is num_rows device doubles, fully written unless `accumulate`; `sigma`
+        (optional, num_rows device doubles) receives the path counts.  -> (depth D, vertices of level >= 1, orphans, non-finite
+        sigmas), for which the call waits at its end; stats=False: None, and only the wait behind the bucketing remains.  With
+        a non-finite sigma nothing is added.  Both plans are square, whole, their rows strictly ascending sets
+        (io.simple_pattern prepares them)."""
+        out = self if plan_out is None else plan_out
+        st = (ctypes.c_uint32 * 4)(0xdeadbeef, 0xdeadbeef, 0xdeadbeef, 0xdeadbeef) if stats else None
+        check(lib().gl_bc_accumulate(ctypes.c_void_p(self.handle), ctypes.c_void_p(out.handle), _p(level), _p(bc),
+                                     ctypes.c_double(float(scale)), 1 if accumulate else 0, _p(sigma), st))
+        return tuple(int(x) for x in st) if stats else None
 
     def rows_sorted(self):
         """gl_spmv_plan_rows_sorted: do the columns of every row of the plan's CSR copy ascend?"""

@@ -63,17 +63,21 @@ __device__ __forceinline__ uint32_t kc_lower_bound(const uint32_t *s, uint32_t n
 }
 
 // the plan's first call, behind the row check (every column is < n): is (u, v) stored for every (v, u)?  A wavefront per row.
+// (u, v) is looked up in the PARTNER's rows: the plan's own for the symmetry verdict, another plan's for gl_bc_accumulate's
+// "is plan_out the transpose" (gl_bc.hip), which also looks the diagonal entries up.
 __global__ __launch_bounds__(256) void kcore_symmetric_kernel(const uint32_t *__restrict__ row_ptr, const uint32_t *__restrict__ row_idx,
-                                                              uint32_t n, uint32_t nz_base, uint32_t *__restrict__ verdict) {
+                                                              uint32_t n, uint32_t nz_base, const uint32_t *__restrict__ prow_ptr,
+                                                              const uint32_t *__restrict__ prow_idx, uint32_t pnz_base, bool self,
+                                                              uint32_t *__restrict__ verdict) {
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     bool bad = false;
     for (uint64_t v = blockIdx.x * 4u + wave; v < n; v += gridDim.x * 4u) {
         const uint32_t b = row_ptr[v] - nz_base, e = row_ptr[v + 1u] - nz_base;
         for (uint64_t j = (uint64_t)b + lane; j < e; j += 64u) {
             const uint32_t u = row_idx[j];
-            if (u == (uint32_t)v) continue;
-            const uint32_t ub = row_ptr[u] - nz_base, lu = row_ptr[u + 1u] - nz_base - ub;
-            bad |= lu == 0u || row_idx[ub + kc_lower_bound(row_idx + ub, lu, (uint32_t)v)] != (uint32_t)v;
+            if (self && u == (uint32_t)v) continue;
+            const uint32_t ub = prow_ptr[u] - pnz_base, lu = prow_ptr[u + 1u] - pnz_base - ub;
+            bad |= lu == 0u || prow_idx[ub + kc_lower_bound(prow_idx + ub, lu, (uint32_t)v)] != (uint32_t)v;
         }
     }
     if (bad) atomicOr(verdict, 1u);
@@ -205,6 +209,21 @@ __global__ void kcore_turn_kernel(uint32_t *ctl, uint32_t n) {
     }
 }
 
+int kcore_check_transpose(gl_spmv_plan p, gl_spmv_plan partner, uint32_t *d_word, uint32_t *h_verdict) {
+    hipStream_t s = ctx().stream;
+    const uint32_t n = p->num_rows;
+    *h_verdict = 1;
+    hipError_t e = hipMemsetAsync(d_word, 0, 4, s);
+    if (e == hipSuccess) {
+        const unsigned grid = std::max(1u, std::min<unsigned>(cdiv(n, 4u), (unsigned)ctx().num_cus * 16u));
+        kcore_symmetric_kernel<<<grid, 256, 0, s>>>(p->d_csr_indptr, p->d_csr_indices, n, p->csr_nz_base, partner->d_csr_indptr,
+                                                    partner->d_csr_indices, partner->csr_nz_base, partner == p, d_word);
+        e = hipGetLastError();
+    }
+    GL_HIP(e != hipSuccess ? e : d2h_word_sync(h_verdict, d_word, s));
+    return GL_OK;
+}
+
 static unsigned kcore_stream_grid(uint32_t n) { return std::max(1u, std::min<unsigned>(cdiv(n, 256u), (unsigned)ctx().num_cus * 8u)); }
 
 // the refusals, the plan's two verdicts and its scratch, on first use (one synchronisation)
@@ -232,16 +251,9 @@ static int kcore_prepare(gl_spmv_plan p, const char *who) {
         if (e != hipSuccess) return set_error(GL_ERR_HIP, "%s: hipMalloc(%zu bytes of control record and queue): %s", who, bytes, hipGetErrorString(e));
     }
     if (p->kcore_symmetric < 0) {
-        hipStream_t s = ctx().stream;
-        uint32_t *ctl = reinterpret_cast<uint32_t *>(p->d_kcore_scratch);
         uint32_t h = 1;
-        hipError_t e = hipMemsetAsync(ctl, 0, kKcCtlBytes, s);
-        if (e == hipSuccess) {
-            const unsigned grid = std::max(1u, std::min<unsigned>(cdiv(n, 4u), (unsigned)ctx().num_cus * 16u));
-            kcore_symmetric_kernel<<<grid, 256, 0, s>>>(p->d_csr_indptr, p->d_csr_indices, n, p->csr_nz_base, ctl);
-            e = hipGetLastError();
-        }
-        GL_HIP(e != hipSuccess ? e : d2h_word_sync(&h, ctl, s));
+        rc = kcore_check_transpose(p, p, reinterpret_cast<uint32_t *>(p->d_kcore_scratch), &h);
+        if (rc != GL_OK) return rc;
         p->kcore_symmetric = h == 0u ? 1 : 0;
     }
     if (p->kcore_symmetric == 0)

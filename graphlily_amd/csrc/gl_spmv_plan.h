@@ -6,6 +6,7 @@
 #include "gl_common.h"
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -163,6 +164,14 @@ inline UnitLayout layout_units(const BlockPlan &bp, const std::vector<uint64_t> 
 
 }  // namespace gl
 
+namespace gl {
+// a number no two plans of a process share (gl_spmv_plan_s::uid)
+inline uint64_t plan_uid() {
+    static std::atomic<uint64_t> next{0};
+    return ++next;
+}
+}  // namespace gl
+
 struct gl_spmv_plan_s {
     uint32_t num_rows = 0, num_cols = 0, row_begin = 0, row_end = 0;
     uint64_t nnz = 0;
@@ -239,6 +248,18 @@ struct gl_spmv_plan_s {
     // tc_rows_ok above), and the pass's scratch -- 256 bytes of control record + num_rows words of queue
     int kcore_symmetric = -1;
     unsigned char *d_kcore_scratch = nullptr;
+    // gl_bc_accumulate (gl_bc.hip), as plan_in, set up by the first call: the pass's scratch -- 256 bytes of control words, two
+    // arrays of num_rows + 2 level offsets, num_rows words of queue, num_rows doubles each of sigma and coef -- the page-locked
+    // room the offsets are read back to, and the verdict on the last plan_out that was not this plan itself: is it the
+    // transpose?  (the partner is remembered by handle AND uid: a later plan may be allocated where a destroyed one was;
+    // plan_out == plan_in asks for kcore_symmetric above)
+    uint64_t uid = gl::plan_uid();
+    unsigned char *d_bc_scratch = nullptr;
+    uint32_t *h_bc_pinned = nullptr;
+    size_t bc_pinned_words = 0;
+    const gl_spmv_plan_s *bc_partner = nullptr;
+    uint64_t bc_partner_uid = 0;
+    int bc_transpose_ok = -1;
     // GL_PLAN_REFERENCE_ORDER: the shard's plain CSR (indptr rebased to 0, values kept), evaluated a thread per row in
     // the reference's own order -- a diagnostic layout, not a fast one
     bool reference_order = false;
@@ -370,6 +391,11 @@ void spmspv_detach_everywhere(gl_spmv_plan dying);
 // gl_tc.hip: establish p->tc_rows_ok (are the rows strictly ascending sets of columns below num_cols?) on first use, with one
 // kernel and one synchronisation; for a plan that keeps the row copy.  Shared by gl_tc_count and gl_kcore.
 int tc_check_rows(gl_spmv_plan p, const char *who);
+// gl_kcore.hip: is (u, v) stored in `partner` for every entry (v, u) of p?  -> *h_verdict = 0 if so.  One kernel and one
+// synchronisation; both plans keep the row copy, are square and whole, their rows strictly ascending sets of columns below
+// num_rows (tc_check_rows); d_word is a device word the check may use.  partner == p: is the pattern symmetric (gl_kcore's
+// verdict, p->kcore_symmetric, which gl_bc_accumulate shares).
+int kcore_check_transpose(gl_spmv_plan p, gl_spmv_plan partner, uint32_t *d_word, uint32_t *h_verdict);
 // gl_spmv.hip: y initialisation for plans whose units fold into y
 int spmv_init_rows(int op, int mask_type, uint32_t r0, uint32_t r1, const float *mask, float *y, float zero, hipStream_t s);
 }  // namespace gl

@@ -9,6 +9,7 @@ Mirrors (names, argument meaning, in-place behaviour):
   util_normalize_csr_matrix_by_outdegree         io/data_formatter.h:36-51
   triangle_orient                                io/data_formatter.h (util_triangle_orient: an extension, no reference counterpart)
   symmetrize_simple                              io/data_formatter.h (util_symmetrize_simple: an extension, no reference counterpart)
+  simple_pattern                                 io/data_formatter.h (util_simple_pattern: an extension, no reference counterpart)
 The FPGA-only formatters (csr2cpsr, formatCSC: io/data_formatter.h:54-721) have no counterpart here:
 the device layout is produced inside gl_spmv_plan_create / gl_spmspv_plan_create.
 """
@@ -125,6 +126,34 @@ def symmetrize_simple(csr_matrix):
         raise ValueError("symmetrize_simple: %d entries do not fit 32-bit offsets" % int(out_indptr[n]))
     sym = CSRMatrix(n, n, np.ones(b.shape[0], dtype=np.float32), b.astype(np.uint32), out_indptr.astype(np.uint32))
     return sym, deg.astype(np.uint32)
+
+
+def simple_pattern(csr_matrix):
+    """The matrix preparation of BetweennessCentrality (an extension) -> (csr_in, csr_out or None, symmetric).  The simple
+    directed graph of the matrix has an edge u -> v iff u != v and a stored non-zero entry A[v, u] exists: zero values, the
+    diagonal and duplicates are dropped, the direction is KEPT.  Row v of csr_in lists the vertices v is pulled from, row u of
+    csr_out (the transposed pattern) the out-neighbours of u; both are n x n, n = max(num_rows, num_cols), every value 1, the
+    columns of every row ascending -- the strictly ascending sets gl_bc_accumulate asks for.  `symmetric` says whether the
+    two are the same matrix; csr_out is then None.  Applied after padding: padding vertices have empty rows."""
+    n = max(int(csr_matrix.num_rows), int(csr_matrix.num_cols))
+    indptr = csr_matrix.adj_indptr.astype(np.int64)[:csr_matrix.num_rows + 1]
+    nnz = int(indptr[-1])
+    rows = np.repeat(np.arange(csr_matrix.num_rows, dtype=np.int64), np.diff(indptr))
+    cols = csr_matrix.adj_indices[:nnz].astype(np.int64)
+    keep = (np.asarray(csr_matrix.adj_data[:nnz]) != 0) & (rows != cols)
+    rows, cols = rows[keep], cols[keep]
+    if rows.shape[0] > 0xFFFFFFFF:
+        raise ValueError("simple_pattern: %d entries do not fit 32-bit offsets" % rows.shape[0])
+
+    def build(key):      # (sorted by (row, column), once each)
+        a, b = key // n, key % n
+        ip = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(np.bincount(a, minlength=n), out=ip[1:])
+        return CSRMatrix(n, n, np.ones(b.shape[0], dtype=np.float32), b.astype(np.uint32), ip.astype(np.uint32))
+
+    key_in, key_out = np.unique(rows * n + cols), np.unique(cols * n + rows)
+    symmetric = bool(np.array_equal(key_in, key_out))
+    return build(key_in), (None if symmetric else build(key_out)), symmetric
 
 
 def sssp_add_self_edges(csr_matrix):

@@ -295,6 +295,20 @@ class SpMVModule(BaseModule):
         self._finish(core_buf, order_buf)
         return stats
 
+    def bc_accumulate(self, out_module, level_buf, bc_buf, scale=1.0, accumulate=False, sigma_buf=None, stats=True):
+        """Extension (gl_bc_accumulate): adds scale x Brandes' dependency of the search whose levels are in `level_buf`
+        (get_num_rows() floats) to `bc_buf` (as many doubles; accumulate=False: overwrites it).  This module's matrix is the
+        pulling side (row v: the vertices v is pulled from), `out_module` (None: the pattern is symmetric) holds the transposed
+        pattern.  `sigma_buf` (optional, doubles) receives the path counts.  -> (depth, reached, orphans, non-finite sigmas),
+        or None with stats=False.  Raises GraphLilyError (GL_ERR_UNSUPPORTED) when a plan keeps no row copy (only the (||,&&)
+        layout does), is not square, is a row shard, its rows are no strictly ascending sets, or the two are not each other's
+        transpose (io.simple_pattern prepares them)."""
+        if self.plan_ is None or (out_module is not None and out_module.plan_ is None):
+            _fatal("SpMVModule.bc_accumulate: send_matrix_host_to_device first")
+        st = self.plan_.bc_accumulate(None if out_module is None else out_module.plan_, level_buf, bc_buf, scale, accumulate, sigma_buf, stats)
+        self._finish(bc_buf, sigma_buf)
+        return st
+
     def fused_bfs_ok(self):
         if self.plan_ is None or not self._plan_serves(self.semiring_.op) or self.semiring_.zero != 0.0:
             return False

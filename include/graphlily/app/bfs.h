@@ -308,7 +308,10 @@ public:
     uint32_t push_iterations() const { return push_iterations_; }
 
     void load_and_format_matrix(std::string csr_float_npz_path, bool skip_empty_rows) {
-        CSRMatrix<float> csr_matrix = graphlily::io::load_csr_matrix_from_float_npz(csr_float_npz_path);
+        load_and_format_matrix(graphlily::io::load_csr_matrix_from_float_npz(csr_float_npz_path), skip_empty_rows);
+    }
+    // extension: a matrix the caller has prepared (app::BetweennessCentrality loads the simple pattern of its graph)
+    void load_and_format_matrix(CSRMatrix<float> csr_matrix, bool skip_empty_rows) {
         graphlily::io::util_round_csr_matrix_dim(csr_matrix, num_channels_ * graphlily::pack_size, num_channels_ * graphlily::pack_size);
         for (auto &x : csr_matrix.adj_data) x = 1;
         CSCMatrix<float> csc_matrix = graphlily::io::csr2csc(csr_matrix);
@@ -395,6 +398,10 @@ public:
         if (!distance.empty()) levels.upload(distance.data(), sizeof(graphlily::val_t) * distance.size());
         return parents_(levels);
     }
+    // extension (app::BetweennessCentrality): the level vector of the last pull / push / pull_push, still on the device, and the
+    // module whose plan pulled it
+    const DeviceBuffer &last_levels() const { return last_levels_; }
+    module::SpMVModule<graphlily::val_t, graphlily::val_t> *spmv_module() { return SpMV_; }
     uint32_t orphans() const { return orphans_; }   // vertices of level >= 2 without a predecessor in the last parents() (0 for a BFS result)
 
     // the reference's four wall-clock buckets (bfs.h:222-347) around the module-call sequence, every call followed by a device

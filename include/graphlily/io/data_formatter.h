@@ -113,6 +113,47 @@ CSRMatrix<data_type> util_symmetrize_simple(CSRMatrix<data_type> const &m, std::
     return out;
 }
 
+// The matrix preparation of app::BetweennessCentrality (an extension): the simple DIRECTED graph of m -- an edge u -> v iff u != v
+// and a stored non-zero entry A[v,u] exists: zero values, the diagonal and duplicates are dropped, the direction is kept.  Row v of
+// `in` lists the vertices v is pulled from, row u of `out` (the transposed pattern) the out-neighbours of u; both n x n, n =
+// max(num_rows, num_cols), every value 1, columns ascending.  Returns whether the two are the same matrix (`out` is then left
+// empty, 0 x 0).  Apply after padding.
+template <typename data_type>
+bool util_simple_pattern(CSRMatrix<data_type> const &m, CSRMatrix<data_type> &in, CSRMatrix<data_type> &out) {
+    const uint64_t n = std::max(m.num_rows, m.num_cols);
+    std::vector<uint64_t> key_in, key_out;
+    key_in.reserve(m.adj_indptr[m.num_rows]);
+    for (uint32_t v = 0; v < m.num_rows; v++)
+        for (uint32_t i = m.adj_indptr[v]; i < m.adj_indptr[v + 1]; i++) {
+            const uint64_t u = m.adj_indices[i];
+            if (u == v || m.adj_data[i] == data_type(0)) continue;
+            key_in.push_back(v * n + u);
+        }
+    std::sort(key_in.begin(), key_in.end());
+    key_in.erase(std::unique(key_in.begin(), key_in.end()), key_in.end());
+    key_out.reserve(key_in.size());
+    for (uint64_t k : key_in) key_out.push_back(k % n * n + k / n);
+    std::sort(key_out.begin(), key_out.end());
+    auto build = [n](const std::vector<uint64_t> &key, CSRMatrix<data_type> &r) {      // (sorted by (row, column), once each)
+        r.num_rows = r.num_cols = (uint32_t)n;
+        r.adj_indptr.assign(n + 1, 0);
+        r.adj_indices.clear();
+        r.adj_indices.reserve(key.size());
+        for (uint64_t k : key) {
+            r.adj_indptr[k / n + 1]++;
+            r.adj_indices.push_back((uint32_t)(k % n));
+        }
+        for (uint64_t v = 0; v < n; v++) r.adj_indptr[v + 1] += r.adj_indptr[v];
+        r.adj_data.assign(r.adj_indices.size(), data_type(1));
+    };
+    build(key_in, in);
+    const bool symmetric = key_in == key_out;
+    out = CSRMatrix<data_type>();
+    out.num_rows = out.num_cols = 0;
+    if (!symmetric) build(key_out, out);
+    return symmetric;
+}
+
 }  // namespace io
 }  // namespace graphlily
 

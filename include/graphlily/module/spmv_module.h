@@ -199,6 +199,18 @@ public:
         GRAPHLILY_CHECK(gl_kcore(plan_, (uint32_t *)core.ptr(), order, stats));
         finish_();
     }
+    // extension (gl_bc_accumulate): adds scale x Brandes' dependency of the search whose levels are in `level` (get_num_rows()
+    // floats) to `bc` (as many doubles; accumulate = false overwrites it).  This module's matrix is the pulling side (row v: the
+    // vertices v is pulled from), `out` holds the transposed pattern (nullptr: the pattern is symmetric); both in the (||,&&)
+    // layout, rows strictly ascending (graphlily::io::util_simple_pattern prepares them).  stats (optional, 4 host words)
+    // receives {depth, reached vertices, orphans, non-finite sigmas}; the call then waits at its end.
+    void bc_accumulate(SpMVModule *out, DeviceBuffer level, DeviceBuffer bc, double scale, bool accumulate, double *sigma = nullptr,
+                       uint32_t *stats = nullptr) {
+        barrier_();
+        GRAPHLILY_CHECK(gl_bc_accumulate(plan_, out ? out->plan_ : plan_, (const float *)level.rptr(), (double *)bc.ptr(), scale,
+                                         accumulate ? 1 : 0, sigma, stats));
+        finish_();
+    }
     uint32_t get_num_rows() { return csr_matrix_float_.num_rows; }
     uint32_t get_num_cols() { return csr_matrix_float_.num_cols; }
     uint32_t get_nnz() { return csr_matrix_float_.adj_indptr[csr_matrix_float_.num_rows]; }

@@ -338,6 +338,36 @@ int gl_tc_count(gl_spmv_plan plan, uint64_t *d_total, uint64_t *d_per_vertex /* 
  * caches) and that the pattern is symmetric, caches both in the plan and allocates 256 + 4 n bytes of scratch, which
  * gl_spmv_plan_destroy frees. */
 int gl_kcore(gl_spmv_plan plan, uint32_t *d_core, uint32_t *d_order /* may be NULL */, uint32_t *h_stats /* may be NULL, 4 words */);
+/* Extension: BETWEENNESS CENTRALITY, the dependency accumulation of one finished search (Brandes), over the plain CSR copies that
+ * GL_PLAN_BOOLEAN plans keep (gl_bc.hip).  plan_in is a square whole-matrix plan whose row v is the strictly
+ * ascending set of the vertices u that v is pulled from (an entry A[v,u] is the edge u -> v, as in gl_bfs_parents); plan_out is
+ * the same for the transposed pattern (row u: the out-neighbours of u) -- for a symmetric pattern pass the same handle twice
+ * (io.simple_pattern prepares both).  d_level is the drivers' level array (n = num_rows floats: 1 on a source, it + 1 on a vertex
+ * reached in iteration it, 0 unreached), D = max level; all arithmetic is f64:
+ *   sigma[v] = 1 on level 1;  the sum over u in row_in(v) with level[u] == level[v] - 1 of sigma[u] on level >= 2;  0 on level 0
+ *   delta[u] = sigma[u] * the sum over v in row_out(u) with level[v] == level[u] + 1 and sigma[v] > 0 of (1 + delta[v]) / sigma[v]
+ *   d_bc[u]  = (accumulate ? d_bc[u] : 0) + scale * delta[u] on level >= 2;   (accumulate ? d_bc[u] : 0) elsewhere
+ * Every vertex of level 1 is a source; with one source delta is Brandes' dependency.  d_bc (n doubles) is fully written when
+ * accumulate == 0, d_sigma (n doubles, may be NULL: scratch of the plan) always.  h_stats (may be NULL) receives four HOST words
+ * {D, vertices of level >= 1, orphans, non-finite sigmas}: an ORPHAN is a vertex of level >= 2 without an in-neighbour one level
+ * up (the array is no BFS result): its sigma is 0, it contributes nothing and is counted, as in gl_bfs_parents.  If any sigma is
+ * NOT FINITE (path counts overflow f64 on lattice-like graphs) the backward sweep does not run -- its launches are gated by a
+ * word on the device -- and d_bc is left as accumulate ? d_bc : 0.
+ * Deterministic: no floating-point atomics; every vertex's sum is formed by one owner in an order that depends only on the row,
+ * so two calls on the same inputs give the same bits.
+ * The call buckets the vertices by level into a queue (scratch of plan_in), waits ONCE to read the D + 2 level offsets back,
+ * enqueues one launch per level 2 .. D pulling sigma through plan_in and one per level D .. 2 pulling through plan_out on the
+ * library's stream, and waits at the end only if h_stats is given.
+ * GL_ERR_UNSUPPORTED for a plan without the row copy, with num_rows != num_cols, for a row shard, for rows that are not strictly
+ * ascending or hold a column >= num_cols (the verdict gl_tc_count caches, on both plans), and for plans that are not each
+ * other's transpose: plan_out == plan_in asks for the symmetry verdict gl_kcore caches; otherwise every entry of plan_in is
+ * looked up in plan_out and the entry counts are compared, cached in plan_in with the partner's handle.  A level that is no
+ * whole number 0 .. n, or d_sigma == d_bc, is GL_ERR_INVALID_ARG.  A plan without entries is an empty graph: d_bc as above,
+ * h_stats {D, vertices of level >= 1, vertices of level >= 2, 0}.  The first call allocates about 28 n bytes of scratch, which
+ * gl_spmv_plan_destroy frees. */
+int gl_bc_accumulate(gl_spmv_plan plan_in, gl_spmv_plan plan_out, const float *d_level, double *d_bc, double scale, int accumulate,
+                     double *d_sigma /* may be NULL: plan scratch */,
+                     uint32_t *h_stats /* may be NULL; 4 HOST words: depth D, reached vertices, orphans, non-finite sigmas */);
 /* gl_spmv_run replaces enqueueTask(overlay, mode = 1) (module/spmv_module.h:471-475,
  * hw/overlay.cpp:308-330 -> hw/kernel_spmv_impl.h:392-819):
  *   y[r] = mask_r ? ( zero (+) sum_{i in row r} A_i (x) x[col_i] ) : 0
