@@ -38,7 +38,7 @@ EXPORTS = [
     "gl_spmv_run_typed", "gl_spmspv_run_typed", "gl_ewise_add_typed", "gl_assign_dense_typed", "gl_assign_sparse_typed",
     "gl_assign_sparse_new_frontier_typed", "gl_sparse_to_dense_typed",
     "gl_buf_alloc", "gl_buf_free", "gl_buf_h2d", "gl_buf_d2h", "gl_buf_d2d", "gl_buf_fill_f32", "gl_buf_fill_u32",     "gl_host_alloc", "gl_host_free", "gl_host_pool_alloc", "gl_host_pool_free", "gl_pool_trim", "gl_pool_stats", "gl_host_pool_reserve", "gl_host_fill_u32", "gl_host_sparse_to_dense",
-    "gl_spmv_plan_create", "gl_spmv_plan_create_ex", "gl_spmv_plan_destroy", "gl_spmv_plan_describe", "gl_spmv_plan_export", "gl_spmv_run", "gl_spmv_plan_chain",
+    "gl_spmv_plan_create", "gl_spmv_plan_create_ex", "gl_spmv_plan_destroy", "gl_spmv_plan_describe", "gl_spmv_plan_values_finite", "gl_spmv_plan_export", "gl_spmv_run", "gl_spmv_plan_chain",
     "gl_spmv_plan_bits_words", "gl_pack_bits", "gl_unpack_bits", "gl_bfs_bits_begin_from", "gl_spmv_run_bits", "gl_bfs_pull_step",
     "gl_bfs_parents", "gl_bfs_parents_entries", "gl_spmv_plan_rows_sorted",
     "gl_cc_begin", "gl_cc_hook", "gl_cc_finish", "gl_cc_labels", "gl_tc_count", "gl_kcore", "gl_bc_accumulate",
@@ -109,7 +109,7 @@ def lib():
         "gl_buf_fill_u32": [vp, u32, ctypes.c_size_t],
         "gl_spmv_plan_create": [P(vp), u32, u32, vp, vp, vp, u32, u32],
         "gl_spmv_plan_create_ex": [P(vp), u32, u32, vp, vp, vp, u32, u32, u32],
-        "gl_spmv_plan_destroy": [vp], "gl_spmv_plan_describe": [vp, vp],
+        "gl_spmv_plan_destroy": [vp], "gl_spmv_plan_describe": [vp, vp], "gl_spmv_plan_values_finite": [vp, P(i32)],
         "gl_spmv_plan_export": [vp, i32, vp, ctypes.c_size_t, P(ctypes.c_size_t)], "gl_spmv_plan_chain": [vp, i32, P(i32)],
         "gl_spmv_plan_bits_words": [vp, P(u64)], "gl_pack_bits": [vp, u32, vp], "gl_unpack_bits": [vp, u32, vp], "gl_bfs_bits_begin_from": [vp, u32, vp, u32, vp, u32, vp, vp], "gl_spmv_run_bits": [vp, vp, vp, vp, f32, i32],
         "gl_bfs_pull_step": [vp, vp, vp, vp, f32],
@@ -388,7 +388,9 @@ class SpMVPlan:
             return dict(cached)
         d = _PlanDesc()
         check(lib().gl_spmv_plan_describe(ctypes.c_void_p(self.handle), ctypes.byref(d)))
-        self._info = {"helper": ("gather", "spread", "self-hot", "none")[d.helper], "packed_columns": d.packed_columns,
+        finite = ctypes.c_int(0)
+        check(lib().gl_spmv_plan_values_finite(ctypes.c_void_p(self.handle), ctypes.byref(finite)))
+        self._info = {"finite_values": bool(finite.value), "helper": ("gather", "spread", "self-hot", "none")[d.helper], "packed_columns": d.packed_columns,
                       "nnz": d.nnz, "device_bytes": d.device_bytes, "num_units": d.num_units, "blocks": d.blocks,
                       "segments": d.segments, "max_block_rows": d.max_block_rows, "groups": d.groups,
                       "hot_columns": d.hot_columns, "hot_nnz": d.hot_nnz, "mix": d.mix,

@@ -68,6 +68,14 @@ __global__ __launch_bounds__(kFmtThreads) void fmt_degree_kernel(const uint32_t 
     }
 }
 
+// is any stored value +-inf / NaN (exponent field all ones)?
+__global__ __launch_bounds__(kFmtThreads) void fmt_non_finite_kernel(const uint32_t *__restrict__ data, uint64_t nnz, uint32_t *__restrict__ found) {
+    bool any = false;
+    for (uint64_t i = (uint64_t)blockIdx.x * kFmtThreads + threadIdx.x; i < nnz; i += (uint64_t)gridDim.x * kFmtThreads)
+        any |= (data[i] & 0x7f800000u) == 0x7f800000u;
+    if (any) *found = 1u;
+}
+
 // pass 1 of the column-constant test: any off-diagonal writer leaves its value bits (all writers of a constant
 // column agree; pass 2 finds out whether they did)
 __global__ __launch_bounds__(kFmtThreads) void fmt_pattern_pass1_kernel(const uint32_t *__restrict__ indptr, const uint32_t *__restrict__ indices,
@@ -1102,6 +1110,21 @@ int fmt_column_degrees(DevCsr *c, uint32_t num_cols, std::vector<uint32_t> &deg,
     GL_HIP(hipMemcpyAsync(deg.data(), d_deg.p, (size_t)num_cols * 4u, hipMemcpyDeviceToHost, s));
     GL_HIP(d2h_word_sync(&bad, d_bad.p, s));
     *bad_col = bad ? 1 : 0;
+    return GL_OK;
+}
+
+int fmt_values_finite(DevCsr *c, int *finite) {
+    hipStream_t s = ctx().stream;
+    DevMem d_found;
+    int rc;
+    if ((rc = d_found.alloc(16)) != GL_OK) return rc;
+    GL_HIP(hipMemsetAsync(d_found.p, 0, 16, s));
+    const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((c->nnz + kFmtThreads - 1) / kFmtThreads, (uint64_t)ctx().num_cus * 16u));
+    fmt_non_finite_kernel<<<grid, kFmtThreads, 0, s>>>(c->d_data, c->nnz, d_found.as<uint32_t>());
+    GL_LAUNCH_CHECK();
+    uint32_t found = 0;
+    GL_HIP(d2h_word_sync(&found, d_found.p, s));
+    *finite = found ? 0 : 1;
     return GL_OK;
 }
 

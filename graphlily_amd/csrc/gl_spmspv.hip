@@ -999,9 +999,12 @@ static int spmspv_run_impl(gl_spmspv_plan p, const gl_idx_val *d_vector, const f
     // at it); (min,+) needs zero <= FLOAT_INF -- the scatter's products saturate there, the SpMV's do not, and the
     // final min with zero hides the difference -- and a plan that was not restricted to other semirings
     gl_spmv_plan pull_plan = nullptr;
+    // -- and, for the float semirings, a matrix without +-inf / NaN: row-wise, a column off the frontier meets x = 0 (+inf), and
+    // inf * 0 = -inf + inf = NaN where the scatter never reads the column; such a matrix always scatters
+    const bool finite = p->pull_arith && p->pull_arith->values_finite;
     if (op == GL_OP_ANDOR && zero == 0.0f) pull_plan = p->pull;
-    else if (op == GL_OP_MULADD && zero == 0.0f && p->pull_arith && !(p->pull_arith->flags & GL_PLAN_NO_MULADD)) pull_plan = p->pull_arith;
-    else if (op == GL_OP_ADDMIN && zero <= gl::kFloatInf) pull_plan = p->pull_arith;
+    else if (op == GL_OP_MULADD && zero == 0.0f && finite && !(p->pull_arith->flags & GL_PLAN_NO_MULADD)) pull_plan = p->pull_arith;
+    else if (op == GL_OP_ADDMIN && zero <= gl::kFloatInf && finite) pull_plan = p->pull_arith;
     bool may_pull = pull_plan != nullptr && nrows > 0 && val_type == GL_VAL_FLOAT && div > 0;
     // a caller that knows how many entries the vector holds (gl_spmspv_plan_hint) spares tiny frontiers the
     // decision kernels: they cannot reach the threshold whatever their columns are

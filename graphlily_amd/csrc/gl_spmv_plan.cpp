@@ -259,6 +259,16 @@ static int detect_pattern_host(const HostCsr &a, std::vector<uint32_t> &colbits,
     return GL_OK;
 }
 
+// host twin of fmt_values_finite (gl_format.hip): no stored value of the shard is +-inf / NaN
+static bool values_finite_host(const HostCsr &a) {
+    const uint64_t nz0 = a.nnz ? a.indptr[a.row_begin] : 0;
+    int found = 0;
+#pragma omp parallel for schedule(static) reduction(| : found)
+    for (int64_t i = 0; i < (int64_t)a.nnz; i++)
+        found |= (__builtin_bit_cast(uint32_t, a.data[nz0 + i]) & 0x7f800000u) == 0x7f800000u;
+    return !found;
+}
+
 // host twin of fmt_column_degrees (gl_format.hip): non-zeros per column within the shard
 static int column_degrees_host(const HostCsr &a, std::vector<uint32_t> &deg, int *bad_col) {
     const uint64_t nz0 = a.indptr[a.row_begin];
@@ -704,6 +714,16 @@ static int plan_general(gl_spmv_plan p, const HostCsr &a, const Knobs &k) {
     const BlockPlan bp = plan_blocks(shape, a.indptr, a.row_begin, a.row_end, kMaxPlainRows);
     for (uint32_t b = 0; b < bp.nblocks; b++) p->max_plain_rows = std::max(p->max_plain_rows, bp.bstart[b + 1] - bp.bstart[b]);
 
+    // ---- are all stored values finite?  (the SpMSpV row-wise leg multiplies every column's values by x, 0 off the frontier:
+    //      only a matrix without +-inf / NaN may take it, gl_spmspv.hip)
+    if (on_device) {
+        int finite = 1;
+        if ((rc = fmt_values_finite(staged.c, &finite)) != GL_OK) return rc;
+        p->values_finite = finite != 0;
+    } else {
+        p->values_finite = values_finite_host(a);
+    }
+
     // ---- pattern plan?  every column's stored values are bitwise equal (unweighted graphs, out-degree normalised PageRank
     //      matrices, bench_spmv's 1/num_rows): the stream then carries no values.  Diagonal entries are looked at separately: a
     //      matrix that is column-constant apart from its diagonal (SSSP's unit weights + zero self edges, app/sssp.h:16-62)
@@ -805,9 +825,11 @@ int gl_spmv_plan_create_ex(gl_spmv_plan *plan, uint32_t num_rows, uint32_t num_c
     p->flags = flags;
     int rc;
     if (flags & GL_PLAN_REFERENCE_ORDER) {
+        p->values_finite = gl::values_finite_host(a);
         rc = gl::plan_reference_order(p.get(), a);
     } else if ((flags & GL_PLAN_BOOLEAN) && nnz > 0 && gl::cdiv(num_cols, gl::kBoolPhaseCols) <= gl::kBoolMaxPhases && k.boolean != 0) {
         // (||,&&)-only plans have their own layout (gl_spmv_bool.hip); very wide matrices keep the general one
+        p->values_finite = gl::values_finite_host(a);
         rc = gl::bool_plan_build(p.get(), h_indptr, h_indices, h_data);
         if (rc == GL_OK) rc = gl::bool_plan_compress(p.get());
     } else {
@@ -874,6 +896,12 @@ int gl_spmv_plan_describe(gl_spmv_plan p, gl_spmv_plan_desc *out) {
     out->mix = p->mix;
     out->helper = p->boolean ? GL_HELPER_NONE : p->self_hot ? GL_HELPER_SELF_HOT : p->d_colmap ? GL_HELPER_SPREAD
                   : (p->pattern || p->nhot || p->ncompact) ? GL_HELPER_GATHER : GL_HELPER_NONE;
+    return GL_OK;
+}
+
+int gl_spmv_plan_values_finite(gl_spmv_plan p, int *finite) {
+    GL_ARG(p != nullptr && finite != nullptr);
+    *finite = p->values_finite ? 1 : 0;
     return GL_OK;
 }
 

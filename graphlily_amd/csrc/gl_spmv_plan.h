@@ -213,6 +213,7 @@ struct gl_spmv_plan_s {
     float *d_colval_bycol = nullptr; // pattern plans in that mode: the column values indexed by column
     bool self_hot = false;           // no helper launch: the workgroups gather their (small) hot table from x themselves
     bool pattern = false;            // every column's values are equal: 4-byte entries, z = colval (x) x per run
+    bool values_finite = true;       // no stored value of the shard is +-inf / NaN (established at creation, gl_spmv_plan_values_finite)
     float *d_colval = nullptr, *d_z = nullptr;
     float *d_diag = nullptr;         // pattern plans whose diagonal differs from the column values: A[r][r] per local row
     uint32_t *d_diag_has = nullptr;
@@ -307,6 +308,7 @@ struct StagedCsr {   // a staged copy that lives until the end of the scope
 int devcsr_adopt_rows(DevCsr *c, uint32_t **d_indptr, uint32_t **d_indices);
 bool format_on_device(uint32_t flags, uint64_t nnz);   // policy: GL_PLAN_HOST_FORMAT / GRAPHLILY_PLAN_DEVICE / size
 int fmt_column_degrees(DevCsr *c, uint32_t num_cols, std::vector<uint32_t> &deg, int *bad_col);
+int fmt_values_finite(DevCsr *c, int *finite);   // one reduction over the staged values: none of them is +-inf / NaN
 int fmt_detect_pattern(DevCsr *c, uint32_t num_cols, std::vector<uint32_t> &colbits, std::vector<uint32_t> &diag_has,
                        std::vector<float> &diag_val, int *mismatch, uint64_t *exceptions);
 

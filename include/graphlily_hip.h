@@ -228,6 +228,11 @@ typedef struct gl_spmv_plan_desc {
     int layout, mix, helper;
 } gl_spmv_plan_desc;
 int gl_spmv_plan_describe(gl_spmv_plan plan, gl_spmv_plan_desc *out);
+/* *finite = 1 if no value the plan's shard stores is +-inf or NaN, established at creation by either formatter.  gl_spmspv_run
+ * takes an attached plan's row-wise leg for (+,x) and (min,+) only then: that leg multiplies (adds) EVERY column's values with
+ * an x that is 0 (+inf) off the frontier, and inf * 0 = -inf + inf = NaN, where the scatter never reads those columns.
+ * (A getter of its own: gl_spmv_plan_desc keeps its size.) */
+int gl_spmv_plan_values_finite(gl_spmv_plan plan, int *finite);
 /* Debugging / tests: copy one of the plan's device arrays to the host.  `array` is one of GL_PLAN_ARRAY_*; *bytes
  * receives its size (also when h_dst is NULL or capacity is too small, in which case nothing is copied and
  * GL_ERR_INVALID_ARG is returned for a non-NULL h_dst). */

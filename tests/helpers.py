@@ -117,3 +117,355 @@ def set_knob(monkeypatch, key, value):
         monkeypatch.setenv("GRAPHLILY_DEBUG", ",".join("%s=%s" % kv for kv in cur.items()))
     else:
         monkeypatch.delenv("GRAPHLILY_DEBUG", raising=False)
+
+
+# ------------------------------------------------------------------ matrices that reach every structure of the SpMV layouts
+def csr_from_coo(n_rows, n_cols, rows, cols, data=None):
+    """CSR of (row, col) pairs that are already grouped by ascending row; values default to 1."""
+    indptr = np.zeros(n_rows + 1, np.uint32)
+    np.cumsum(np.bincount(rows, minlength=n_rows), out=indptr[1:])
+    if data is None:
+        data = np.ones(len(rows), np.float32)
+    return io.CSRMatrix(n_rows, n_cols, np.asarray(data, np.float32), np.asarray(cols).astype(np.uint32), indptr)
+
+
+def record_boundary_coo(rng, n, hotc, cold_cols=None, empty_every=0):
+    """Row r holds r % 17 of the `hotc` hot columns (0, 1, 7, 8, 14, 15 among the counts: an empty, a padded, an exactly full
+    record of the row-packed hot stream, one over) and three cold ones drawn from `cold_cols` (default: every other column);
+    every `empty_every`-th row stays empty."""
+    if cold_cols is None:
+        cold_cols = hotc + np.arange(n - hotc)
+    rows, cols = [], []
+    for r in range(n):
+        if empty_every and r % empty_every == 0:
+            continue
+        k = r % 17
+        hot = (np.arange(k) * 5 + r) % hotc                      # k distinct hot columns (5 is coprime to 64)
+        cold = cold_cols[rng.choice(len(cold_cols), size=3, replace=False)]
+        c = np.unique(np.concatenate([hot, cold]))
+        rows.append(np.full(c.shape[0], r))
+        cols.append(c)
+    return np.concatenate(rows), np.concatenate(cols)
+
+
+def hub_rows_coo(rng, n, dense_rows, others=3, from_cols=None):
+    """`dense_rows` hold n / 2 entries each (hub rows: the 16 private LDS slots), every other row `others` (0: none)."""
+    if from_cols is None:
+        from_cols = np.arange(n)
+    rows, cols = [], []
+    for r in range(n):
+        k = n // 2 if r in dense_rows else others
+        if k == 0:
+            continue
+        rows.append(np.full(k, r))
+        cols.append(np.sort(from_cols[rng.choice(len(from_cols), size=k, replace=False)]))
+    return np.concatenate(rows), np.concatenate(cols)
+
+
+EDGE_HOT = 64                    # hot columns of edge_matrix (the tests set the planner's table to this size)
+EDGE_HUBS = (7, 1000, 4095)
+EDGE_KINDS = ("general", "pattern", "pattern_diag")
+
+
+def edge_matrix(kind, n=4096):
+    """One small matrix that reaches every structure of the general / pattern layouts: 64 hot columns with r % 17 hot entries
+    in row r next to 3 cold ones, the hub rows EDGE_HUBS of n / 2 entries, every 97th row empty, column n - 2 empty, column
+    n - 1 in every 64th row (from row 5 on) and a diagonal entry in every third row.  `kind`: `general` per-entry values, `pattern`
+    column-constant ones, `pattern_diag` column-constant ones with a differing diagonal that is negative on half of its
+    rows; all signed (signed_inputs replaces them by the other value kinds on the same structure)."""
+    assert kind in EDGE_KINDS
+    rng = np.random.default_rng(97)
+    usable = np.arange(EDGE_HOT, n - 2)                      # cold columns: neither n - 2 (stays empty) nor n - 1
+    r0, c0 = record_boundary_coo(rng, n, EDGE_HOT, cold_cols=usable, empty_every=97)
+    r1, c1 = hub_rows_coo(rng, n, EDGE_HUBS, others=0, from_cols=np.delete(np.arange(n), n - 2))
+    last = np.arange(5, n, 64)
+    last = last[last % 97 != 0]
+    diag = np.arange(0, n, 3)
+    diag = diag[(diag % 97 != 0) & (diag != n - 2)]
+    key = np.unique(np.concatenate([r0 * n + c0, r1 * n + c1, last * n + (n - 1), diag * n + diag]).astype(np.int64))
+    m = csr_from_coo(n, n, key // n, key % n)
+    m.adj_data, _ = signed_inputs(np.random.default_rng(98), m, "signed", layout=kind)
+    return m
+
+
+def wide_matrix():
+    """1024 x 262144 with 4 sorted random columns per row: with spmv_blocks=16 most gaps of the delta-coded cold stream exceed
+    255 columns and are bridged by dummy entries (the smallest shape at which that holds)."""
+    rng = np.random.default_rng(77)
+    rows, cols, deg = 1024, 262144, 4
+    indices = np.sort(rng.integers(0, cols, size=(rows, deg)), axis=1).astype(np.uint32).reshape(-1)
+    return io.CSRMatrix(rows, cols, np.ones(rows * deg, np.float32), indices, np.arange(0, rows * deg + 1, deg, dtype=np.uint32))
+
+
+def edge_poison(m, layout, a):
+    """{column: non-finite x} for edge_matrix with the values `a`: the hot columns 3 and 8 with signs such that a row holding
+    both expects inf - inf = NaN whatever the layout (column-constant values give every such row the same two signs), a cold
+    column, the empty column n - 2 (a NaN there must reach no row), column n - 1, a cold column of a hub row and, for
+    pattern_diag, a column whose diagonal entry is an exception."""
+    n = m.num_cols
+    ip, ix = m.adj_indptr.astype(np.int64), m.adj_indices
+    cold_of = lambda r: int([c for c in ix[ip[r]:ip[r + 1]] if EDGE_HOT <= c < n - 2 and c != r][0])
+    both = [r for r in range(EDGE_HOT, n) if r not in EDGE_HUBS and {3, 8} <= set(ix[ip[r]:ip[r + 1]].tolist())][0]
+    e3, e40 = (ip[both] + list(ix[ip[both]:ip[both + 1]]).index(c) for c in (3, 8))
+    p = {3: np.inf, 8: np.inf * -np.sign(a[e3]) * np.sign(a[e40]), cold_of(1): -np.inf, n - 2: np.nan, n - 1: np.inf,
+         cold_of(EDGE_HUBS[1]): np.nan}
+    if layout == "pattern_diag":
+        p[300] = -np.inf          # row 300 holds a diagonal entry (300 % 3 == 0, 300 % 97 != 0)
+    return p
+
+
+def wide_poison(m, a):
+    """{column: non-finite x} for wide_matrix with the values `a`: the first column of every 16th row, +inf / -inf / NaN in
+    turn, the second column of row 0 with the sign that makes the row inf - inf, and a NaN in a column no row holds."""
+    ix = m.adj_indices
+    p = {}
+    for k, r in enumerate(range(0, m.num_rows, 16)):
+        p[int(ix[4 * r])] = (np.inf, -np.inf, np.nan)[k % 3]
+    p[int(ix[1])] = np.inf * -np.sign(a[0]) * np.sign(a[1])
+    unused = np.setdiff1d(np.arange(1000), ix[:m.nnz])
+    p[int(unused[0])] = np.nan
+    return p
+
+
+def _signs(rng, n):
+    return np.where(rng.integers(0, 2, size=n) > 0, 1.0, -1.0)
+
+
+def signed_inputs(rng, m, kind, layout="general", poison=None):
+    """(adj_data, x) for the CSR m.  Kinds: `signed` a, x uniform in [-1, 1); `cancelling` (general layout) x signed with
+    |x| in [0.5, 2) and a_i = s_i c_r / x[col_i], s_i = +1, -1, ... along the row, c_r in [1, 2): the products are +-c_r up to
+    one rounding; `wide` a, x = +-10^U(-15, 15); `subnormal` |a| in [1e-25, 1e-20], |x| in [1e-20, 1e-18] (log-uniform):
+    every product is subnormal or underflows; `poison` = `signed` with x[c] = v for the {c: v} that `poison(a)` returns.
+    layout `pattern`: the values are drawn per column (a = colval[col]); `pattern_diag`: so, and the diagonal entries get
+    values of their own, negative on every second row that holds one."""
+    nnz, nc = m.nnz, m.num_cols
+    ip = m.adj_indptr.astype(np.int64)
+    col = m.adj_indices[:nnz].astype(np.int64)
+    row = np.repeat(np.arange(m.num_rows), np.diff(ip))
+    count = nnz if layout == "general" else nc
+
+    def draw(k, lo, hi):          # +-10^U(lo, hi)
+        return _signs(rng, k) * 10.0 ** rng.uniform(lo, hi, size=k)
+
+    if kind in ("signed", "poison"):
+        a, x = rng.uniform(-1, 1, size=count), rng.uniform(-1, 1, size=nc)
+        dg = lambda k: rng.uniform(0.25, 1, size=k)
+    elif kind == "wide":
+        a, x = draw(count, -15, 15), draw(nc, -15, 15)
+        dg = lambda k: 10.0 ** rng.uniform(-15, 15, size=k)
+    elif kind == "subnormal":
+        a, x = draw(count, -25, -20), draw(nc, -20, -18)
+        dg = lambda k: 10.0 ** rng.uniform(-25, -20, size=k)
+    elif kind == "cancelling":
+        assert layout == "general", "a cancelling row needs per-entry values"
+        x = _signs(rng, nc) * rng.uniform(0.5, 2, size=nc)
+        x = x.astype(np.float32)
+        c_r = rng.uniform(1, 2, size=m.num_rows)
+        sigma = np.where((np.arange(nnz) - ip[row]) % 2 == 0, 1.0, -1.0)
+        a = (sigma * c_r[row]).astype(np.float32) / x[col]
+    else:
+        raise KeyError(kind)
+    a, x = np.asarray(a, np.float32), np.asarray(x, np.float32)
+    if layout != "general":
+        a = a[col]
+        if layout == "pattern_diag":
+            d = np.flatnonzero(col == row)
+            mag = dg(len(d))
+            a = a.copy()
+            a[d] = (mag * np.where(np.arange(len(d)) % 2 == 0, -1.0, 1.0)).astype(np.float32)
+    if kind == "poison":
+        for c, v in poison(a).items():
+            x[c] = v
+    return np.ascontiguousarray(a, np.float32), x
+
+
+# ------------------------------------------------------------------ the (+,x) reference and its derived bounds
+def _arith_rows(row_of, a, xv, num_rows):
+    with np.errstate(all="ignore"):
+        p = np.asarray(a, np.float32) * np.asarray(xv, np.float32)       # the one rounding oracle and device both do
+        p64 = p.astype(np.float64)
+        exact = np.bincount(row_of, weights=p64, minlength=num_rows)     # inf / NaN propagate, inf + -inf = NaN
+        abs_sum = np.bincount(row_of, weights=np.where(np.isfinite(p64), np.abs(p64), 0.0), minlength=num_rows)
+    lens = np.bincount(row_of, minlength=num_rows)
+    return exact, abs_sum, lens
+
+
+def arith_expected(m, x):
+    """The (+,x) product of the CSR m: p = f32(a) * f32(x[col]) in float32 (numpy keeps subnormals), exact[r] = sum p in
+    float64, abs_sum[r] = sum |p| over the finite p, lens[r] -> (exact, abs_sum, lens)."""
+    n = m.nnz
+    row_of = np.repeat(np.arange(m.num_rows), np.diff(m.adj_indptr.astype(np.int64)))
+    return _arith_rows(row_of, m.adj_data[:n], np.asarray(x, np.float32)[m.adj_indices[:n]], m.num_rows)
+
+
+def arith_expected_frontier(csc, v):
+    """arith_expected of the product restricted to the columns the sparse vector v names (columns off the frontier are never
+    read, whatever they hold; a column named twice is applied twice)."""
+    cnt = int(v["index"][0])
+    cols, xv = v["index"][1:cnt + 1].astype(np.int64), v["val"][1:cnt + 1]
+    ip = csc.adj_indptr.astype(np.int64)
+    lens = ip[cols + 1] - ip[cols]
+    pos = np.repeat(ip[cols] - np.concatenate([[0], np.cumsum(lens)[:-1]]), lens) + np.arange(int(lens.sum()))
+    return _arith_rows(csc.adj_indices[pos].astype(np.int64), csc.adj_data[pos], np.repeat(xv, lens), csc.num_rows)
+
+
+def _assert_arith(got, exp, bound, lens, keep, what):
+    got = np.asarray(got, np.float64)
+    assert got.shape == exp.shape, "%s: shape %s vs %s" % (what, got.shape, exp.shape)
+    if keep is None:
+        keep = np.ones(got.shape[0], bool)
+    off = ~keep
+    if np.any(got[off] != 0) or np.any(np.isnan(got[off])):
+        raise AssertionError("%s: masked-off rows must be the literal 0" % what)
+    nan, inf = np.isnan(exp) & keep, np.isinf(exp) & keep
+    fin = keep & ~nan & ~inf
+    with np.errstate(all="ignore"):
+        bad = (nan & ~np.isnan(got)) | (inf & (got != exp)) | (fin & ~(np.abs(got - exp) <= bound))
+    bad = np.flatnonzero(bad)
+    if bad.size:
+        i = bad[0]
+        raise AssertionError("%s: %d rows wrong, first row %d (len %d): got %r expected %r bound %r" %
+                             (what, bad.size, i, lens[i], got[i], exp[i], bound[i]))
+
+
+def assert_arith_signed(got, exp, abs_sum, lens, split, keep=None, what=""):
+    """Every row of a (+,x) SpMV result against arith_expected.  Masked-off rows are the literal 0, rows that expect NaN hold
+    a NaN, rows that expect +-inf hold it, every other row is within
+        u |exp| + (u if split) abs_sum + lens 2^-52 abs_sum + 2^-149,   u = 2^-24:
+    the device sum is an f64 sum of the same f32 products in some order (lens 2^-52 abs_sum covers its rounding and that of
+    the expectation) rounded once to f32; split plans round each segment's partial sum to f32 first (at most abs_sum large)
+    and add the planes in f64.  2^-149: the rounding of a subnormal result.  Derived, not measured."""
+    with np.errstate(all="ignore"):
+        bound = U32 * np.abs(exp) + (U32 if split else 0.0) * abs_sum + lens * 2.0 ** -52 * abs_sum + 2.0 ** -149
+    _assert_arith(got, exp, bound, lens, keep, what)
+
+
+def assert_arith_scatter(got, exp, abs_sum, lens, keep=None, what=""):
+    """The same with the bound of an f32 sum in any order, lens u abs_sum + u |exp| + 2^-149: the SpMSpV paths (global f32
+    atomics, mixed LDS / global folds) and either side against the fp32 oracle."""
+    with np.errstate(all="ignore"):
+        bound = lens * U32 * abs_sum + U32 * np.abs(exp) + 2.0 ** -149
+    _assert_arith(got, exp, bound, lens, keep, what)
+
+
+def mask_keep(mask_name, mask, ref=0.0):
+    """Rows a mask leaves on (None: all), compared with `ref` (SpMV: 0, SpMSpV: the semiring's zero)."""
+    if MASKS[mask_name] == O.WRITETOZERO:
+        return np.asarray(mask) == np.float32(ref)
+    if MASKS[mask_name] == O.WRITETOONE:
+        return np.asarray(mask) != np.float32(ref)
+    return None
+
+
+def stable_seed(*names):
+    """A seed that depends on the case's names only (not on Python's per-process string hashing)."""
+    import zlib
+    return zlib.crc32("/".join(str(n) for n in names).encode())
+
+
+def min_plus_inputs(rng, m, zero, layout="general"):
+    """(adj_data, x) for (min,+): weights are signed eighths in [-8, 8] with -0.0 and 0.0 among them (per entry, per column, or
+    per column with a differing diagonal); x is finite in [-50, 50], the semiring's zero on half of the columns, +inf on a few
+    and -inf on a few.  No weight is non-finite, so no product is a NaN."""
+    nnz, nc = m.nnz, m.num_cols
+    col = m.adj_indices[:nnz].astype(np.int64)
+    row = np.repeat(np.arange(m.num_rows), np.diff(m.adj_indptr.astype(np.int64)))
+    count = nnz if layout == "general" else nc
+    a = (rng.integers(-64, 65, size=count) / 8.0).astype(np.float32)
+    a[rng.integers(0, count, size=max(count // 16, 2))] = np.float32(-0.0)
+    a[rng.integers(0, count, size=max(count // 16, 2))] = np.float32(0.0)
+    if layout != "general":
+        colval, a = a, a[col]
+        if layout == "pattern_diag":
+            d = np.flatnonzero(col == row)
+            mag = np.abs(colval[col[d]])
+            a[d] = np.where(mag > 7.5, mag - np.float32(0.5), mag + np.float32(0.5)) * np.where(np.arange(len(d)) % 2 == 0, np.float32(-1), np.float32(1))
+    x = rng.uniform(-50, 50, size=nc).astype(np.float32)
+    x[rng.random(nc) < 0.5] = np.float32(zero)
+    x[rng.integers(0, nc, size=max(nc // 100, 3))] = np.inf
+    x[rng.integers(0, nc, size=max(nc // 100, 3))] = -np.inf
+    return np.ascontiguousarray(a, np.float32), x
+
+
+ODD_VALUES = np.array([1.0, 0.0, -0.0, -3.5, np.nan, 2.0, np.inf, -np.inf, 1e-40], np.float32)
+ODD_X = np.array([0.0] * 8 + [1.0, -0.0, np.nan, -2.0, np.inf, -np.inf, 1e-40], np.float32)
+ODD_MASK = np.array([0.0, 0.0, 1.0, 1.0, -0.0, np.nan, -1.0, np.inf, 1e-40], np.float32)
+
+
+def logical_odd_inputs(rng, m, layout="general"):
+    """(adj_data, x, mask) for (||,&&) on floats: explicit zeros, -0.0, NaN, negatives, +-inf and a subnormal in the weights
+    (per entry, or per column: some columns are all NaN, bitwise equal), in x and in the mask."""
+    nnz = m.nnz
+    if layout == "general":
+        a = rng.choice(ODD_VALUES, size=nnz)
+    else:
+        colval = rng.choice(ODD_VALUES, size=m.num_cols)
+        a = colval[m.adj_indices[:nnz].astype(np.int64)]
+    return np.ascontiguousarray(a, np.float32), rng.choice(ODD_X, size=m.num_cols), rng.choice(ODD_MASK, size=m.num_rows)
+
+
+def cancelling_csc(n=4096, frontier=256):
+    """An n x n CSC with 4 entries per column and two sparse vectors over the same `frontier` columns (4 * frontier products:
+    the one-workgroup SpMSpV path).  The frontier columns come in groups of four, A B C D, and every group has two rows
+    of its own: row ra receives w x from A and -w x from B and nothing else -- it cancels to the fill value --, row rb receives
+    u x, -u x and a third product q from C -- it returns to the fill value and is reached again.  w, u, x and q are small
+    dyadic rationals, so these sums are exact in any order.  All other entries are signed random floats in rows outside the
+    ra / rb.  The second vector doubles x on the B columns: nothing cancels any more.
+    -> (csc, v1, v2, ra, rb, q)"""
+    rng = np.random.default_rng(4096)
+    assert frontier % 4 == 0
+    g = frontier // 4
+    rows = np.stack([rng.choice(n, size=4, replace=False) for _ in range(n)])
+    vals = rng.uniform(-1, 1, size=(n, 4)).astype(np.float32)
+    special = rng.choice(n, size=2 * g, replace=False)
+    ra, rb = special[:g], special[g:]
+    plain = np.setdiff1d(np.arange(n), special)
+    fcols = np.sort(rng.choice(n, size=frontier, replace=False))
+    for c in fcols:                                               # frontier columns reach the special rows only on purpose
+        rows[c] = plain[rng.choice(len(plain), size=4, replace=False)]
+    x = np.zeros(n, np.float32)
+    x[fcols] = rng.uniform(-1, 1, size=frontier)
+    q = np.zeros(g, np.float32)
+    for j in range(g):
+        A, B, C = fcols[4 * j], fcols[4 * j + 1], fcols[4 * j + 2]
+        w, u, t = (rng.integers(1, 17, size=3) * rng.choice([-1, 1], size=3) / 8.0).astype(np.float32)
+        x[A] = x[B] = np.float32(rng.integers(1, 9) / 4.0)
+        x[C] = np.float32(-rng.integers(1, 9) / 4.0)
+        rows[A, :2], vals[A, :2] = (ra[j], rb[j]), (w, u)
+        rows[B, :2], vals[B, :2] = (ra[j], rb[j]), (-w, -u)
+        rows[C, 0], vals[C, 0] = rb[j], t
+        q[j] = t * x[C]
+    order = np.argsort(rows, axis=1)
+    rows, vals = np.take_along_axis(rows, order, 1), np.take_along_axis(vals, order, 1)
+    csc = io.CSCMatrix(n, n, vals.reshape(-1), rows.reshape(-1).astype(np.uint32), np.arange(0, 4 * n + 1, 4, dtype=np.uint32))
+    x2 = x.copy()
+    x2[fcols[1::4]] *= 2
+    sv = lambda xs: O.make_sparse_vec(fcols.astype(np.uint32), xs[fcols])
+    return csc, sv(x), sv(x2), ra, rb, q
+
+
+def rmat_signed(kind, layout):
+    """rmat_20K with signed values of `kind` (signed / wide), per entry (`general`) or per column (`pattern`)
+    -> (csr, csc, x): x is dense, a frontier takes its entries."""
+    m = named_matrix("rmat_20K")
+    m.adj_data, x = signed_inputs(np.random.default_rng(stable_seed("rmat", kind, layout)), m, kind, layout=layout)
+    return m, io.csr2csc(m), x
+
+
+def frontier_of(x, idx):
+    idx = np.asarray(idx, np.uint32)
+    return O.make_sparse_vec(idx, np.asarray(x, np.float32)[idx])
+
+
+def checked_sparse_result(mod, zero, num_rows):
+    """A SpMSpV module's result list, checked for this build's documented form -- ascending unique indices, head {nnz, zero},
+    no emitted value equal to zero -- and densified."""
+    from graphlily_amd import module as M
+    res = mod.send_results_device_to_host()
+    nnz = mod.get_results_nnz()
+    assert nnz == int(res["index"][0])
+    idx = res["index"][1:nnz + 1].astype(np.int64)
+    assert np.all(np.diff(idx) > 0), "result indices must be ascending and unique"
+    assert res["val"][0] == np.float32(zero)          # head {nnz, Zero} (kernel_spmspv_impl.h:551-555)
+    assert not np.any(res["val"][1:nnz + 1] == np.float32(zero)), "entries equal to zero must not be emitted"
+    return M.convert_sparse_vec_to_dense_vec(res, num_rows, zero)

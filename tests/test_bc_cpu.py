@@ -178,7 +178,7 @@ def test_library_exports_and_binds_the_entry_point():
     L = capi.lib()
     header = open(os.path.join(ROOT, "include", "graphlily_hip.h")).read()
     assert hasattr(L, "gl_bc_accumulate"), "libgraphlily_hip.so does not export gl_bc_accumulate"
-    assert "gl_bc_accumulate" in capi.EXPORTS and len(capi.EXPORTS) == 112 and len(L.gl_bc_accumulate.argtypes) == 8
+    assert "gl_bc_accumulate" in capi.EXPORTS and len(capi.EXPORTS) == 113 and len(L.gl_bc_accumulate.argtypes) == 8
     assert DECL in header
     assert callable(capi.SpMVPlan.bc_accumulate) and callable(M.SpMVModule.bc_accumulate) and callable(io.simple_pattern)
     assert callable(app.BetweennessCentrality.run) and callable(app.betweenness_by_levels) and callable(app.validate_betweenness)

@@ -132,3 +132,91 @@ def test_pinned_readback(gpu):
     out = capi.pinned_empty(n, np.float32)
     got = buf.read(np.float32, n, out=out)
     assert np.array_equal(got, src) and np.shares_memory(got, out)
+
+
+# ------------------------------------------------------------------ signed zeros, infinities, NaN and subnormals
+_ODD = np.array([-0.0, 0.0, np.inf, -np.inf, np.nan, 1e-40, -1e-45, 1.5, -2.25, 3e38], np.float32)
+
+
+def _same_outside_nan(got, want):
+    """Bit-equal where `want` is not a NaN, a NaN where it is."""
+    nan = np.isnan(want)
+    return np.array_equal(np.isnan(got), nan) and np.array_equal(got.view(np.uint32)[~nan], want.view(np.uint32)[~nan])
+
+
+def _shifted(nbytes, shift):
+    """A device buffer that starts 4 bytes past a 16-byte boundary (shift) or on one."""
+    whole = capi.DeviceBuffer(nbytes + 16)
+    buf = capi.DeviceBuffer(nbytes, ptr=whole.ptr + (4 if shift else 0), keepalive=whole)
+    assert (buf.ptr % 16 != 0) == shift
+    return buf
+
+
+@pytest.mark.parametrize("shift", [False, True], ids=["aligned", "unaligned"])
+@pytest.mark.parametrize("length", [1, 3, 5, 1023, 4099])
+def test_add_scalar_odd_values(gpu, length, shift):
+    """gl_ewise_add on -0.0, +-inf, NaN and subnormals, with val = -1.5, -0.0, inf and NaN: the float4 body and its scalar
+    tail (lengths that are no multiple of 4), and the scalar kernel a pointer off a 16-byte boundary selects."""
+    rng = np.random.default_rng(length)
+    inp = rng.choice(_ODD, size=length)
+    inp[:min(length, _ODD.size)] = _ODD[:min(length, _ODD.size)]
+    d_in, d_out = _shifted(4 * length, shift), _shifted(4 * length, shift)
+    d_in.write(inp)
+    for val in (-1.5, -0.0, np.inf, np.nan):
+        capi.ewise_add(d_in, d_out, length, val)
+        capi.sync()
+        with np.errstate(all="ignore"):
+            want = inp + np.float32(val)
+        assert _same_outside_nan(d_out.read(np.float32, length), want), val
+        assert _same_outside_nan(O.ewise_add(inp, length, val), want), val
+
+
+@pytest.mark.parametrize("mask_type", [M.kMaskWriteToOne, M.kMaskWriteToZero])
+@pytest.mark.parametrize("val", [-0.0, np.nan])
+def test_assign_dense_odd_masks(gpu, mask_type, val):
+    """gl_assign_dense with -0.0 (zero), NaN, a subnormal and -1 (all non-zero) in the mask; val = -0.0 / NaN written bit for bit."""
+    length = 4099
+    rng = np.random.default_rng(17)
+    mask = rng.choice(np.array([0.0, -0.0, np.nan, 1e-40, -1.0, 1.0], np.float32), size=length)
+    inout = rng.choice(_ODD, size=length)
+    d_mask, d_inout = capi.DeviceBuffer.from_host(mask), capi.DeviceBuffer.from_host(inout)
+    capi.assign_dense(d_mask, d_inout, length, val, mask_type)
+    capi.sync()
+    got = d_inout.read(np.float32, length)
+    ref = inout.copy()
+    O.assign_dense(mask_type, mask, ref, length, val)
+    assert np.array_equal(got.view(np.uint32), ref.view(np.uint32))
+    written = (mask == 0) if mask_type == M.kMaskWriteToZero else ~(mask == 0)
+    assert 0.2 < written.mean() < 0.8
+    assert np.all(got.view(np.uint32)[written] == np.float32(val).view(np.uint32))
+    assert np.array_equal(got.view(np.uint32)[~written], inout.view(np.uint32)[~written])
+
+
+def test_assign_sparse_new_frontier_odd_values(gpu):
+    """gl_assign_sparse_new_frontier (keep and relax where inout > candidate) with negatives, -0.0 / 0.0 ties (not greater: not
+    kept), NaN on either side (never greater: not kept) and +-inf; 140 000 unique candidates = more than 128 chunks, so the
+    compaction's second pass over the chunk offsets runs.  The list and inout are the oracle's, bit for bit outside NaN."""
+    n, cnt = 300000, 140000
+    rng = np.random.default_rng(23)
+    alphabet = np.array([-0.0, 0.0, np.nan, np.inf, -np.inf, -3.0, -1.0, 2.0, 5.0, 1e-40], np.float32)
+    inout = rng.choice(alphabet, size=n)
+    idx = np.sort(rng.choice(n, size=cnt, replace=False)).astype(np.uint32)
+    mask = M.make_sparse_vec(idx, rng.choice(alphabet, size=cnt))
+    mod = M.AssignVectorSparseModule(True)
+    mod.set_up_runtime()
+    mod.send_mask_host_to_device(mask)
+    mod.send_inout_host_to_device(inout)
+    mod.run()
+    ref = inout.copy()
+    ref_nf = O.assign_sparse_new_frontier(mask, ref)
+    assert _same_outside_nan(mod.send_inout_device_to_host(), ref)
+    nf = mod.send_new_frontier_device_to_host()
+    k = int(nf["index"][0])
+    assert k == int(ref_nf["index"][0]) and 0.2 * cnt < k < 0.8 * cnt and nf["val"][0] == 0.0
+    assert np.array_equal(nf["index"][1:k + 1], ref_nf["index"][1:]) and not np.isnan(ref_nf["val"]).any()
+    assert np.array_equal(nf["val"][1:k + 1].view(np.uint32), ref_nf["val"][1:].view(np.uint32))
+    # ties and NaN: a candidate -0.0 never replaces 0.0 (nor the reverse), nothing replaces or is replaced by a NaN
+    cand, old, new = mask["val"][1:], inout[idx], ref[idx]
+    tie = (cand == 0) & (old == 0)
+    assert tie.any() and np.array_equal(new.view(np.uint32)[tie], old.view(np.uint32)[tie])
+    assert np.isnan(new[np.isnan(old)]).all() and not np.isnan(new[~np.isnan(old)]).any()

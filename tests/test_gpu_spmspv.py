@@ -12,7 +12,7 @@ import pytest
 from graphlily_amd import datasets, io, module as M
 from oracle import oracle as O
 
-from helpers import MASKS, SEMIRINGS, assert_parity, named_matrix, rand01, to_oracle, set_knob
+from helpers import MASKS, SEMIRINGS, assert_parity, checked_sparse_result, named_matrix, rand01, to_oracle, set_knob
 
 pytestmark = pytest.mark.gpu
 
@@ -38,14 +38,7 @@ def _run(gpu, csc, sem, mask_name, v, mask, shard=None):
     mod.send_mask_host_to_device(mask)
     mod.send_vector_host_to_device(v)
     mod.run()
-    res = mod.send_results_device_to_host()
-    nnz = mod.get_results_nnz()
-    assert nnz == int(res["index"][0])
-    idx = res["index"][1:nnz + 1].astype(np.int64)
-    assert np.all(np.diff(idx) > 0), "result indices must be ascending and unique"
-    assert res["val"][0] == np.float32(zero)          # head {nnz, Zero} (kernel_spmspv_impl.h:551-555)
-    assert not np.any(res["val"][1:nnz + 1] == np.float32(zero)), "entries equal to zero must not be emitted"
-    return M.convert_sparse_vec_to_dense_vec(res, csc.num_rows, zero), mod
+    return checked_sparse_result(mod, zero, csc.num_rows), mod
 
 
 def _case(gpu, csc, sem, mask_name, sparsity, seed=0):

@@ -12,8 +12,8 @@ import pytest
 from graphlily_amd import datasets, io, module as M
 from oracle import oracle as O
 
-from helpers import (MASKS, SEMIRINGS, arith_exact, assert_arith_parity, assert_parity, rand01, set_knob, spmv_prepare,
-                     to_oracle)
+from helpers import (MASKS, SEMIRINGS, arith_exact, assert_arith_parity, assert_parity, csr_from_coo, hub_rows_coo, rand01,
+                     record_boundary_coo, set_knob, spmv_prepare, to_oracle)
 
 pytestmark = pytest.mark.gpu
 
@@ -189,19 +189,10 @@ def test_row_packed_hot_stream_record_boundaries(gpu, monkeypatch, shape):
     from graphlily_amd import capi
     rng = np.random.default_rng(61)
     n, hotc = 4096, 64
-    rows, cols = [], []
-    for r in range(n):
-        k = r % 17
-        hot = (np.arange(k) * 5 + r) % hotc                      # k distinct hot columns (5 is coprime to 64)
-        cold = hotc + rng.choice(n - hotc, size=3, replace=False)
-        c = np.unique(np.concatenate([hot, cold]))
-        rows.append(np.full(c.shape[0], r))
-        cols.append(c)
-    rows, cols = np.concatenate(rows), np.concatenate(cols)
-    indptr = np.zeros(n + 1, np.uint32)
-    np.cumsum(np.bincount(rows, minlength=n), out=indptr[1:])
+    rows, cols = record_boundary_coo(rng, n, hotc)
     data = np.full(rows.shape[0], np.float32(0.5), np.float32)
-    m = io.CSRMatrix(n, n, data, cols.astype(np.uint32), indptr)
+    m = csr_from_coo(n, n, rows, cols, data)
+    indptr = m.adj_indptr
     set_knob(monkeypatch, "spmv_hot", hotc)
     set_knob(monkeypatch, "spmv_blocks", str(shape[0]))
     set_knob(monkeypatch, "spmv_segments", str(shape[1]))
@@ -248,17 +239,9 @@ def test_hub_row_spreading(gpu, kind):
     records of the row-packed stream, private slot by lane)."""
     rng = np.random.default_rng(5)
     n = 4096
-    dense_rows = [7, 1000, 4095]
-    rows, cols = [], []
-    for r in range(n):
-        k = n // 2 if r in dense_rows else 3
-        rows.append(np.full(k, r))
-        cols.append(np.sort(rng.choice(n, size=k, replace=False)))
-    rows, cols = np.concatenate(rows), np.concatenate(cols)
-    indptr = np.zeros(n + 1, np.uint32)
-    np.cumsum(np.bincount(rows, minlength=n), out=indptr[1:])
+    rows, cols = hub_rows_coo(rng, n, [7, 1000, 4095])
     data = rng.random(rows.shape[0], dtype=np.float32) if kind == "general" else np.full(rows.shape[0], np.float32(0.25), np.float32)
-    m = io.CSRMatrix(n, n, data, cols.astype(np.uint32), indptr)
+    m = csr_from_coo(n, n, rows, cols, data)
     x, mask = rng.random(n, dtype=np.float32), rand01(n, 1)
     for sem in ("Arithmetic", "Logical", "Tropical"):
         got = _run_spmv(gpu, m, sem, "NoMask", x, mask)
