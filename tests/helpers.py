@@ -1,4 +1,6 @@
 """Shared helpers for the parity tests (the oracle is the checker, never the thing under test)."""
+import functools
+
 import numpy as np
 
 from graphlily_amd import datasets, io
@@ -469,3 +471,362 @@ def checked_sparse_result(mod, zero, num_rows):
     assert res["val"][0] == np.float32(zero)          # head {nnz, Zero} (kernel_spmspv_impl.h:551-555)
     assert not np.any(res["val"][1:nnz + 1] == np.float32(zero)), "entries equal to zero must not be emitted"
     return M.convert_sparse_vec_to_dense_vec(res, num_rows, zero)
+
+
+# ------------------------------------------------------------------ SpMV plans of edge_matrix / wide_matrix with their structure asserted
+PLAN_EXPORTS = ("entries", "bases", "units", "hub_rows", "hot", "hot_hdr", "present")
+# (row blocks, column segments) through GRAPHLILY_DEBUG: the planner's own choice and a split plan.  The wide matrix keeps 16 row
+# blocks in both (fewer entries per block = wider gaps between a block's sorted columns)
+SPMV_SHAPES = {"edge": {"unsplit": (0, 0), "split": (5, 3)}, "wide": {"unsplit": (16, 1), "split": (16, 3)}}
+
+
+def plan_formatters():
+    from graphlily_amd import capi
+    return (capi.GL_PLAN_HOST_FORMAT, capi.GL_PLAN_DEVICE_FORMAT)
+
+
+def set_plan_knobs(monkeypatch, which, shape, hot=EDGE_HOT):
+    """The planner overrides under which edge_matrix / wide_matrix reach their structures: a hot table of `hot` columns (0: none)
+    and the (row blocks, column segments) of SPMV_SHAPES[which][shape]."""
+    if which == "edge":
+        set_knob(monkeypatch, "spmv_hot", hot)
+        set_knob(monkeypatch, "spmv_hot_floor", 1)      # (the general layout asks 4 entries per row block of a hot column: few rows per block here)
+    blocks, segments = SPMV_SHAPES[which][shape]
+    set_knob(monkeypatch, "spmv_blocks", blocks)
+    set_knob(monkeypatch, "spmv_segments", segments)
+
+
+def spmv_plans(monkeypatch, which, layout, shape, m, flags=None, extra=0, hot=EDGE_HOT):
+    """One plan per formatter flag, with the structure the cases rely on asserted and the formatters' arrays compared
+    -> (plans, split)."""
+    from graphlily_amd import capi
+    if flags is None:
+        flags = plan_formatters()
+    set_plan_knobs(monkeypatch, which, shape, hot)
+    plans = [capi.SpMVPlan(m.num_rows, m.num_cols, m.adj_indptr, m.adj_indices, m.adj_data, flags=f | extra) for f in flags]
+    info = plans[0].info()
+    assert info["layout"] == ("general" if layout == "general" else "pattern")
+    assert (info["segments"] > 1) == (shape == "split")
+    if which == "edge":
+        assert info["hot_columns"] == hot and (info["hot_nnz"] > 0) == (hot > 0) and plans[0].export("hub_rows").size > 0
+    else:
+        assert info["groups"] * 64 > 1.3 * m.nnz          # the stream holds visibly more slots than entries: the dummies
+    for p in plans[1:]:
+        assert p.info()["finite_values"] == info["finite_values"]
+        for name in PLAN_EXPORTS:
+            assert np.array_equal(plans[0].export(name), p.export(name)), name
+    return plans, info["segments"] > 1
+
+
+# ------------------------------------------------------------------ the integer value types: an independent restatement, inputs
+VAL_UNSIGNED, VAL_UFIXED = 1, 2          # GL_VAL_UNSIGNED, GL_VAL_UFIXED_32_8 (graphlily/global.h:62-64)
+VALUE_TYPES = {"unsigned": VAL_UNSIGNED, "ufixed": VAL_UFIXED}
+WORD_MAX = 0xffffffff
+WORD_OPS = {"Arithmetic": 0, "Logical": 1, "Tropical": 2}
+
+
+def word_one(vt):
+    """a && b / a || b: 1 for `unsigned`, 1.0 = 1 << 24 for the fixed point."""
+    return 1 << 24 if vt == VAL_UFIXED else 1
+
+
+def word_zero(vt, op):
+    """The semiring's own zero: 0, 0, UINT_INF / UFIXED_INF = 255.0 (global.h:78-79)."""
+    if op != 2:
+        return 0
+    return WORD_MAX if vt == VAL_UNSIGNED else 255 << 24
+
+
+def word_nonzero_zero(vt, op, ref=None):
+    """A `zero` other than the semiring's: (+,x) a word that saturates (fixed point) or wraps (unsigned) most rows, (||,&&) 2 -- neither
+    0 nor ONE --, (min,+) the median of `ref` (the result under the semiring's zero): about half of the rows come out as it."""
+    if op == 0:
+        return 250 << 24 if vt == VAL_UFIXED else 0xfffffff0
+    if op == 1:
+        return 2
+    return int(np.sort(np.asarray(ref, np.uint32))[len(ref) // 2])
+
+
+def _word_products(a, b, op, vt):
+    """The (x) ALU on uint64 copies of the words (hw/ufixed_pe_fwd.h:27-45 and the assignment to ValT): unsigned wraps; the fixed
+    point rounds a product half up to 24 fraction bits and clamps it, and clamps a sum."""
+    a, b, top = np.asarray(a).astype(np.uint64), np.asarray(b).astype(np.uint64), np.uint64(WORD_MAX)
+    if op == 0:
+        p = a * b                                                    # < 2^64
+        return p & top if vt == VAL_UNSIGNED else np.minimum((p + np.uint64(1 << 23)) >> np.uint64(24), top)
+    if op == 1:
+        return np.where((a != 0) & (b != 0), np.uint64(word_one(vt)), np.uint64(0))
+    s = a + b
+    return s & top if vt == VAL_UNSIGNED else np.minimum(s, top)
+
+
+def _word_rows(row_of, p, num_rows, op, vt, zero):
+    """The (+) ALU folded over every row's products, the accumulator starting at `zero` (spmv_module.h:478-510).  The fixed point's
+    clamped running sum of non-negative terms is min(exact sum, 2^32 - 1); a || b gives ONE as soon as one is applied, so a row
+    without products keeps `zero` itself."""
+    top = np.uint64(WORD_MAX)
+    if op == 0:
+        tot = np.zeros(num_rows, np.uint64)
+        np.add.at(tot, row_of, p)                                    # < 2^64: fewer than 2^32 terms below 2^32
+        tot += np.uint64(zero)
+        return (tot & top if vt == VAL_UNSIGNED else np.minimum(tot, top)).astype(np.uint32)
+    if op == 1:
+        applied = np.bincount(row_of, minlength=num_rows) > 0
+        hit = np.bincount(row_of, weights=(p != 0), minlength=num_rows) > 0
+        return np.where(applied, np.where(hit | (zero != 0), word_one(vt), 0), zero).astype(np.uint32)
+    out = np.full(num_rows, zero, np.uint64)
+    np.minimum.at(out, row_of, p)
+    return out.astype(np.uint32)
+
+
+def words_expected(indptr, indices, data, x, op, vt, zero):
+    """y = zero (+) A (x) x of the CSR in the value type vt, restated from the ALUs with numpy uint64 -- not the oracle."""
+    ip = np.asarray(indptr).astype(np.int64)
+    n, nnz = len(ip) - 1, int(ip[-1] - ip[0])
+    row_of = np.repeat(np.arange(n), np.diff(ip))
+    col = np.asarray(indices)[ip[0]:ip[0] + nnz].astype(np.int64)
+    return _word_rows(row_of, _word_products(np.asarray(data)[ip[0]:ip[0] + nnz], np.asarray(x)[col], op, vt), n, op, vt, zero)
+
+
+def words_expected_frontier(indptr, indices, data, v, num_rows, op, vt, zero):
+    """The frontier form: the CSC's columns that the sparse vector v names, each as often as it is named, applied to a result that
+    starts at `zero` (spmspv_module.h:445-497)."""
+    cnt = int(v["index"][0])
+    cols, xv = v["index"][1:cnt + 1].astype(np.int64), v["val"][1:cnt + 1]
+    ip = np.asarray(indptr).astype(np.int64)
+    lens = ip[cols + 1] - ip[cols]
+    pos = np.repeat(ip[cols] - np.concatenate([[0], np.cumsum(lens)[:-1]]), lens) + np.arange(int(lens.sum()))
+    return _word_rows(np.asarray(indices)[pos].astype(np.int64), _word_products(np.asarray(data)[pos], np.repeat(xv, lens), op, vt),
+                      num_rows, op, vt, zero)
+
+
+def words_mask_spmv(y, mask, mask_type):
+    """SpMV: the mask is compared with 0 and masked-off rows are the literal 0 (spmv_module.h:518-530)."""
+    if mask_type == 0:
+        return y
+    on = (np.asarray(mask) == 0) if mask_type == 1 else (np.asarray(mask) != 0)
+    return np.where(on, y, 0).astype(np.uint32)
+
+
+def words_mask_spmspv(y, mask, mask_type, zero):
+    """SpMSpV: the mask is compared with `zero` and masked-off rows are `zero` (spmspv_module.h:499-516)."""
+    if mask_type == 0:
+        return y
+    on = (np.asarray(mask) == zero) if mask_type == 1 else (np.asarray(mask) != zero)
+    return np.where(on, y, zero).astype(np.uint32)
+
+
+def _draw_words(rng, k, hi):
+    return rng.integers(0, hi, size=k, dtype=np.uint64).astype(np.uint32)
+
+
+def _sprinkle(rng, w, top=True, near_max=False):
+    """The words every type has corners at: 5 % zeros (dropped by &&), 2 % 0x80000000 (a float -0.0, negative as an int), and for
+    (min,+) 3 % 0xfffffff0 (saturates in the fixed point, wraps in unsigned when something is added)."""
+    u = rng.random(w.shape[0])
+    w[u < 0.05] = 0
+    if top:
+        w[(u >= 0.05) & (u < 0.07)] = 0x80000000
+    if near_max:
+        w[(u >= 0.07) & (u < 0.10)] = 0xfffffff0
+    return w
+
+
+def _word_ranges(vt, op, kind):
+    """(matrix words below, x words below).  (+,x) `small`: products below 2^15 -- no row of edge_matrix saturates, the hub rows'
+    sums come out exactly; `large`: products up to 2^31 = 128.0 -- rows of more than about 8 entries saturate.  The other semirings:
+    `frontier` (SpMSpV): products up to 2^30, a row saturates
+    from about 16 columns on.  The other semirings: the fixed point below 8.0 / 120.0, unsigned below 2^20 / 2^28."""
+    if op == 0:
+        return {"small": (1 << 25, 1 << 14), "large": (1 << 25, 1 << 30), "frontier": (1 << 25, 1 << 29)}[kind]
+    return (8 << 24, 120 << 24) if vt == VAL_UFIXED else (1 << 20, 1 << 28)
+
+
+HUB_SMALL_ROW, HUB_CROSSING_ROW, HUB_CROSSING_WORD = 7, 1000, 98304
+
+
+def typed_inputs(rng, m, layout, vt, op, kind=None):
+    """(data words, x words, mask words, zero word) for the CSR m in the value type vt and the semiring op.  Layout `general`: a word
+    per entry; `pattern`: per column; `pattern_diag`: so, with a diagonal word that differs from its column's.  Masks are drawn from
+    {0, 1, 0x80000000}; the corner words of _sprinkle are in the matrix and in x ((+,x) `small` keeps 0x80000000 out of x: times a
+    matrix word it saturates on its own).  (||,&&) and (min,+): x is the semiring's zero on half of the columns.  (+,x) `large` on the general
+    layout of edge_matrix: hub row 7 gets words below 2^12 (it stays unsaturated) and hub row 1000 the constant word 98304, with which
+    its sum is about 1.5 x 2^32 while any column-contiguous half of its entries stays below 2^32."""
+    nnz, nc = m.nnz, m.num_cols
+    ip = m.adj_indptr.astype(np.int64)
+    col = m.adj_indices[:nnz].astype(np.int64)
+    row = np.repeat(np.arange(m.num_rows), np.diff(ip))
+    a_hi, x_hi = _word_ranges(vt, op, kind)
+    zero = word_zero(vt, op)
+    a = _sprinkle(rng, _draw_words(rng, nnz if layout == "general" else nc, a_hi), near_max=op == 2)
+    x = _sprinkle(rng, _draw_words(rng, nc, x_hi), top=not (op == 0 and kind == "small"), near_max=op == 2)
+    if op != 0:
+        x[rng.random(nc) < 0.5] = zero
+    if layout != "general":
+        a = a[col]
+        if layout == "pattern_diag":
+            d = np.flatnonzero(col == row)
+            alt = _sprinkle(rng, _draw_words(rng, len(d), a_hi), near_max=op == 2)
+            a[d] = np.where(alt == a[d], alt ^ np.uint32(1), alt)
+    elif op == 0 and kind == "large" and m.num_rows > HUB_CROSSING_ROW:
+        lo, hi = ip[HUB_SMALL_ROW], ip[HUB_SMALL_ROW + 1]
+        a[lo:hi] = _draw_words(rng, hi - lo, 1 << 12)
+        a[ip[HUB_CROSSING_ROW]:ip[HUB_CROSSING_ROW + 1]] = HUB_CROSSING_WORD
+    mask = rng.choice(np.array([0, 1, 0x80000000], np.uint32), size=m.num_rows)
+    return np.ascontiguousarray(a, np.uint32), x, mask, zero
+
+
+def word_vec(indices, vals):
+    """A sparse vector of value words: [0] = {count, -}, the entries behind it."""
+    v = np.zeros(len(indices) + 1, dtype=O.IDX_WORD)
+    v["index"][0] = len(indices)
+    v["index"][1:] = indices
+    v["val"][1:] = vals
+    return v
+
+
+def frontier_words(rng, vt, op, k, kind=None):
+    """k x words for a frontier (typed_inputs' ranges and corner words; (min,+): none equal to the semiring's zero)."""
+    return _sprinkle(rng, _draw_words(rng, k, _word_ranges(vt, op, kind)[1]), top=not (op == 0 and kind == "small"), near_max=op == 2)
+
+
+def csc_words(rng, nnz, vt, op, kind=None):
+    """A word per stored entry of a CSC (typed_inputs' ranges and corner words)."""
+    return _sprinkle(rng, _draw_words(rng, nnz, _word_ranges(vt, op, kind)[0]), near_max=op == 2)
+
+
+def spmspv_mask_words(rng, num_rows, zero):
+    """SpMSpV compares its mask with `zero`: a third of the rows hold it, a third 7 and a third 0x80000000 (equal to 0 as a float)."""
+    return rng.choice(np.array([zero, 7, 0x80000000], np.uint32), size=num_rows)
+
+
+def _csc_from_keys(n, key):
+    """CSC structure (values 1) of the distinct keys column * n + row."""
+    key = np.unique(np.asarray(key, np.int64))
+    indptr = np.zeros(n + 1, np.uint32)
+    np.cumsum(np.bincount(key // n, minlength=n), out=indptr[1:])
+    return io.CSCMatrix(n, n, np.ones(key.shape[0], np.float32), (key % n).astype(np.uint32), indptr)
+
+
+def long_columns_csc():
+    """16384 x 16384 with 24 columns of 4097 .. 8191 entries (four of 4097: just above the 4096-entry chunk) and nothing else: with all
+    of them in the frontier the columns are shared between workgroups by chunks, and with every column named twice the bins
+    overflow into the dense accumulator -> (csc, the 24 columns)."""
+    rng = np.random.default_rng(17)
+    n = 16384
+    degs = rng.integers(4097, 8192, size=24)
+    degs[:4] = 4097
+    cols = np.sort(rng.choice(n, size=24, replace=False))
+    key = np.concatenate([c * n + rng.choice(n, size=int(d), replace=False) for c, d in zip(cols, degs)])
+    return _csc_from_keys(n, key), cols.astype(np.uint32)
+
+
+def random_csc(n, avg, seed, hub=None):
+    """n x n, 0 .. 2 avg distinct random rows per column; hub = (count, length): that many columns of that length."""
+    rng = np.random.default_rng(seed)
+    col = np.repeat(np.arange(n), rng.integers(0, 2 * avg + 1, size=n))
+    keys = [col * n + rng.integers(0, n, size=col.shape[0])]
+    if hub:
+        keys += [c * n + rng.choice(n, size=hub[1], replace=False) for c in rng.choice(n, size=hub[0], replace=False)]
+    return _csc_from_keys(n, np.concatenate(keys))
+
+
+CONTENDED_N = 131136                 # 2049 row tiles of 64: one more than the SpMSpV bin kernel has counters for
+CONTENDED_ROWS = (0, 1)
+
+
+def contended_csc(n=CONTENDED_N):
+    """n x n with 6 random rows (from row 2 on) per column and the rows 0 and 1 in every 4th column: whatever the frontier, a
+    quarter of its columns meet in these two rows."""
+    rng = np.random.default_rng(n)
+    c = np.repeat(np.arange(n), 6)
+    c4 = np.arange(0, n, 4)
+    return _csc_from_keys(n, np.concatenate([c * n + rng.integers(2, n, size=c.shape[0]), c4 * n, c4 * n + 1]))
+
+
+def contended_words(rng, csc, vt, op):
+    """csc_words for contended_csc; for (+,x), whose x words are below 2^29 (`frontier`), row 0 holds 1.0 -- in the fixed point it
+    saturates from about 16 columns on -- and row 1 holds 2^-14: a few thousand columns leave it far below 2^32."""
+    a = csc_words(rng, csc.nnz, vt, op, "frontier")
+    if op == 0:
+        a[csc.adj_indices == 0] = 1 << 24
+        a[csc.adj_indices == 1] = 1 << 10
+    return a
+
+
+# ---- the SpMSpV cases of the integer value types, shared by tests/test_typed_edges_cpu.py (which proves them on the oracle) and
+# tests/test_gpu_typed_edges.py.  The structures are built once and shared: callers do not write to them.
+long_columns_csc = functools.lru_cache(maxsize=None)(long_columns_csc)
+contended_csc = functools.lru_cache(maxsize=None)(contended_csc)
+random_csc = functools.lru_cache(maxsize=None)(random_csc)
+
+
+@functools.lru_cache(maxsize=None)
+def rmat_sssp_csc():
+    """rmat_20K with SSSP's self edges, padded to a multiple of 128, by columns: no column longer than 12288 entries, so a
+    mid-size vector is cut by entries unless the knob forces the cut by products."""
+    m = named_matrix("rmat_20K")
+    io.sssp_add_self_edges(m)
+    io.util_round_csr_matrix_dim(m, 128, 128)
+    return io.csr2csc(m)
+
+
+@functools.lru_cache(maxsize=None)
+def rmat_csc():
+    return io.csr2csc(named_matrix("rmat_20K"))
+
+
+def spmspv_kind(op):
+    return "frontier" if op == 0 else None
+
+
+def long_columns_case(vt_name, op):
+    """The long-column matrix in words -> (csc, data, [v, v doubled, v], mask, zero): the doubled vector names every column twice,
+    with a second set of x words."""
+    vt = VALUE_TYPES[vt_name]
+    csc, cols = long_columns_csc()
+    rng = np.random.default_rng(stable_seed("long columns", vt_name, op))
+    zero = word_zero(vt, op)
+    data = csc_words(rng, csc.nnz, vt, op, spmspv_kind(op))
+    xv, xv2 = (frontier_words(rng, vt, op, len(cols), spmspv_kind(op)) for _ in range(2))
+    v, v2 = word_vec(cols, xv), word_vec(np.concatenate([cols, cols]), np.concatenate([xv, xv2]))
+    return csc, data, [v, v2, v], spmspv_mask_words(rng, csc.num_rows, zero), zero
+
+
+def contended_case(vt_name, op):
+    """contended_csc in words with frontiers of 300 and 5000 columns -> (csc, data, [v300, v5000], mask, zero)."""
+    vt = VALUE_TYPES[vt_name]
+    csc = contended_csc()
+    rng = np.random.default_rng(stable_seed("contended", vt_name, op))
+    zero = word_zero(vt, op)
+    data = contended_words(rng, csc, vt, op)
+    vs = []
+    for cnt in (300, 5000):
+        cols = np.sort(rng.choice(csc.num_cols, size=cnt, replace=False)).astype(np.uint32)
+        vs.append(word_vec(cols, frontier_words(rng, vt, op, cnt, spmspv_kind(op))))
+    return csc, data, vs, spmspv_mask_words(rng, csc.num_rows, zero), zero
+
+
+def frontier_case(csc, name, vt_name, op, counts):
+    """Any CSC structure in words with frontiers of `counts` random columns -> (data, [v ...], mask, zero)."""
+    vt = VALUE_TYPES[vt_name]
+    rng = np.random.default_rng(stable_seed(name, vt_name, op))
+    zero = word_zero(vt, op)
+    data = csc_words(rng, csc.nnz, vt, op, spmspv_kind(op))
+    vs = []
+    for cnt in counts:
+        cols = np.sort(rng.choice(csc.num_cols, size=cnt, replace=False)).astype(np.uint32)
+        vs.append(word_vec(cols, frontier_words(rng, vt, op, cnt, spmspv_kind(op))))
+    return data, vs, spmspv_mask_words(rng, csc.num_rows, zero), zero
+
+
+def spmv_words_reference(m, a, x, op, vt, zero, mask=None, mask_type=0):
+    """What a typed SpMV run must give, word for word: the oracle's O.spmv_words -- with one documented difference.  The library
+    computes y = zero (+) sum (graphlily_hip.h), so under (||,&&) a row WITHOUT stored entries gives zero || nothing = ONE when
+    `zero` is non-zero, where the reference's loop never applies || to such a row and leaves `zero` itself; the two agree on every
+    other row and for every zero a driver uses (0).  tests/test_typed_edges_cpu.py proves that these rows are the only difference."""
+    ref = O.spmv_words(m.adj_indptr, m.adj_indices, a, x, op, vt, zero, mask if mask_type else None, mask_type)
+    if op == 1 and zero != 0:
+        empty = np.diff(m.adj_indptr.astype(np.int64)) == 0
+        ref = np.where(empty, words_mask_spmv(np.full(m.num_rows, word_one(vt), np.uint32), mask, mask_type), ref).astype(np.uint32)
+    return ref

@@ -12,18 +12,14 @@ import pytest
 from graphlily_amd import capi, io, module as M
 from oracle import oracle as O
 
-from helpers import (EDGE_HOT, EDGE_KINDS, MASKS, SEMIRINGS, arith_expected, arith_expected_frontier, assert_arith_scatter,
+from helpers import (EDGE_KINDS, MASKS, SEMIRINGS, arith_expected, arith_expected_frontier, assert_arith_scatter,
                      assert_arith_signed, cancelling_csc, checked_sparse_result, edge_matrix, edge_poison, frontier_of,
-                     logical_odd_inputs, mask_keep, min_plus_inputs, rand01, rmat_signed, set_knob, signed_inputs, stable_seed,
-                     to_oracle, wide_matrix, wide_poison)
+                     logical_odd_inputs, mask_keep, min_plus_inputs, plan_formatters, rand01, rmat_signed, set_knob, signed_inputs, spmv_plans,
+                     stable_seed, to_oracle, wide_matrix, wide_poison)
 
 pytestmark = pytest.mark.gpu
 
-EXPORTS = ("entries", "bases", "units", "hub_rows", "hot", "hot_hdr", "present")
-FORMATTERS = (capi.GL_PLAN_HOST_FORMAT, capi.GL_PLAN_DEVICE_FORMAT)
-# (row blocks, column segments) through GRAPHLILY_DEBUG: the planner's own choice and a split plan.  The wide matrix keeps 16 row
-# blocks in both (fewer entries per block = wider gaps between a block's sorted columns)
-SHAPES = {"edge": {"unsplit": (0, 0), "split": (5, 3)}, "wide": {"unsplit": (16, 1), "split": (16, 3)}}
+FORMATTERS = plan_formatters()
 EDGE = [("edge", k) for k in EDGE_KINDS]
 
 
@@ -38,28 +34,7 @@ def _with_values(which, layout, data):
     return m
 
 
-def _plans(monkeypatch, which, layout, shape, m, flags=FORMATTERS, extra=0):
-    """One plan per formatter flag, with the structure the cases rely on asserted and the formatters' arrays compared
-    -> (plans, split)."""
-    if which == "edge":
-        set_knob(monkeypatch, "spmv_hot", EDGE_HOT)
-        set_knob(monkeypatch, "spmv_hot_floor", 1)      # (the general layout asks 4 entries per row block of a hot column: few rows per block here)
-    blocks, segments = SHAPES[which][shape]
-    set_knob(monkeypatch, "spmv_blocks", blocks)
-    set_knob(monkeypatch, "spmv_segments", segments)
-    plans = [capi.SpMVPlan(m.num_rows, m.num_cols, m.adj_indptr, m.adj_indices, m.adj_data, flags=f | extra) for f in flags]
-    info = plans[0].info()
-    assert info["layout"] == ("general" if layout == "general" else "pattern")
-    assert (info["segments"] > 1) == (shape == "split")
-    if which == "edge":
-        assert info["hot_columns"] == EDGE_HOT and info["hot_nnz"] > 0 and plans[0].export("hub_rows").size > 0
-    else:
-        assert info["groups"] * 64 > 1.3 * m.nnz          # the stream holds visibly more slots than entries: the dummies
-    for p in plans[1:]:
-        assert p.info()["finite_values"] == info["finite_values"]
-        for name in EXPORTS:
-            assert np.array_equal(plans[0].export(name), p.export(name)), name
-    return plans, info["segments"] > 1
+_plans = spmv_plans      # one plan per formatter flag, the structure asserted, the formatters' arrays compared (helpers.py)
 
 
 def _run_plan(p, x, mask, rows, op, zero, mask_name):

@@ -179,19 +179,30 @@ def test_spmspv_words(gpu, vt_name, sem, mask_name):
 
 @pytest.mark.parametrize("vt_name", list(VT))
 def test_apply_ops_words(gpu, vt_name):
-    vt = VT[vt_name]
+    _apply_ops_words(VT[vt_name], 100000)
+
+
+@pytest.mark.parametrize("n", [1, 5, 1023, 4099])
+@pytest.mark.parametrize("vt_name", list(VT))
+def test_apply_ops_words_short(gpu, vt_name, n):
+    _apply_ops_words(VT[vt_name], n)
+
+
+def _apply_ops_words(vt, n):
+    """The element-wise and assign kernels in words: one element, fewer than a wavefront, one short of and a few past a multiple of
+    the block, and a long vector; the three sparse assigns also with an empty list, which must change nothing."""
     rng = np.random.default_rng(5)
-    n = 100000
     a = rng.integers(0, 1 << 32, size=n, dtype=np.uint64).astype(np.uint32)
     val = 0x40000000
     da, db = capi.DeviceBuffer.from_host(a), capi.DeviceBuffer(4 * n)
     capi.ewise_add_typed(da, db, n, val, vt)
     ref = O.ewise_add_words(vt, a, val)
     assert np.array_equal(db.read(np.uint32, n), ref)
-    if vt == capi.GL_VAL_UFIXED_32_8:
-        assert (ref == 0xffffffff).sum() > n // 8                       # saturated
-    else:
-        assert (ref < a).sum() > n // 8                                 # wrapped
+    if n >= 1000:
+        if vt == capi.GL_VAL_UFIXED_32_8:
+            assert (ref == 0xffffffff).sum() > n // 8                   # saturated
+        else:
+            assert (ref < a).sum() > n // 8                             # wrapped
     mask = rng.integers(0, 3, size=n).astype(np.uint32)
     mask[mask == 2] = 0x80000000
     for mt in (1, 2):
@@ -200,30 +211,34 @@ def test_apply_ops_words(gpu, vt_name):
         capi.assign_dense_typed(dm, di, n, 0xfffffffe, mt, vt)
         O.assign_dense_words(mt, mask, inout, 0xfffffffe)
         assert np.array_equal(di.read(np.uint32, n), inout)
-    # SSSP-mode sparse assign: relax where the stored word is larger (unsigned order, incl. words above 2^31)
-    idx = np.sort(rng.choice(n, size=n // 10, replace=False)).astype(np.uint32)
-    sv = np.zeros(idx.shape[0] + 1, dtype=capi.IDX_WORD)
-    sv["index"][0] = idx.shape[0]
-    sv["index"][1:] = idx
-    sv["val"][1:] = rng.integers(0, 1 << 32, size=idx.shape[0], dtype=np.uint64).astype(np.uint32)
-    inout = a.copy()
-    dsv, di, dn = capi.DeviceBuffer(8 * (n + 1)), capi.DeviceBuffer.from_host(inout), capi.DeviceBuffer(8 * (n + 1))
-    dsv.write(sv)
-    capi.assign_sparse_new_frontier_typed(dsv, di, dn, n, vt)
-    nf_ref = O.assign_sparse_new_frontier_words(sv, inout)
-    nf = dn.read(capi.IDX_WORD, n + 1)
-    k = int(nf["index"][0])
-    assert k == int(nf_ref["index"][0]) and k > n // 40
-    assert np.array_equal(nf[1:k + 1], nf_ref[1:k + 1]) and np.array_equal(di.read(np.uint32, n), inout)
-    # BFS-mode sparse assign and sparse -> dense move words untouched
-    capi.assign_sparse_typed(dsv, di, 0xffffffff, n)
-    inout[idx] = 0xffffffff
-    assert np.array_equal(di.read(np.uint32, n), inout)
-    dd = capi.DeviceBuffer(4 * n)
-    capi.sparse_to_dense_typed(dsv, dd, n, 0xffffffff, n)
-    dense = np.full(n, 0xffffffff, dtype=np.uint32)
-    dense[idx] = sv["val"][1:]
-    assert np.array_equal(dd.read(np.uint32, n), dense)
+    for k in (max(n // 10, 1), 0):
+        # SSSP-mode sparse assign: relax where the stored word is larger (unsigned order, incl. words above 2^31)
+        idx = np.sort(rng.choice(n, size=k, replace=False)).astype(np.uint32)
+        sv = np.zeros(idx.shape[0] + 1, dtype=capi.IDX_WORD)
+        sv["index"][0] = idx.shape[0]
+        sv["index"][1:] = idx
+        sv["val"][1:] = rng.integers(0, 1 << 32, size=idx.shape[0], dtype=np.uint64).astype(np.uint32)
+        inout = a.copy()
+        dsv, di, dn = capi.DeviceBuffer(8 * (n + 1)), capi.DeviceBuffer.from_host(inout), capi.DeviceBuffer(8 * (n + 1))
+        dsv.write(sv)
+        dn.write(np.full(2 * (n + 1), 0xdeadbeef, np.uint32))
+        capi.assign_sparse_new_frontier_typed(dsv, di, dn, n, vt)
+        nf_ref = O.assign_sparse_new_frontier_words(sv, inout)
+        nf = dn.read(capi.IDX_WORD, n + 1)
+        cnt = int(nf["index"][0])
+        assert cnt == int(nf_ref["index"][0]) and (cnt > n // 40 if n >= 1000 and k else cnt <= k)
+        assert np.array_equal(nf[1:cnt + 1], nf_ref[1:cnt + 1]) and np.array_equal(di.read(np.uint32, n), inout)
+        if k == 0:
+            assert np.array_equal(inout, a)
+        # BFS-mode sparse assign and sparse -> dense move words untouched
+        capi.assign_sparse_typed(dsv, di, 0xffffffff, n)
+        inout[idx] = 0xffffffff
+        assert np.array_equal(di.read(np.uint32, n), inout)
+        dd = capi.DeviceBuffer(4 * n)
+        capi.sparse_to_dense_typed(dsv, dd, n, 0xffffffff, n)
+        dense = np.full(n, 0xffffffff, dtype=np.uint32)
+        dense[idx] = sv["val"][1:]
+        assert np.array_equal(dd.read(np.uint32, n), dense)
 
 
 def test_word_conversions_follow_the_value_types():
