@@ -1191,49 +1191,68 @@ class BFS(_GraphApp):
         return result
 
 
-class ConnectedComponents(_GraphApp):
-    """Weakly connected components (an extension: the reference has no such driver).  One SpMVModule with the (||,&&) semiring,
-    so that the plan is the boolean layout, whose plain row copy gl_cc_labels walks: lock-free union-find over
-    the rows, then pointer doubling.  run() labels every vertex with the smallest vertex of its component."""
+class _PatternApp(_GraphApp):
+    """What the single-device drivers of the kernels that walk a boolean plan's plain row copy share (extensions: the reference
+    has no such drivers): one SpMVModule with the (||,&&) semiring, so that the plan is the boolean layout, which keeps that
+    copy; a matrix that _prepare() turns into what the kernel accepts; no row shards, for the reason _no_shards_ gives."""
+    _no_shards_ = ""
 
     def __init__(self, num_channels=M.num_hbm_channels, spmv_out_buf_len=0, vec_buf_len=0, comm=None, backend=None):
-        super().__init__(num_channels, comm, backend)
-        if self.comm.distributed:
-            # (before anything touches the device)
-            raise NotImplementedError("ConnectedComponents: row shards are not supported -- every rank would hold the forest of its own "
-                                      "rows and the forests would have to be merged.  On ONE device gl_cc_hook composes: cc_begin, "
-                                      "cc_hook on every shard's plan, cc_finish (capi.cc_begin / SpMVPlan.cc_hook / capi.cc_finish)")
+        _GraphApp.__init__(self, num_channels, comm, backend)
+        self._refuse_shards()
         self.semiring_ = M.LogicalSemiring
         self.SpMV_ = self.backend.SpMVModule(num_channels, spmv_out_buf_len, vec_buf_len)
         self.SpMV_.set_semiring(self.semiring_)
         self.SpMV_.set_mask_type(M.kNoMask)
         self.add_module(self.SpMV_)
         self.sent_ = False
-        self.num_components_ = self.largest_component_ = None
+
+    def _refuse_shards(self):
+        if self.comm.distributed:                                # (called before anything touches the device)
+            raise NotImplementedError("%s: row shards are not supported -- %s" % (type(self).__name__, self._no_shards_))
+
+    def _require_sent(self):
+        if not self.sent_:
+            raise RuntimeError("%s.run(): send_matrix_host_to_device first" % type(self).__name__)
+
+    def _prepare(self, csr):
+        """-> the matrix to plan, from the padded one (padding vertices have empty rows)"""
+        return csr
 
     def load_and_format_matrix(self, csr_float_npz_path, skip_empty_rows=True):
         csr = self._load(csr_float_npz_path)
-        n_real = csr.num_rows
+        self.n_real_ = csr.num_rows
         self._pad(csr)
-        csr.adj_data = np.ones(csr.nnz, dtype=np.float32)       # every stored entry is an edge, as in BFS (app/bfs.h:90)
+        csr = self._prepare(csr)
         self._shard(csr)
         self.SpMV_.set_row_shard(self.r0_, self.r1_)
         self.SpMV_.load_and_format_matrix(csr, skip_empty_rows)
         self.n_ = self.SpMV_.get_num_rows()
         assert self.n_ == self.SpMV_.get_num_cols()
-        self.n_real_ = n_real
         self.sent_ = False
 
     def send_matrix_host_to_device(self):
         self.SpMV_.send_matrix_host_to_device()
         self.sent_ = True
 
+
+class ConnectedComponents(_PatternApp):
+    """Weakly connected components: gl_cc_labels, lock-free union-find over the rows, then pointer doubling.
+    run() labels every vertex with the smallest vertex of its component."""
+    _no_shards_ = ("every rank would hold the forest of its own rows and the forests would have to be merged.  On ONE device "
+                   "gl_cc_hook composes: cc_begin, cc_hook on every shard's plan, cc_finish (capi.cc_begin / SpMVPlan.cc_hook / "
+                   "capi.cc_finish)")
+    num_components_ = largest_component_ = None
+
+    def _prepare(self, csr):
+        csr.adj_data = np.ones(csr.nnz, dtype=np.float32)       # every stored entry is an edge, as in BFS (app/bfs.h:90)
+        return csr
+
     def run(self):
         """-> uint32[n_]: labels[v] = the smallest vertex joined to v by a chain of stored entries taken in either direction
         (padding vertices are singletons).  Leaves num_components_ (over the n_real_ real vertices) and largest_component_
         (vertices in the largest one)."""
-        if not self.sent_:
-            raise RuntimeError("ConnectedComponents.run(): send_matrix_host_to_device first")
+        self._require_sent()
         B, n = self.backend, self.n_
         out = B.alloc(n + 1, np.float32)      # (32-bit words: vertex numbers, then the component count)
         self.SpMV_.cc_labels(out, B.view(out, n, 1, 4))
@@ -1245,50 +1264,22 @@ class ConnectedComponents(_GraphApp):
         return labels
 
 
-class TriangleCount(_GraphApp):
-    """Triangle counting (an extension: the reference has no such driver).  One SpMVModule with the (||,&&) semiring, so that
-    the plan is the boolean layout, whose plain row copy gl_tc_count walks.  The matrix is read as an undirected
-    simple graph -- duplicates, the diagonal, zero-valued entries and direction are ignored, as in ConnectedComponents -- and
-    oriented by degree on the host (io.triangle_orient), so that every triangle is found exactly once and hub rows are short."""
+class TriangleCount(_PatternApp):
+    """Triangle counting: gl_tc_count.  The matrix is read as an undirected simple graph -- duplicates, the
+    diagonal, zero-valued entries and direction are ignored, as in ConnectedComponents -- and oriented by degree on the host
+    (io.triangle_orient), so that every triangle is found exactly once and hub rows are short."""
+    _no_shards_ = "gl_tc_count reads row u for every column u of a row, so every rank would need the whole oriented matrix"
+    degrees_ = num_triangles_ = triangles_ = num_wedges_ = transitivity_ = None
 
-    def __init__(self, num_channels=M.num_hbm_channels, spmv_out_buf_len=0, vec_buf_len=0, comm=None, backend=None):
-        super().__init__(num_channels, comm, backend)
-        if self.comm.distributed:
-            # (before anything touches the device)
-            raise NotImplementedError("TriangleCount: row shards are not supported -- gl_tc_count reads row u for every column u "
-                                      "of a row, so every rank would need the whole oriented matrix")
-        self.semiring_ = M.LogicalSemiring
-        self.SpMV_ = self.backend.SpMVModule(num_channels, spmv_out_buf_len, vec_buf_len)
-        self.SpMV_.set_semiring(self.semiring_)
-        self.SpMV_.set_mask_type(M.kNoMask)
-        self.add_module(self.SpMV_)
-        self.sent_ = False
-        self.degrees_ = None
-        self.num_triangles_ = self.triangles_ = self.num_wedges_ = self.transitivity_ = None
-
-    def load_and_format_matrix(self, csr_float_npz_path, skip_empty_rows=True):
-        csr = self._load(csr_float_npz_path)
-        n_real = csr.num_rows
-        self._pad(csr)
-        csr, self.degrees_ = io.triangle_orient(csr)            # (after padding: padding vertices have empty rows)
-        self._shard(csr)
-        self.SpMV_.set_row_shard(self.r0_, self.r1_)
-        self.SpMV_.load_and_format_matrix(csr, skip_empty_rows)
-        self.n_ = self.SpMV_.get_num_rows()
-        assert self.n_ == self.SpMV_.get_num_cols()
-        self.n_real_ = n_real
-        self.sent_ = False
-
-    def send_matrix_host_to_device(self):
-        self.SpMV_.send_matrix_host_to_device()
-        self.sent_ = True
+    def _prepare(self, csr):
+        csr, self.degrees_ = io.triangle_orient(csr)
+        return csr
 
     def run(self, per_vertex=True):
         """-> uint64[n_]: triangles[v] = triangles through v (padding vertices: 0); with per_vertex=False -> the number of
         triangles as an int (a kernel without the per-vertex bookkeeping).  Leaves num_triangles_, triangles_ (None for a
         total-only run), num_wedges_ = sum of deg (deg - 1) / 2 and transitivity_ = 3 triangles / wedges (0.0 without wedges)."""
-        if not self.sent_:
-            raise RuntimeError("TriangleCount.run(): send_matrix_host_to_device first")
+        self._require_sent()
         B, n = self.backend, self.n_
         words = n + 1 if per_vertex else 1
         out = B.alloc(2 * words, np.float32)      # (64-bit words: the total, then the per-vertex counts)
@@ -1314,51 +1305,23 @@ class TriangleCount(_GraphApp):
         return out
 
 
-class KCore(_GraphApp):
-    """k-core decomposition (an extension: the reference has no such driver).  One SpMVModule with the (||,&&) semiring, so that
-    the plan is the boolean layout, whose plain row copy gl_kcore peels.  The matrix is read as an undirected
-    simple graph -- duplicates, the diagonal, zero-valued entries and direction are ignored, as in TriangleCount -- and stored
-    in both directions by the host (io.symmetrize_simple): peeling v must reach every neighbour of v through row v."""
+class KCore(_PatternApp):
+    """k-core decomposition: gl_kcore.  The matrix is read as an undirected simple graph -- duplicates, the
+    diagonal, zero-valued entries and direction are ignored, as in TriangleCount -- and stored in both directions by the host
+    (io.symmetrize_simple): peeling v must reach every neighbour of v through row v."""
+    _no_shards_ = "gl_kcore reads row u for every column u of a row, so every rank would need the whole symmetric matrix"
+    degrees_ = core_ = order_ = degeneracy_ = levels_ = sub_rounds_ = launches_ = core_sizes_ = None
 
-    def __init__(self, num_channels=M.num_hbm_channels, spmv_out_buf_len=0, vec_buf_len=0, comm=None, backend=None):
-        super().__init__(num_channels, comm, backend)
-        if self.comm.distributed:
-            # (before anything touches the device)
-            raise NotImplementedError("KCore: row shards are not supported -- gl_kcore reads row u for every column u of a row, "
-                                      "so every rank would need the whole symmetric matrix")
-        self.semiring_ = M.LogicalSemiring
-        self.SpMV_ = self.backend.SpMVModule(num_channels, spmv_out_buf_len, vec_buf_len)
-        self.SpMV_.set_semiring(self.semiring_)
-        self.SpMV_.set_mask_type(M.kNoMask)
-        self.add_module(self.SpMV_)
-        self.sent_ = False
-        self.degrees_ = None
-        self.core_ = self.order_ = self.degeneracy_ = self.levels_ = self.sub_rounds_ = self.launches_ = self.core_sizes_ = None
-
-    def load_and_format_matrix(self, csr_float_npz_path, skip_empty_rows=True):
-        csr = self._load(csr_float_npz_path)
-        n_real = csr.num_rows
-        self._pad(csr)
-        csr, self.degrees_ = io.symmetrize_simple(csr)          # (after padding: padding vertices have empty rows)
-        self._shard(csr)
-        self.SpMV_.set_row_shard(self.r0_, self.r1_)
-        self.SpMV_.load_and_format_matrix(csr, skip_empty_rows)
-        self.n_ = self.SpMV_.get_num_rows()
-        assert self.n_ == self.SpMV_.get_num_cols()
-        self.n_real_ = n_real
-        self.sent_ = False
-
-    def send_matrix_host_to_device(self):
-        self.SpMV_.send_matrix_host_to_device()
-        self.sent_ = True
+    def _prepare(self, csr):
+        csr, self.degrees_ = io.symmetrize_simple(csr)
+        return csr
 
     def run(self, order=False):
         """-> uint32[n_]: core[v] = the core number of v (padding vertices: 0).  Leaves core_, degeneracy_ = max core, order_
         (uint32[n_], a degeneracy ordering -- not unique -- or None without order=True), levels_ (levels that peeled a vertex,
         padding vertices included), sub_rounds_, launches_ and core_sizes_[k] = real vertices with core >= k, k = 0 ..
         degeneracy_.  The call waits for the device."""
-        if not self.sent_:
-            raise RuntimeError("KCore.run(): send_matrix_host_to_device first")
+        self._require_sent()
         B, n = self.backend, self.n_
         out = B.alloc(2 * n if order else n, np.float32)          # (32-bit words: the core numbers, then the order)
         stats = self.SpMV_.kcore(B.view(out, 0, n, 4), B.view(out, n, n, 4) if order else None)
@@ -1380,20 +1343,20 @@ class KCore(_GraphApp):
         return mask
 
 
-class BetweennessCentrality(_GraphApp):
+class BetweennessCentrality(_PatternApp):
     """Betweenness centrality (an extension: the reference has no such driver): Brandes' algorithm, one search per source.  The
     search is an app.BFS this object owns, loaded with the simple pattern of the matrix (io.simple_pattern: zero values, the
     diagonal and duplicates dropped, rows ascending); its levels stay on the device, and gl_bc_accumulate
     counts the shortest paths level by level through that BFS's SpMV plan and adds every vertex's dependency, pulled through
     the transposed pattern's plan -- a second boolean SpMVModule, which exists only when the pattern is not symmetric."""
 
+    _no_shards_ = ("gl_bc_accumulate reads the level and the path count of every column of a row, so every rank would need both "
+                   "whole matrices")
+
     def __init__(self, num_channels=M.num_hbm_channels, spmv_out_buf_len=0, spmspv_out_buf_len=0, vec_buf_len=0, comm=None,
                  backend=None):
-        super().__init__(num_channels, comm, backend)
-        if self.comm.distributed:
-            # (before anything touches the device)
-            raise NotImplementedError("BetweennessCentrality: row shards are not supported -- gl_bc_accumulate reads the level and "
-                                      "the path count of every column of a row, so every rank would need both whole matrices")
+        _GraphApp.__init__(self, num_channels, comm, backend)
+        self._refuse_shards()
         self.buf_lens_ = (spmv_out_buf_len, vec_buf_len)
         self.bfs_ = BFS(num_channels, spmv_out_buf_len, spmspv_out_buf_len, vec_buf_len, backend=self.backend)
         self.SpMV_ = self.bfs_.SpMV_
@@ -1448,8 +1411,7 @@ class BetweennessCentrality(_GraphApp):
         Leaves bc_, sources_, depths_ and reached_ (per source: the deepest level, the vertices of level >= 1), orphans_ (0: the
         levels are BFS results), overflowed_ (the sources whose path counts overflowed f64: they contribute nothing, a
         RuntimeWarning names them) and directed_."""
-        if not self.sent_:
-            raise RuntimeError("BetweennessCentrality.run(): send_matrix_host_to_device first")
+        self._require_sent()
         B, n, nr = self.backend, self.n_, self.n_real_
         src = list(range(nr)) if sources is None else [int(s) for s in sources]
         if any(s < 0 or s >= nr for s in src):

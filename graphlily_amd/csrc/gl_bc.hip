@@ -27,7 +27,7 @@
 // waits, no hand-offs between workgroups, no cooperative launch.
 // GATHERS: an edge reads the neighbour's level (4 bytes) and, on a match only, its sigma / coef (8 bytes).  The packed 16-byte
 // record per vertex that DESIGN.md 4.15 names as the alternative is NOT built.
-#include "gl_spmv_plan.h"
+#include "gl_rows.h"
 
 namespace gl {
 
@@ -230,69 +230,23 @@ __global__ __launch_bounds__(256) void bc_sweep_kernel(BcSweepArgs a) {
     }
 }
 
-static unsigned bc_stream_grid(uint32_t n) { return std::max(1u, std::min<unsigned>(cdiv(n, 256u), (unsigned)ctx().num_cus * 8u)); }
-
-// what every plan of the call must be
-static int bc_check_plan(gl_spmv_plan p, const char *who, const char *which) {
-    // (a matrix without entries is planned in the general layout whatever the flags, and keeps no row copy: an empty graph)
-    if (p->nnz != 0 && (!p->d_csr_indptr || !p->d_csr_indices))
-        return set_error(GL_ERR_UNSUPPORTED, "%s: %s keeps no row copy (a GL_PLAN_BOOLEAN plan in the (||,&&) layout does)", who, which);
-    if (p->num_rows != p->num_cols)
-        return set_error(GL_ERR_UNSUPPORTED, "%s: %s: rows and columns name the same vertices: needs num_rows == num_cols (%u x %u)", who,
-                         which, p->num_rows, p->num_cols);
-    if (p->row_begin != 0u || p->row_end != p->num_rows)
-        return set_error(GL_ERR_UNSUPPORTED, "%s: %s is a row shard [%u, %u) of %u rows: row u must be readable for every column u", who,
-                         which, p->row_begin, p->row_end, p->num_rows);
-    if (p->nnz > 0xffffffffull)
-        return set_error(GL_ERR_UNSUPPORTED, "%s: %s: %llu entries do not fit 32-bit offsets", who, which, (unsigned long long)p->nnz);
-    if (p->nnz == 0) return GL_OK;
-    int rc = tc_check_rows(p, who);
-    if (rc != GL_OK) return rc;
-    if (p->tc_rows_ok == 0)
-        return set_error(GL_ERR_UNSUPPORTED, "%s: the rows of %s must be strictly ascending sets of columns below num_cols (no duplicate, "
-                         "no zero-valued entry, which the row copy stores as column 0xffffffff): io.simple_pattern prepares such a matrix", who, which);
-    return GL_OK;
-}
-
 // the refusals, the verdicts and plan_in's scratch, on first use
 static int bc_prepare(gl_spmv_plan pin, gl_spmv_plan pout, const char *who) {
-    int rc = bc_check_plan(pin, who, "plan_in");
+    const char *hint = "io.simple_pattern";
+    int rc = rows_require(pin, pout == pin ? kRowsSymmetric : kRowsSets, who, "plan_in", hint);
+    if (rc == GL_OK && pout != pin) rc = rows_require(pout, kRowsSets, who, "plan_out", hint);
     if (rc != GL_OK) return rc;
-    if (pout != pin) {
-        rc = bc_check_plan(pout, who, "plan_out");
-        if (rc != GL_OK) return rc;
-        if (pout->num_rows != pin->num_rows)
-            return set_error(GL_ERR_UNSUPPORTED, "%s: plan_out is not the transpose of plan_in: %u and %u vertices", who, pout->num_rows, pin->num_rows);
-    }
-    const uint32_t n = pin->num_rows;
-    if (!pin->d_bc_scratch) {
-        const size_t bytes = bc_scratch_bytes(n);
-        hipError_t e = hipMalloc((void **)&pin->d_bc_scratch, bytes);
-        if (e != hipSuccess) return set_error(GL_ERR_HIP, "%s: hipMalloc(%zu bytes of queue, offsets, sigma and coef): %s", who, bytes, hipGetErrorString(e));
-    }
-    uint32_t *word = reinterpret_cast<uint32_t *>(pin->d_bc_scratch);
-    if (pout == pin) {
-        if (pin->nnz != 0 && pin->kcore_symmetric < 0) {
-            uint32_t h = 1;
-            rc = kcore_check_transpose(pin, pin, word, &h);
-            if (rc != GL_OK) return rc;
-            pin->kcore_symmetric = h == 0u ? 1 : 0;
-        }
-        if (pin->nnz != 0 && pin->kcore_symmetric == 0)
-            return set_error(GL_ERR_UNSUPPORTED, "%s: plan_out == plan_in, but the pattern is not symmetric (an entry (v, u) without (u, v)): "
-                             "pass the transposed pattern's plan as plan_out (io.simple_pattern prepares both)", who);
-        return GL_OK;
-    }
+    if (pout->num_rows != pin->num_rows)
+        return set_error(GL_ERR_UNSUPPORTED, "%s: plan_out is not the transpose of plan_in: %u and %u vertices", who, pout->num_rows, pin->num_rows);
+    rc = plan_scratch(pin->d_bc_scratch, bc_scratch_bytes(pin->num_rows), who, "queue, offsets, sigma and coef");
+    if (rc != GL_OK || pout == pin) return rc;
     if (pin->bc_partner != pout || pin->bc_partner_uid != pout->uid) {
         // every entry (v, u) of plan_in is an entry (u, v) of plan_out, and there are as many: the rows are sets, so that is a bijection
-        uint32_t h = pin->nnz == pout->nnz ? 0u : 1u;
-        if (h == 0u && pin->nnz != 0) {
-            rc = kcore_check_transpose(pin, pout, word, &h);
-            if (rc != GL_OK) return rc;
-        }
+        bool ok = pin->nnz == pout->nnz;
+        if (ok && pin->nnz != 0 && (rc = rows_check_transpose(pin, pout, &ok)) != GL_OK) return rc;
         pin->bc_partner = pout;
         pin->bc_partner_uid = pout->uid;
-        pin->bc_transpose_ok = h == 0u ? 1 : 0;
+        pin->bc_transpose_ok = ok ? 1 : 0;
     }
     if (pin->bc_transpose_ok == 0)
         return set_error(GL_ERR_UNSUPPORTED, "%s: plan_out is not the transpose of plan_in (%llu and %llu entries; an entry (v, u) of plan_in "
@@ -330,7 +284,7 @@ static int bc_accumulate(gl_spmv_plan pin, gl_spmv_plan pout, const float *d_lev
     // (ctl and both offset arrays are one stretch: zeroed together)
     GL_HIP(hipMemsetAsync(sc.ctl, 0, kBcCtlBytes + 8u * ((size_t)n + 2u), s));
     if (!accumulate) GL_HIP(hipMemsetAsync(d_bc, 0, 8u * (size_t)n, s));
-    const unsigned stream_grid = bc_stream_grid(n);
+    const unsigned stream_grid = rows_stream_grid(n);
     bc_hist_kernel<<<stream_grid, 256, 0, s>>>(d_level, n, sc.cursor, sc.ctl, sigma);
     bc_scan_kernel<<<1, 1024, 0, s>>>(sc.cursor, sc.off, sc.ctl);
     bc_scatter_kernel<<<stream_grid, 256, 0, s>>>(d_level, n, sc.cursor, sc.queue);

@@ -10,13 +10,13 @@
 //   * 64 rows per wavefront, a thread per row, four entries per step (the bottom-up scan's shape, gl_spmspv.hip); a row still
 //     undecided after `cut` entries is finished by the whole wavefront, 256 entries per step with coalesced index loads and
 //     one butterfly min per row -- the stand-ins have rows of 1e5 entries;
-//   * where every row's columns ascend (established once per plan by parents_sorted_kernel, cached in the plan) the first
+//   * where every row's columns ascend (established once per plan, gl_rows.h: rows_sorted) the first
 //     match is the minimum and the scan stops there; otherwise every entry is read;
 //   * the levels are gathered from a one-byte copy (3 MB instead of 12 MB for 3 M vertices: it stays in the L2) that a
 //     streaming pass packs first; a level array that does not fit a byte (>= 255, or not a whole number) raises a device flag
 //     and the same launch gathers the floats instead -- no host decision, no synchronisation;
 //   * entries with column 0xffffffff (zero-valued) are never parents.
-#include "gl_spmv_plan.h"
+#include "gl_rows.h"
 
 #include <type_traits>
 
@@ -66,24 +66,6 @@ __global__ __launch_bounds__(256) void parents_pack_levels_kernel(const float *_
         out[i] = (unsigned char)b;
     }
     if (__any(bad) && (threadIdx.x & 63u) == 0) atomicOr(overflow, 1u);
-}
-
-// do the valid (!= 0xffffffff) columns of every row ascend?  a wavefront per row, once per plan
-__global__ __launch_bounds__(256) void parents_sorted_kernel(const uint32_t *__restrict__ row_ptr, const uint32_t *__restrict__ row_idx,
-                                                             uint32_t rows, uint32_t nz_base, uint32_t *__restrict__ unsorted) {
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    bool bad = false;
-    for (uint32_t r = blockIdx.x * 4u + wave; r < rows; r += gridDim.x * 4u) {
-        const uint32_t beg = row_ptr[r] - nz_base, end = row_ptr[r + 1u] - nz_base;
-        for (uint32_t k = beg + 1u + lane; k < end; k += 64u) {
-            const uint32_t cur = row_idx[k];
-            if (cur == kNoParent) continue;
-            uint32_t j = k - 1u, prev = row_idx[j];
-            while (prev == kNoParent && j > beg) prev = row_idx[--j];
-            bad |= prev != kNoParent && prev > cur;
-        }
-    }
-    if (__any(bad) && lane == 0) atomicOr(unsorted, 1u);
 }
 
 template <typename T, bool SORTED, bool COUNT>
@@ -154,32 +136,11 @@ __global__ __launch_bounds__(256) void bfs_parents_kernel(ParentsArgs a) {
         parents_body<float, SORTED, COUNT>(a, a.dist);
 }
 
-// the plan's scratch (control words + one byte per column) and its rows' sortedness, on first use
+// the refusals, the plan's scratch (control words + one byte per column) and its rows' sortedness, on first use
 static int parents_prepare(gl_spmv_plan p, const char *who) {
-    if (!p->d_csr_indptr || !p->d_csr_indices)
-        return set_error(GL_ERR_UNSUPPORTED, "%s: the plan keeps no row copy (a GL_PLAN_BOOLEAN plan in the (||,&&) layout does)", who);
-    if (p->row_end > p->num_cols)
-        return set_error(GL_ERR_UNSUPPORTED, "%s: the level vector is indexed by row and by column: needs num_rows <= num_cols", who);
-    hipStream_t s = ctx().stream;
-    if (!p->d_parents_scratch) {
-        const size_t bytes = kParentsCtlBytes + (((size_t)p->num_cols + 3u) & ~(size_t)3u);
-        hipError_t e = hipMalloc((void **)&p->d_parents_scratch, bytes);
-        if (e != hipSuccess) return set_error(GL_ERR_HIP, "%s: hipMalloc(%zu bytes of level scratch): %s", who, bytes, hipGetErrorString(e));
-    }
-    if (p->rows_sorted < 0) {
-        const uint32_t rows = p->row_end - p->row_begin;
-        uint32_t *ctl = reinterpret_cast<uint32_t *>(p->d_parents_scratch);
-        GL_HIP(hipMemsetAsync(ctl, 0, kParentsCtlBytes, s));
-        if (rows) {
-            const unsigned grid = std::min<unsigned>((rows + 3u) / 4u, (unsigned)ctx().num_cus * 32u);
-            parents_sorted_kernel<<<grid, 256, 0, s>>>(p->d_csr_indptr, p->d_csr_indices, rows, p->csr_nz_base, ctl + 1);
-            GL_LAUNCH_CHECK();
-        }
-        uint32_t unsorted = 0;
-        GL_HIP(d2h_word_sync(&unsorted, ctl + 1, s));
-        p->rows_sorted = unsorted ? 0 : 1;
-    }
-    return GL_OK;
+    int rc = rows_require(p, kRowsIndexable, who, "the plan");
+    if (rc == GL_OK) rc = plan_scratch(p->d_parents_scratch, kParentsCtlBytes + (((size_t)p->num_cols + 3u) & ~(size_t)3u), who, "level scratch");
+    return rc == GL_OK ? rows_check_sorted(p) : rc;
 }
 
 static int parents_run(gl_spmv_plan p, const float *d_distance, uint32_t *d_parent, uint32_t *d_orphans, bool count, const char *who) {
@@ -249,14 +210,5 @@ int gl_bfs_parents_entries(gl_spmv_plan plan, const float *d_distance, uint32_t 
     const hipError_t w = hipStreamSynchronize(s);
     GL_HIP(e != hipSuccess ? e : w);
     *entries_read = h;
-    return GL_OK;
-}
-
-int gl_spmv_plan_rows_sorted(gl_spmv_plan plan, int *sorted) {
-    GL_REQUIRE_INIT();
-    GL_ARG(plan != nullptr && sorted != nullptr);
-    int rc = gl::parents_prepare(plan, "gl_spmv_plan_rows_sorted");
-    if (rc != GL_OK) return rc;
-    *sorted = plan->rows_sorted;
     return GL_OK;
 }

@@ -33,7 +33,7 @@
 // one ballot and one atomic add per wavefront.  No call synchronises with the host.
 // NO ROW SKIPPING: entries are stored one way only (row v lists the vertices v is pulled from), so a row skipped because its
 // vertex already sits in the giant component (Afforest's shortcut) may hold the only copy of an edge that leaves it.
-#include "gl_spmv_plan.h"
+#include "gl_rows.h"
 
 namespace gl {
 
@@ -159,19 +159,9 @@ __global__ __launch_bounds__(256) void cc_count_kernel(const uint32_t *__restric
     if ((threadIdx.x & 63u) == 0u && roots != 0u) atomicAdd(count, roots);
 }
 
-static unsigned cc_stream_grid(uint32_t n) { return std::max(1u, std::min<unsigned>((n + 255u) / 256u, (unsigned)ctx().num_cus * 8u)); }
-
-static int cc_check_plan(gl_spmv_plan p, const char *who) {
-    if (!p->d_csr_indptr || !p->d_csr_indices)
-        return set_error(GL_ERR_UNSUPPORTED, "%s: the plan keeps no row copy (a GL_PLAN_BOOLEAN plan in the (||,&&) layout does)", who);
-    if (p->row_end > p->num_cols)
-        return set_error(GL_ERR_UNSUPPORTED, "%s: the parent array is indexed by row and by column: needs num_rows <= num_cols", who);
-    return GL_OK;
-}
-
 static int cc_begin(uint32_t *d_parent, uint32_t n) {
     if (!n) return GL_OK;
-    cc_begin_kernel<<<cc_stream_grid(n), 256, 0, ctx().stream>>>(d_parent, n);
+    cc_begin_kernel<<<rows_stream_grid(n), 256, 0, ctx().stream>>>(d_parent, n);
     GL_LAUNCH_CHECK();
     return GL_OK;
 }
@@ -204,16 +194,14 @@ static int cc_finish(uint32_t *d_parent, uint32_t n, uint32_t *d_labels, uint32_
     if (d_count) GL_HIP(hipMemsetAsync(d_count, 0, 4, s));
     if (!n) return GL_OK;
     uint32_t *&ctl = ctx().cc_ctl;
-    if (!ctl) {
-        hipError_t e = hipMalloc((void **)&ctl, kCcCtlBytes);
-        if (e != hipSuccess) return set_error(GL_ERR_HIP, "%s: hipMalloc(%u bytes of control words): %s", who, kCcCtlBytes, hipGetErrorString(e));
-    }
+    const int rc = plan_scratch(ctl, kCcCtlBytes, who, "control words");
+    if (rc != GL_OK) return rc;
     GL_HIP(hipMemsetAsync(ctl, 0, kCcCtlBytes, s));
     uint32_t rounds = 1;                      // ceil(log2 n) + 1 ...
     while ((1ull << (rounds - 1u)) < n) rounds++;
     rounds |= 1u;                             // ... made odd: the last round writes d_labels
     static_assert(kCcMaxRounds * 4u <= kCcCtlBytes && kCcMaxRounds >= 33u, "one word per round");
-    const unsigned grid = cc_stream_grid(n);
+    const unsigned grid = rows_stream_grid(n);
     uint32_t *in = d_parent, *out = d_labels;
     for (uint32_t r = 0; r < rounds; r++) {
         cc_jump_kernel<<<grid, 256, 0, s>>>(in, out, n, ctl, r);
@@ -240,7 +228,7 @@ int gl_cc_hook(gl_spmv_plan plan, uint32_t *d_parent) {
     GL_TRACE();
     GL_REQUIRE_INIT();
     GL_ARG(plan != nullptr && d_parent != nullptr);
-    int rc = gl::cc_check_plan(plan, "gl_cc_hook");
+    int rc = gl::rows_require(plan, gl::kRowsIndexable, "gl_cc_hook", "the plan");
     if (rc != GL_OK) return rc;
     return gl::cc_hook(plan, d_parent);
 }
@@ -257,14 +245,10 @@ int gl_cc_labels(gl_spmv_plan plan, uint32_t *d_labels, uint32_t *d_count) {
     GL_TRACE();
     GL_REQUIRE_INIT();
     GL_ARG(plan != nullptr && d_labels != nullptr);
-    int rc = gl::cc_check_plan(plan, "gl_cc_labels");
+    int rc = gl::rows_require(plan, gl::kRowsIndexable, "gl_cc_labels", "the plan");
     if (rc != GL_OK) return rc;
     const uint32_t n = plan->num_cols;
-    if (!plan->d_cc_scratch) {
-        const size_t bytes = 4u * (size_t)std::max(n, 4u);
-        hipError_t e = hipMalloc((void **)&plan->d_cc_scratch, bytes);
-        if (e != hipSuccess) return gl::set_error(GL_ERR_HIP, "gl_cc_labels: hipMalloc(%zu bytes of parent scratch): %s", bytes, hipGetErrorString(e));
-    }
+    if ((rc = gl::plan_scratch(plan->d_cc_scratch, 4u * (size_t)std::max(n, 4u), "gl_cc_labels", "parent scratch")) != GL_OK) return rc;
     if ((rc = gl::cc_begin(plan->d_cc_scratch, n)) != GL_OK) return rc;
     if ((rc = gl::cc_hook(plan, plan->d_cc_scratch)) != GL_OK) return rc;
     return gl::cc_finish(plan->d_cc_scratch, n, d_labels, d_count, "gl_cc_labels");

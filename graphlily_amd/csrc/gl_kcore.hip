@@ -31,7 +31,7 @@
 // returns at once and vice versa, everything returns once the phase is "done" -- so the host enqueues (scan, peel, turn) x
 // kcore_batch blindly, of which exactly one of scan / peel runs per triple, copies the record to page-locked memory and waits
 // ONCE per batch.  The result does not depend on kcore_batch.  At most n sub-rounds and n + 1 levels exist, so the loop is capped.
-#include "gl_spmv_plan.h"
+#include "gl_rows.h"
 
 namespace gl {
 
@@ -51,38 +51,6 @@ __device__ __forceinline__ uint32_t kc_sub(uint32_t *p, uint32_t v) {
     return __hip_atomic_fetch_sub((kc_gu32 *)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// position of the first entry >= w in the ascending s[0 .. n), n >= 1; the result is < n
-__device__ __forceinline__ uint32_t kc_lower_bound(const uint32_t *s, uint32_t n, uint32_t w) {
-    uint32_t lo = 0;
-    while (n > 1u) {
-        const uint32_t half = n >> 1;
-        lo += s[lo + half - 1u] < w ? half : 0u;
-        n -= half;
-    }
-    return lo;
-}
-
-// the plan's first call, behind the row check (every column is < n): is (u, v) stored for every (v, u)?  A wavefront per row.
-// (u, v) is looked up in the PARTNER's rows: the plan's own for the symmetry verdict, another plan's for gl_bc_accumulate's
-// "is plan_out the transpose" (gl_bc.hip), which also looks the diagonal entries up.
-__global__ __launch_bounds__(256) void kcore_symmetric_kernel(const uint32_t *__restrict__ row_ptr, const uint32_t *__restrict__ row_idx,
-                                                              uint32_t n, uint32_t nz_base, const uint32_t *__restrict__ prow_ptr,
-                                                              const uint32_t *__restrict__ prow_idx, uint32_t pnz_base, bool self,
-                                                              uint32_t *__restrict__ verdict) {
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    bool bad = false;
-    for (uint64_t v = blockIdx.x * 4u + wave; v < n; v += gridDim.x * 4u) {
-        const uint32_t b = row_ptr[v] - nz_base, e = row_ptr[v + 1u] - nz_base;
-        for (uint64_t j = (uint64_t)b + lane; j < e; j += 64u) {
-            const uint32_t u = row_idx[j];
-            if (self && u == (uint32_t)v) continue;
-            const uint32_t ub = prow_ptr[u] - pnz_base, lu = prow_ptr[u + 1u] - pnz_base - ub;
-            bad |= lu == 0u || prow_idx[ub + kc_lower_bound(prow_idx + ub, lu, (uint32_t)v)] != (uint32_t)v;
-        }
-    }
-    if (bad) atomicOr(verdict, 1u);
-}
-
 // deg[v] = entries of row v other than v itself (the rows are sets of columns < n), the control record of level 0
 __global__ __launch_bounds__(256) void kcore_init_kernel(const uint32_t *__restrict__ row_ptr, const uint32_t *__restrict__ row_idx,
                                                          uint32_t n, uint32_t nz_base, uint32_t *__restrict__ deg, uint32_t *__restrict__ ctl) {
@@ -90,7 +58,7 @@ __global__ __launch_bounds__(256) void kcore_init_kernel(const uint32_t *__restr
     for (uint64_t v = blockIdx.x * 256u + threadIdx.x; v < n; v += gridDim.x * 256u) {
         const uint32_t b = row_ptr[v] - nz_base, len = row_ptr[v + 1u] - nz_base - b;
         uint32_t d = len;
-        if (len != 0u && row_idx[b + kc_lower_bound(row_idx + b, len, (uint32_t)v)] == (uint32_t)v) d -= 1u;
+        if (len != 0u && row_idx[b + rows_lower_bound(row_idx + b, len, (uint32_t)v)] == (uint32_t)v) d -= 1u;
         deg[v] = d;
     }
 }
@@ -209,57 +177,12 @@ __global__ void kcore_turn_kernel(uint32_t *ctl, uint32_t n) {
     }
 }
 
-int kcore_check_transpose(gl_spmv_plan p, gl_spmv_plan partner, uint32_t *d_word, uint32_t *h_verdict) {
-    hipStream_t s = ctx().stream;
-    const uint32_t n = p->num_rows;
-    *h_verdict = 1;
-    hipError_t e = hipMemsetAsync(d_word, 0, 4, s);
-    if (e == hipSuccess) {
-        const unsigned grid = std::max(1u, std::min<unsigned>(cdiv(n, 4u), (unsigned)ctx().num_cus * 16u));
-        kcore_symmetric_kernel<<<grid, 256, 0, s>>>(p->d_csr_indptr, p->d_csr_indices, n, p->csr_nz_base, partner->d_csr_indptr,
-                                                    partner->d_csr_indices, partner->csr_nz_base, partner == p, d_word);
-        e = hipGetLastError();
-    }
-    GL_HIP(e != hipSuccess ? e : d2h_word_sync(h_verdict, d_word, s));
-    return GL_OK;
-}
-
-static unsigned kcore_stream_grid(uint32_t n) { return std::max(1u, std::min<unsigned>(cdiv(n, 256u), (unsigned)ctx().num_cus * 8u)); }
-
-// the refusals, the plan's two verdicts and its scratch, on first use (one synchronisation)
+// the refusals, the plan's verdicts and its scratch, on first use
 static int kcore_prepare(gl_spmv_plan p, const char *who) {
-    // (a matrix without entries is planned in the general layout whatever the flags, and keeps no row copy: an empty graph)
-    if (p->nnz != 0 && (!p->d_csr_indptr || !p->d_csr_indices))
-        return set_error(GL_ERR_UNSUPPORTED, "%s: the plan keeps no row copy (a GL_PLAN_BOOLEAN plan in the (||,&&) layout does)", who);
-    if (p->num_rows != p->num_cols)
-        return set_error(GL_ERR_UNSUPPORTED, "%s: rows and columns name the same vertices: needs num_rows == num_cols (%u x %u)", who,
-                         p->num_rows, p->num_cols);
-    if (p->row_begin != 0u || p->row_end != p->num_rows)
-        return set_error(GL_ERR_UNSUPPORTED, "%s: a row shard [%u, %u) of %u rows: row u must be readable for every column u", who,
-                         p->row_begin, p->row_end, p->num_rows);
-    if (p->nnz > 0xffffffffull) return set_error(GL_ERR_UNSUPPORTED, "%s: %llu entries do not fit 32-bit offsets", who, (unsigned long long)p->nnz);
-    if (p->nnz == 0) return GL_OK;
-    int rc = tc_check_rows(p, who);
-    if (rc != GL_OK) return rc;
-    if (p->tc_rows_ok == 0)
-        return set_error(GL_ERR_UNSUPPORTED, "%s: the rows must be strictly ascending sets of columns below num_cols (no duplicate, no "
-                         "zero-valued entry, which the row copy stores as column 0xffffffff): io.symmetrize_simple prepares such a matrix", who);
-    const uint32_t n = p->num_rows;
-    if (!p->d_kcore_scratch) {
-        const size_t bytes = kKcCtlBytes + 4u * (size_t)n;       // the control record, then the queue of a call without d_order
-        hipError_t e = hipMalloc((void **)&p->d_kcore_scratch, bytes);
-        if (e != hipSuccess) return set_error(GL_ERR_HIP, "%s: hipMalloc(%zu bytes of control record and queue): %s", who, bytes, hipGetErrorString(e));
-    }
-    if (p->kcore_symmetric < 0) {
-        uint32_t h = 1;
-        rc = kcore_check_transpose(p, p, reinterpret_cast<uint32_t *>(p->d_kcore_scratch), &h);
-        if (rc != GL_OK) return rc;
-        p->kcore_symmetric = h == 0u ? 1 : 0;
-    }
-    if (p->kcore_symmetric == 0)
-        return set_error(GL_ERR_UNSUPPORTED, "%s: the pattern is not symmetric (an entry (v, u) without (u, v)): peeling v must reach u "
-                         "through row v; io.symmetrize_simple prepares such a matrix", who);
-    return GL_OK;
+    const int rc = rows_require(p, kRowsSymmetric, who, "the plan", "io.symmetrize_simple");
+    if (rc != GL_OK || p->nnz == 0) return rc;
+    // the control record, then the queue of a call without d_order
+    return plan_scratch(p->d_kcore_scratch, kKcCtlBytes + 4u * (size_t)p->num_rows, who, "control record and queue");
 }
 
 static int kcore(gl_spmv_plan p, uint32_t *d_core, uint32_t *d_order, uint32_t *h_stats, const char *who) {
@@ -272,7 +195,7 @@ static int kcore(gl_spmv_plan p, uint32_t *d_core, uint32_t *d_order, uint32_t *
     if (p->nnz == 0) {                                            // an empty graph: nobody has a neighbour, any order will do
         GL_HIP(hipMemsetAsync(d_core, 0, 4u * (size_t)n, s));
         if (d_order) {
-            kcore_iota_kernel<<<kcore_stream_grid(n), 256, 0, s>>>(d_order, n);
+            kcore_iota_kernel<<<rows_stream_grid(n), 256, 0, s>>>(d_order, n);
             GL_LAUNCH_CHECK();
         }
         return GL_OK;
@@ -294,7 +217,7 @@ static int kcore(gl_spmv_plan p, uint32_t *d_core, uint32_t *d_order, uint32_t *
     a.n = n;
     a.nz_base = p->csr_nz_base;
     a.cut_steps = (uint32_t)std::max<long>(0, std::min<long>(cut, 1l << 30)) / 4u;
-    const unsigned stream_grid = kcore_stream_grid(n);
+    const unsigned stream_grid = rows_stream_grid(n);
     const unsigned peel_grid = std::max(1u, std::min<unsigned>(cdiv(n, 256u), (unsigned)ctx().num_cus * per_cu));
     uint32_t *&w = ctx().pinned_word;
     if (!w) GL_HIP(hipHostMalloc((void **)&w, 64, hipHostMallocDefault));

@@ -232,28 +232,29 @@ struct gl_spmv_plan_s {
     // d_csr_indices holds the shard's part starting at csr_nz_base)
     uint32_t *d_csr_indptr = nullptr, *d_csr_indices = nullptr;
     uint32_t csr_nz_base = 0;
-    // gl_bfs_parents (gl_bfs_parents.hip), both set up by the first call: do the valid columns of every row of that copy
-    // ascend (-1: not established yet), and the pass's scratch -- 256 bytes of control words + one byte per column
-    int rows_sorted = -1;
+    // what the graph kernels that walk this copy have established about it (gl_rows.h), each by one kernel on first need:
+    // -1 not established yet, 0 no, 1 yes
+    int rows_sorted = -1;      // the valid columns of every row ascend (gl_bfs_parents stops at the first match)
+    int rows_are_sets = -1;    // the rows are strictly ascending sets of columns below num_cols (gl_tc_count, gl_kcore, gl_bc_accumulate)
+    int rows_symmetric = -1;   // ... and hold (u, v) for every (v, u) (gl_kcore; gl_bc_accumulate with plan_out == plan_in)
+    // gl_bfs_parents (gl_bfs_parents.hip): the pass's scratch, allocated by the first call -- 256 bytes of control words + one
+    // byte per column
     unsigned char *d_parents_scratch = nullptr;
     // gl_cc_labels (gl_cc.hip): num_cols words of parent scratch, allocated by the first call
     uint32_t *d_cc_scratch = nullptr;
-    // gl_tc_count (gl_tc.hip), all set up by the first call: are the rows strictly ascending sets of columns below num_cols
-    // (-1: not established yet), and the rows binned by length -- row numbers of the short bin (tc_items[0] rows, the longest of
-    // tc_cap[0] entries rounded up to 4), of the wave bin (tc_items[1], tc_cap[1]) and of the wide bin (tc_items[2], tc_cap[2]),
-    // then tc_items[3] pairs {row, first entry} of the long rows' chunks
-    int tc_rows_ok = -1;
+    // gl_tc_count (gl_tc.hip), set up by the first call: the rows binned by length -- row numbers of the short bin (tc_items[0]
+    // rows, the longest of tc_cap[0] entries rounded up to 4), of the wave bin (tc_items[1], tc_cap[1]) and of the wide bin
+    // (tc_items[2], tc_cap[2]), then tc_items[3] pairs {row, first entry} of the long rows' chunks
     unsigned char *d_tc_scratch = nullptr;
     uint32_t tc_items[4] = {0, 0, 0, 0}, tc_cap[3] = {0, 0, 0};
-    // gl_kcore (gl_kcore.hip), set up by the first call: is the pattern symmetric (-1: not established yet; the rows' verdict is
-    // tc_rows_ok above), and the pass's scratch -- 256 bytes of control record + num_rows words of queue
-    int kcore_symmetric = -1;
+    // gl_kcore (gl_kcore.hip): the pass's scratch, allocated by the first call -- 256 bytes of control record + num_rows words
+    // of queue
     unsigned char *d_kcore_scratch = nullptr;
     // gl_bc_accumulate (gl_bc.hip), as plan_in, set up by the first call: the pass's scratch -- 256 bytes of control words, two
     // arrays of num_rows + 2 level offsets, num_rows words of queue, num_rows doubles each of sigma and coef -- the page-locked
     // room the offsets are read back to, and the verdict on the last plan_out that was not this plan itself: is it the
     // transpose?  (the partner is remembered by handle AND uid: a later plan may be allocated where a destroyed one was;
-    // plan_out == plan_in asks for kcore_symmetric above)
+    // plan_out == plan_in asks for rows_symmetric above)
     uint64_t uid = gl::plan_uid();
     unsigned char *d_bc_scratch = nullptr;
     uint32_t *h_bc_pinned = nullptr;
@@ -390,14 +391,6 @@ struct SpmspvCsc {
 SpmspvCsc spmspv_plan_csc(gl_spmspv_plan p);
 // gl_spmspv.hip: forget `dying` wherever gl_spmspv_plan_attach_pull attached it
 void spmspv_detach_everywhere(gl_spmv_plan dying);
-// gl_tc.hip: establish p->tc_rows_ok (are the rows strictly ascending sets of columns below num_cols?) on first use, with one
-// kernel and one synchronisation; for a plan that keeps the row copy.  Shared by gl_tc_count and gl_kcore.
-int tc_check_rows(gl_spmv_plan p, const char *who);
-// gl_kcore.hip: is (u, v) stored in `partner` for every entry (v, u) of p?  -> *h_verdict = 0 if so.  One kernel and one
-// synchronisation; both plans keep the row copy, are square and whole, their rows strictly ascending sets of columns below
-// num_rows (tc_check_rows); d_word is a device word the check may use.  partner == p: is the pattern symmetric (gl_kcore's
-// verdict, p->kcore_symmetric, which gl_bc_accumulate shares).
-int kcore_check_transpose(gl_spmv_plan p, gl_spmv_plan partner, uint32_t *d_word, uint32_t *h_verdict);
 // gl_spmv.hip: y initialisation for plans whose units fold into y
 int spmv_init_rows(int op, int mask_type, uint32_t r0, uint32_t r1, const float *mask, float *y, float zero, hipStream_t s);
 }  // namespace gl

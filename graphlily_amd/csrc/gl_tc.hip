@@ -7,10 +7,8 @@
 // A formula about sets: an acyclic orientation (io.triangle_orient) gives every triangle once, a full symmetric pattern six
 // times, a diagonal entry simply takes part.  Integer adds commute, so the result is exact whatever the order.
 //
-// THE PLAN'S FIRST CALL establishes, with one kernel and one synchronisation, that every column is below
-// num_cols and that the columns of every row strictly ascend -- the descents of the whole entry list are counted, and so are
-// those that sit on a row boundary: the rows ascend iff the two counts agree -- then reads the row offsets back once and bins
-// the rows by length on the host (longest first inside a bin); verdict, bins and caps are cached in the plan.
+// THE PLAN'S FIRST CALL has it established that the rows are such sets (gl_rows.h: kRowsSets), then reads the
+// row offsets back once and bins the rows by length on the host (longest first inside a bin); bins and caps are cached in the plan.
 //   short  1 .. tc_short entries (32)        a sub-wave GROUP of tc_group lanes (16) per row: 256 / G rows per workgroup
 //   wave   .. tc_wave entries (1024)         a wavefront per row, four to a workgroup
 //   wide   .. tc_lds entries (4096)          a wavefront per row, one to a workgroup (the LDS BUDGET: 16 KiB of N(v) per wavefront)
@@ -29,46 +27,13 @@
 // once per row, one 64-bit add per entry that earned any; the long bin adds them to global memory directly.
 // Groups share no LDS and meet at no barrier: a slice is written and read by lanes of ONE wavefront, whose LDS operations
 // complete in order.  No spin-waits, no hand-offs between workgroups.
-#include "gl_spmv_plan.h"
+#include "gl_rows.h"
 
 namespace gl {
 
-constexpr uint32_t kTcCtlBytes = 256;
 constexpr uint32_t kTcChunk = 256;         // entries of a long row per work item
 constexpr uint32_t kTcMaxShort = 256;      // ceilings of the caps (knobs): a wavefront's slice of 4096 entries is 16 KiB of LDS,
 constexpr uint32_t kTcMaxLds = 4096;       // 32 KiB with the credit words
-
-// descents of the whole entry list and descents on row boundaries (see above); a column >= num_cols (0xffffffff: zero-valued)
-__global__ __launch_bounds__(256) void tc_check_kernel(const uint32_t *__restrict__ row_ptr, const uint32_t *__restrict__ row_idx,
-                                                       uint32_t rows, uint32_t nnz, uint32_t nz_base, uint32_t num_cols,
-                                                       uint32_t *__restrict__ ctl) {
-    uint32_t bad = 0, descents = 0, allowed = 0;
-    const uint32_t stride = gridDim.x * 256u, first = blockIdx.x * 256u + threadIdx.x;
-    for (uint64_t k = first; k < nnz; k += stride) {
-        const uint32_t c = row_idx[k];
-        bad |= c >= num_cols ? 1u : 0u;
-        if (k != 0u) descents += row_idx[k - 1u] >= c ? 1u : 0u;
-    }
-    for (uint64_t r = first; r < rows; r += stride) {
-        const uint32_t b = row_ptr[r] - nz_base, e = row_ptr[r + 1u] - nz_base;     // (offsets into the caller's entry list)
-        if (b != 0u && b < e) allowed += row_idx[b - 1u] >= row_idx[b] ? 1u : 0u;
-    }
-    if (bad) atomicOr(ctl, 1u);
-    if (descents) atomicAdd(ctl + 1, descents);
-    if (allowed) atomicAdd(ctl + 2, allowed);
-}
-
-// position of the first entry >= w in the ascending s[0 .. n), n >= 1; the result is < n
-template <typename P>
-__device__ __forceinline__ uint32_t tc_lower_bound(P s, uint32_t n, uint32_t w) {
-    uint32_t lo = 0;
-    while (n > 1u) {
-        const uint32_t half = n >> 1;
-        lo += s[lo + half - 1u] < w ? half : 0u;
-        n -= half;
-    }
-    return lo;
-}
 
 struct TcArgs {
     const uint32_t *row_ptr, *row_idx;
@@ -133,10 +98,10 @@ __global__ __launch_bounds__(256) void tc_count_kernel(TcArgs a) {
                 if (k < steps) {
                     if (flip) {
                         w = LDS ? slice[k] : nv[k];
-                        hit = nu[tc_lower_bound(nu, lu, w)] == w;
+                        hit = nu[rows_lower_bound(nu, lu, w)] == w;
                     } else {
                         w = nu[k];
-                        at = LDS ? tc_lower_bound(slice, len, w) : tc_lower_bound(nv, len, w);
+                        at = LDS ? rows_lower_bound(slice, len, w) : rows_lower_bound(nv, len, w);
                         hit = (LDS ? slice[at] : nv[at]) == w;
                     }
                 }
@@ -186,51 +151,12 @@ static void tc_launch(const TcArgs &a, bool per, unsigned threads, unsigned grid
     else tc_count_kernel<G, false, LDS><<<grid, threads, lds, s>>>(a);
 }
 
-// are the rows strictly ascending sets of columns below num_cols?  -> p->tc_rows_ok, established by one kernel and one
-// synchronisation on first use (a plan with a row copy and entries that fit 32-bit offsets; shared with gl_kcore.hip)
-int tc_check_rows(gl_spmv_plan p, const char *who) {
-    if (p->tc_rows_ok >= 0) return GL_OK;
-    hipStream_t s = ctx().stream;
-    const uint32_t rows = p->num_rows, nnz = (uint32_t)p->nnz;
-    uint32_t *ctl = nullptr;
-    hipError_t e = hipMalloc((void **)&ctl, kTcCtlBytes);
-    if (e != hipSuccess) return set_error(GL_ERR_HIP, "%s: hipMalloc(%u bytes of control words): %s", who, kTcCtlBytes, hipGetErrorString(e));
-    uint32_t h[4] = {0, 0, 0, 0};
-    e = hipMemsetAsync(ctl, 0, kTcCtlBytes, s);
-    if (e == hipSuccess && rows) {
-        const unsigned grid = std::max(1u, std::min<unsigned>(cdiv(std::max(nnz, rows), 256u), (unsigned)ctx().num_cus * 16u));
-        tc_check_kernel<<<grid, 256, 0, s>>>(p->d_csr_indptr, p->d_csr_indices, rows, nnz, p->csr_nz_base, p->num_cols, ctl);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(h, ctl, sizeof(h), hipMemcpyDeviceToHost, s);
-    const hipError_t w = hipStreamSynchronize(s);     // (waited for whether or not the copy could be enqueued: h is on the stack)
-    (void)hipFree(ctl);
-    GL_HIP(e != hipSuccess ? e : w);
-    p->tc_rows_ok = (h[0] == 0u && h[1] == h[2]) ? 1 : 0;
-    return GL_OK;
-}
-
-// the plan's verdict and bins, on first use (one synchronisation)
+// the plan's bins, on first use (one synchronisation); a matrix without entries has none: tc_items stay 0, the call only
+// zeroes its outputs
 static int tc_prepare(gl_spmv_plan p, const char *who) {
-    // (a matrix without entries is planned in the general layout whatever the flags, and keeps no row copy: it has no triangles)
-    if (p->nnz != 0 && (!p->d_csr_indptr || !p->d_csr_indices))
-        return set_error(GL_ERR_UNSUPPORTED, "%s: the plan keeps no row copy (a GL_PLAN_BOOLEAN plan in the (||,&&) layout does)", who);
-    if (p->num_rows != p->num_cols)
-        return set_error(GL_ERR_UNSUPPORTED, "%s: rows and columns name the same vertices: needs num_rows == num_cols (%u x %u)", who,
-                         p->num_rows, p->num_cols);
-    if (p->row_begin != 0u || p->row_end != p->num_rows)
-        return set_error(GL_ERR_UNSUPPORTED, "%s: a row shard [%u, %u) of %u rows: row u must be readable for every column u", who,
-                         p->row_begin, p->row_end, p->num_rows);
-    if (p->nnz > 0xffffffffull) return set_error(GL_ERR_UNSUPPORTED, "%s: %llu entries do not fit 32-bit offsets", who, (unsigned long long)p->nnz);
-    if (p->nnz == 0) return GL_OK;      // nothing to check or to bin: tc_items stay 0, the call only zeroes its outputs
     hipStream_t s = ctx().stream;
     const uint32_t rows = p->num_rows;
-    int rc = tc_check_rows(p, who);
-    if (rc != GL_OK) return rc;
-    if (p->tc_rows_ok == 0)
-        return set_error(GL_ERR_UNSUPPORTED, "%s: the rows must be strictly ascending sets of columns below num_cols (no duplicate, no "
-                         "zero-valued entry, which the row copy stores as column 0xffffffff): io.triangle_orient prepares such a matrix", who);
-    if (!p->d_tc_scratch) {
+    if (p->nnz != 0 && !p->d_tc_scratch) {
         // A/B knobs (GRAPHLILY_DEBUG, read by the plan's first call): tc_short = longest row a sub-wave group takes, tc_wave =
         // longest row of the wave bin, tc_lds = longest row staged in LDS at all (the LDS budget: longer rows are searched in
         // global memory)
@@ -258,10 +184,10 @@ static int tc_prepare(gl_spmv_plan p, const char *who) {
             std::stable_sort(b.begin(), b.end(), [&](uint32_t x, uint32_t y) { return ip[x + 1u] - ip[x] > ip[y + 1u] - ip[y]; });
         const size_t words = bin[0].size() + bin[1].size() + bin[2].size() + chunks.size();
         unsigned char *d = nullptr;
-        hipError_t e = hipMalloc((void **)&d, std::max<size_t>(words, 4u) * 4u);
-        if (e != hipSuccess) return set_error(GL_ERR_HIP, "%s: hipMalloc(%zu bytes of row bins): %s", who, words * 4u, hipGetErrorString(e));
+        const int rc = plan_scratch(d, std::max<size_t>(words, 4u) * 4u, who, "row bins");
+        if (rc != GL_OK) return rc;
         uint32_t *w = reinterpret_cast<uint32_t *>(d);
-        e = hipSuccess;
+        hipError_t e = hipSuccess;
         size_t at = 0;
         for (auto &b : bin) {
             if (e == hipSuccess && !b.empty()) e = hipMemcpy(w + at, b.data(), b.size() * 4u, hipMemcpyHostToDevice);
@@ -284,7 +210,8 @@ static int tc_prepare(gl_spmv_plan p, const char *who) {
 }
 
 static int tc_count(gl_spmv_plan p, uint64_t *d_total, uint64_t *d_per_vertex, const char *who) {
-    int rc = tc_prepare(p, who);
+    int rc = rows_require(p, kRowsSets, who, "the plan", "io.triangle_orient");
+    if (rc == GL_OK) rc = tc_prepare(p, who);
     if (rc != GL_OK) return rc;
     hipStream_t s = ctx().stream;
     GL_HIP(hipMemsetAsync(d_total, 0, 8, s));
