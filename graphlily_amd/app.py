@@ -367,6 +367,87 @@ def validate_cores(csr, core, order=None):
     return int(c.max()) if n else 0
 
 
+def _first_fit_of(indptr, indices, n, colors, prio):
+    """mex[v] = the smallest non-negative integer that is not colors[u] for any entry u of row v that goes before v in gl_color's
+    order (prio[u] > prio[v], or equal and u < v; prio None: all equal), for a symmetric simple CSR over n vertices, in numpy.
+    colors IS the first-fit greedy colouring of that order iff mex == colors: by induction along the order, every vertex's
+    colour is then the one the sequential loop would give it."""
+    indptr = np.asarray(indptr).astype(np.int64)
+    rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(indptr))
+    cols = np.asarray(indices).astype(np.int64)
+    if prio is None:
+        before = cols < rows
+    else:
+        p = np.asarray(prio).astype(np.int64)
+        before = (p[cols] > p[rows]) | ((p[cols] == p[rows]) & (cols < rows))
+    c = np.asarray(colors).astype(np.int64)
+    span = int(c.max()) + 2 if n else 1
+    key = np.unique(rows[before] * span + c[cols[before]])             # per vertex, the colours before it, ascending, once each
+    kv, kc = key // span, key % span
+    first = np.searchsorted(kv, np.arange(n, dtype=np.int64))
+    count = np.searchsorted(kv, np.arange(n, dtype=np.int64), side="right") - first
+    rank = np.arange(key.shape[0], dtype=np.int64) - first[kv]
+    mex = count.copy()                                                   # colours 0 .. count - 1 all taken: the next one
+    gap = kc != rank                                                     # the first rank whose colour is not the rank itself
+    np.minimum.at(mex, kv[gap], rank[gap])
+    return mex
+
+
+def validate_coloring(csr, colors, priorities=False):
+    """Host-side check (numpy) that `colors` is a colouring of the undirected simple graph of `csr` -- an edge {u, v} iff u != v
+    and a stored non-zero entry A[v, u] or A[u, v] exists; duplicates, the diagonal, zero values and direction are ignored -- of
+    the kind gl_color produces.  Raises ValueError naming the first offender and the rule; returns the number of colours.  The
+    rules:
+      1. no edge joins two vertices of one colour (the colouring is proper);
+      2. 0 <= colors[v] <= deg[v] (first-fit never skips more colours than v has neighbours);
+      3. colour class 0 is a MAXIMAL independent set: every vertex outside it has a neighbour inside;
+      4. with `priorities` an array (larger first, ties to the smaller vertex number) or None (ascending vertex order): colors[v]
+         is the smallest colour that no neighbour going before v has -- the array is exactly the sequential first-fit greedy
+         colouring in that order.  The default False skips this rule.
+    `colors` and `priorities` may be longer than the matrix (the drivers pad them): the extra vertices are isolated; priorities
+    shorter than colors are extended with 0 (an isolated vertex's priority does not matter)."""
+    nr, nc = int(csr.num_rows), int(csr.num_cols)
+    c = np.asarray(colors)
+    n = c.shape[0] if c.ndim == 1 else -1
+    if n < max(nr, nc):
+        raise ValueError("validate_coloring: %d colours for a %d x %d matrix" % (n, nr, nc))
+    c = c.astype(np.int64)
+    sym, deg = io.symmetrize_simple(csr)
+    m = sym.num_rows
+    indptr = np.concatenate([sym.adj_indptr.astype(np.int64), np.full(n - m, sym.nnz, dtype=np.int64)])
+    deg = np.diff(indptr)
+    rows = np.repeat(np.arange(n, dtype=np.int64), deg)
+    cols = sym.adj_indices.astype(np.int64)
+
+    def first(bad):
+        return int(np.flatnonzero(bad)[0])
+
+    same = c[rows] == c[cols]
+    if np.any(same):
+        i = first(same)
+        raise ValueError("validate_coloring: the neighbours %d and %d both have colour %d (rule 1)" % (rows[i], cols[i], c[rows[i]]))
+    if np.any((c < 0) | (c > deg)):
+        v = first((c < 0) | (c > deg))
+        raise ValueError("validate_coloring: vertex %d of degree %d is given colour %d (rule 2)" % (v, deg[v], c[v]))
+    covered = np.bincount(rows[c[cols] == 0], minlength=n) > 0
+    if np.any((c != 0) & ~covered):
+        v = first((c != 0) & ~covered)
+        raise ValueError("validate_coloring: vertex %d of colour %d has no neighbour of colour 0: class 0 is not maximal (rule 3)" % (v, c[v]))
+    if priorities is not False:
+        prio = None
+        if priorities is not None:
+            prio = np.asarray(priorities)
+            if prio.ndim != 1 or prio.shape[0] < max(nr, nc) or prio.shape[0] > n:
+                raise ValueError("validate_coloring: %d priorities for %d colours (rule 4)" % (prio.shape[0] if prio.ndim == 1 else -1, n))
+            prio = np.concatenate([prio.astype(np.int64), np.zeros(n - prio.shape[0], dtype=np.int64)])
+        want = _first_fit_of(indptr, cols, n, c, prio)
+        if np.any(want != c):
+            v = first(want != c)
+            raise ValueError("validate_coloring: vertex %d is given colour %d, the smallest colour its earlier neighbours leave free is %d "
+                             "(rule 4)" % (v, c[v], want[v]))
+    return int(c.max()) + 1 if n else 0
+
+
 def _pattern_as_scipy(csr, n):
     """the entries of a CSRMatrix as an n x n scipy matrix of f64 ones (the matrix may have fewer rows and columns)"""
     import scipy.sparse as sp
@@ -1339,6 +1420,62 @@ class KCore(_PatternApp):
         if self.core_ is None:
             raise RuntimeError("KCore.k_core(): run() first")
         mask = self.core_ >= k
+        mask[self.n_real_:] = False
+        return mask
+
+
+class GraphColoring(_PatternApp):
+    """Graph colouring: gl_color, Jones-Plassmann colouring with dependency counters.  The matrix is read as an
+    undirected simple graph -- duplicates, the diagonal, zero-valued entries and direction are ignored, as in KCore -- and stored
+    in both directions by the host (io.symmetrize_simple): colouring v must reach every neighbour of v through row v.  The result
+    is the sequential first-fit greedy colouring in the order the priorities give, to the bit."""
+    _no_shards_ = "gl_color reads row u for every column u of a row, so every rank would need the whole symmetric matrix"
+    degrees_ = colors_ = priorities_ = num_colors_ = rounds_ = launches_ = widest_ = degeneracy_ = color_sizes_ = None
+
+    def _prepare(self, csr):
+        csr, self.degrees_ = io.symmetrize_simple(csr)
+        return csr
+
+    def run(self, order="largest_first", seed=0, priorities=None):
+        """-> uint32[n_]: colors[v] = the smallest colour that no neighbour going before v has (padding vertices: 0).  The order
+        is io.coloring_priorities(degrees_, order, seed) -- "natural", "random", "largest_first" or "smallest_last", which first
+        runs gl_kcore on the same plan for its peeling order and then needs at most degeneracy_ + 1 colours -- or an explicit
+        `priorities` array of n_real_ or n_ words (larger first, ties to the smaller vertex number), which overrides `order`.
+        Leaves colors_, priorities_ (uint32[n_], the array the run used; None for natural), num_colors_, rounds_ (the depth of
+        the order's DAG), launches_, widest_ (the most vertices coloured by one round, padding vertices included), degeneracy_
+        (None unless "smallest_last" ran) and color_sizes_[c] = real vertices of colour c.  The call waits for the device."""
+        self._require_sent()
+        B, n = self.backend, self.n_
+        self.degeneracy_ = None
+        if priorities is not None:
+            prio = np.asarray(priorities)
+            if prio.ndim != 1 or prio.shape[0] not in (self.n_real_, n):
+                raise ValueError("GraphColoring.run(): priorities of shape %s, expected %d or %d words" % (prio.shape, self.n_real_, n))
+            prio = np.concatenate([prio.astype(np.uint32), np.zeros(n - prio.shape[0], dtype=np.uint32)])
+        elif order == "smallest_last":
+            peel = B.alloc(2 * n, np.float32)                        # (32-bit words: the core numbers, then the order)
+            self.degeneracy_ = self.SpMV_.kcore(B.view(peel, 0, n, 4), B.view(peel, n, n, 4))[0]
+            B.sync()
+            prio = io.coloring_priorities(self.degrees_, order, seed, peel_order=B.download(peel, np.uint32, 2 * n)[n:])
+        else:
+            prio = io.coloring_priorities(self.degrees_, order, seed)
+        out = B.alloc(2 * n if prio is not None else n, np.float32)  # (32-bit words: the colours, then the priorities)
+        if prio is not None:
+            B.upload(B.view(out, n, n, 4), prio)
+        stats = self.SpMV_.color(B.view(out, 0, n, 4), B.view(out, n, n, 4) if prio is not None else None)
+        B.sync()
+        self.colors_ = B.download(out, np.uint32, n)
+        self.priorities_ = prio
+        self.num_colors_, self.rounds_, self.launches_, self.widest_ = stats
+        self.color_sizes_ = np.bincount(self.colors_[:self.n_real_], minlength=self.num_colors_).astype(np.int64)
+        return self.colors_
+
+    def independent_set(self, c=0):
+        """-> bool[n_]: the vertices of colour c of the last run -- an independent set; padding vertices are in none.  Class 0 is
+        a MAXIMAL independent set, the first-fit one of the run's order: every other vertex has a neighbour in it."""
+        if self.colors_ is None:
+            raise RuntimeError("GraphColoring.independent_set(): run() first")
+        mask = self.colors_ == c
         mask[self.n_real_:] = False
         return mask
 

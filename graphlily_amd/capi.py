@@ -51,6 +51,9 @@ EXPORTS = [
     "gl_assign_sparse_new_frontier", "gl_sparse_to_dense",
     "gl_csr2csc", "gl_csr_normalize_by_outdegree", "gl_npz_csr_open", "gl_npz_csr_read", "gl_npz_csr_close",
 ]
+# every symbol include/graphlily_hip_ext.h declares: extensions to the ABI are listed here from now on (EXPORTS and its header are
+# pinned by the suite as they are; tests and build() check this list in the same way)
+EXT_EXPORTS = ["gl_color"]
 
 
 class GraphLilyError(RuntimeError):
@@ -117,6 +120,7 @@ def lib():
         "gl_cc_begin": [vp, u32], "gl_cc_hook": [vp, vp], "gl_cc_finish": [vp, u32, vp, vp], "gl_cc_labels": [vp, vp, vp],
         "gl_tc_count": [vp, vp, vp],
         "gl_kcore": [vp, vp, vp, P(u32)],
+        "gl_color": [vp, vp, vp, P(u64)],
         "gl_bc_accumulate": [vp, vp, vp, vp, ctypes.c_double, i32, vp, P(u32)],
         "gl_spmv_run": [vp, vp, vp, vp, i32, f32, i32],
         "gl_prof_begin": [u32, u32], "gl_prof_end": [P(ctypes.c_double), P(u32)], "gl_span_begin": [], "gl_span_end": [P(ctypes.c_double)],
@@ -466,6 +470,17 @@ class SpMVPlan:
         written by the call, which SYNCHRONISES (it reads a control record back between batches of launches)."""
         stats = (ctypes.c_uint32 * 4)(0xdeadbeef, 0xdeadbeef, 0xdeadbeef, 0xdeadbeef)
         check(lib().gl_kcore(ctypes.c_void_p(self.handle), _p(core), _p(order), stats))
+        return tuple(int(x) for x in stats)
+
+    def color(self, prio, color):
+        """gl_color: the first-fit greedy colouring of this plan's graph in the order of `prio` (num_rows device words, or None:
+        ascending vertex order; u goes before v iff prio[u] > prio[v], or they are equal and u < v) into `color` (num_rows device
+        words) -> (num_colors, rounds = depth of the order's DAG, launches enqueued, widest round).  The plan is square, whole,
+        its rows strictly ascending sets, its pattern symmetric (io.symmetrize_simple prepares it).  `color` is fully written
+        by the call, which SYNCHRONISES (it reads a control record back between batches of launches)."""
+        garbage = 0xdeadbeefdeadbeef
+        stats = (ctypes.c_uint64 * 4)(garbage, garbage, garbage, garbage)
+        check(lib().gl_color(ctypes.c_void_p(self.handle), _p(prio), _p(color), stats))
         return tuple(int(x) for x in stats)
 
     def bc_accumulate(self, plan_out, level, bc, scale=1.0, accumulate=False, sigma=None, stats=True):

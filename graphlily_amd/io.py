@@ -128,6 +128,49 @@ def symmetrize_simple(csr_matrix):
     return sym, deg.astype(np.uint32)
 
 
+COLORING_ORDERS = ("natural", "random", "largest_first", "smallest_last")
+
+
+def coloring_hash(v, seed=0):
+    """-> uint32 array: murmur3's fmix32 of (v + 0x9e3779b9 * (seed + 1)) mod 2^32, all arithmetic mod 2^32 -- a bijection of the
+    32-bit words, so the hashes of distinct vertices never tie"""
+    h = (np.asarray(v).astype(np.uint64) + np.uint64(0x9e3779b9) * np.uint64((int(seed) + 1) & 0xFFFFFFFF)) & np.uint64(0xFFFFFFFF)
+    h ^= h >> np.uint64(16)
+    h = (h * np.uint64(0x85ebca6b)) & np.uint64(0xFFFFFFFF)
+    h ^= h >> np.uint64(13)
+    h = (h * np.uint64(0xc2b2ae35)) & np.uint64(0xFFFFFFFF)
+    h ^= h >> np.uint64(16)
+    return h.astype(np.uint32)
+
+
+def coloring_priorities(degrees, order, seed=0, peel_order=None):
+    """The priorities of GraphColoring (an extension) for the len(degrees) vertices -> uint32[n], or None for "natural".  A vertex
+    of larger priority is coloured first, ties go to the smaller vertex number (gl_color's order):
+      "natural"        None: every priority equal, plain ascending vertex order
+      "random"         coloring_hash(v, seed): a permutation, no ties
+      "largest_first"  (min(deg[v], 4095) << 20) | (coloring_hash(v, seed) >> 12): by capped degree, then by hash; ties exist
+      "smallest_last"  prio[peel_order[i]] = i for the peeling order gl_kcore returns on the same graph: the last vertex
+                       peeled is coloured first, every vertex has at most core[v] neighbours before it, so degeneracy + 1
+                       colours suffice (Matula & Beck).  The order is not unique: keep the array the run used.
+    graphlily::io::util_coloring_priorities (include/graphlily/io/data_formatter.h) computes the same words."""
+    deg = np.asarray(degrees)
+    n = deg.shape[0]
+    if order == "natural":
+        return None
+    if order == "random":
+        return coloring_hash(np.arange(n), seed)
+    if order == "largest_first":
+        return ((np.minimum(deg.astype(np.uint64), np.uint64(4095)) << np.uint64(20)).astype(np.uint32)
+                | (coloring_hash(np.arange(n), seed) >> np.uint32(12)))
+    if order == "smallest_last":
+        if peel_order is None or np.asarray(peel_order).shape != (n,):
+            raise ValueError("coloring_priorities: \"smallest_last\" needs peel_order, the %d vertices in gl_kcore's peeling order" % n)
+        prio = np.empty(n, dtype=np.uint32)
+        prio[np.asarray(peel_order).astype(np.int64)] = np.arange(n, dtype=np.uint32)
+        return prio
+    raise ValueError("coloring_priorities: order %r is none of %s" % (order, ", ".join(COLORING_ORDERS)))
+
+
 def simple_pattern(csr_matrix):
     """The matrix preparation of BetweennessCentrality (an extension) -> (csr_in, csr_out or None, symmetric).  The simple
     directed graph of the matrix has an edge u -> v iff u != v and a stored non-zero entry A[v, u] exists: zero values, the

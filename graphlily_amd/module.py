@@ -295,6 +295,19 @@ class SpMVModule(BaseModule):
         self._finish(core_buf, order_buf)
         return stats
 
+    def color(self, color_buf, prio_buf=None):
+        """Extension (gl_color): the first-fit greedy colouring of this module's matrix, read as a graph -- rows as strictly
+        ascending sets N(v), the pattern symmetric -- in the order of `prio_buf` (get_num_rows() words, larger first, ties by
+        vertex number; None: ascending vertex order) into `color_buf` (get_num_rows() words) -> (num_colors, rounds, launches,
+        widest).  The call synchronises.  Raises GraphLilyError (GL_ERR_UNSUPPORTED) when the plan keeps no row copy (only the
+        (||,&&) layout does), is not square, is a row shard, its rows are no such sets or its pattern is not symmetric
+        (io.symmetrize_simple prepares it)."""
+        if self.plan_ is None:
+            _fatal("SpMVModule.color: send_matrix_host_to_device first")
+        stats = self.plan_.color(prio_buf, color_buf)
+        self._finish(color_buf)
+        return stats
+
     def bc_accumulate(self, out_module, level_buf, bc_buf, scale=1.0, accumulate=False, sigma_buf=None, stats=True):
         """Extension (gl_bc_accumulate): adds scale x Brandes' dependency of the search whose levels are in `level_buf`
         (get_num_rows() floats) to `bc_buf` (as many doubles; accumulate=False: overwrites it).  This module's matrix is the

@@ -8,6 +8,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <string>
 #include <type_traits>
 #include <vector>
 
@@ -111,6 +112,46 @@ CSRMatrix<data_type> util_symmetrize_simple(CSRMatrix<data_type> const &m, std::
     for (uint64_t v = 0; v < n; v++) out.adj_indptr[v + 1] = out.adj_indptr[v] + degrees[v];
     out.adj_data.assign(out.adj_indices.size(), data_type(1));
     return out;
+}
+
+// murmur3's fmix32 of (v + 0x9e3779b9 * (seed + 1)) mod 2^32, all arithmetic mod 2^32: a bijection of the 32-bit words, so the
+// hashes of distinct vertices never tie (io.coloring_hash computes the same word)
+inline uint32_t util_coloring_hash(uint32_t v, uint32_t seed) {
+    uint32_t h = v + 0x9e3779b9u * (seed + 1u);
+    h ^= h >> 16;
+    h *= 0x85ebca6bu;
+    h ^= h >> 13;
+    h *= 0xc2b2ae35u;
+    h ^= h >> 16;
+    return h;
+}
+
+// The priorities of app::GraphColoring (an extension) for the degrees.size() vertices, the words io.coloring_priorities gives: a
+// vertex of larger priority is coloured first, ties go to the smaller vertex number.  "natural": an EMPTY vector (every priority
+// equal, plain ascending vertex order); "random": the hash; "largest_first": (min(deg, 4095) << 20) | (hash >> 12);
+// "smallest_last": prio[peel_order[i]] = i for the peeling order gl_kcore returns on the same graph -- the last vertex peeled is
+// coloured first, and degeneracy + 1 colours suffice.
+inline std::vector<uint32_t> util_coloring_priorities(std::vector<uint32_t> const &degrees, std::string const &order, uint32_t seed,
+                                                      std::vector<uint32_t> const &peel_order = std::vector<uint32_t>()) {
+    const size_t n = degrees.size();
+    std::vector<uint32_t> prio;
+    if (order == "natural") return prio;
+    prio.assign(n, 0);
+    if (order == "random") {
+        for (size_t v = 0; v < n; v++) prio[v] = util_coloring_hash((uint32_t)v, seed);
+    } else if (order == "largest_first") {
+        for (size_t v = 0; v < n; v++) prio[v] = (std::min<uint32_t>(degrees[v], 4095u) << 20) | (util_coloring_hash((uint32_t)v, seed) >> 12);
+    } else if (order == "smallest_last") {
+        if (peel_order.size() != n) {
+            printf("util_coloring_priorities: \"smallest_last\" needs the %zu vertices in gl_kcore's peeling order\n", n);
+            exit(EXIT_FAILURE);
+        }
+        for (size_t i = 0; i < n; i++) prio[peel_order[i]] = (uint32_t)i;
+    } else {
+        printf("util_coloring_priorities: order \"%s\" is none of natural, random, largest_first, smallest_last\n", order.c_str());
+        exit(EXIT_FAILURE);
+    }
+    return prio;
 }
 
 // The matrix preparation of app::BetweennessCentrality (an extension): the simple DIRECTED graph of m -- an edge u -> v iff u != v

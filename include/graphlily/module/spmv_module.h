@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "graphlily/global.h"
+#include "graphlily_hip_ext.h"
 #include "graphlily/io/data_formatter.h"
 #include "graphlily/io/data_loader.h"
 #include "graphlily/module/base_module.h"
@@ -197,6 +198,16 @@ public:
     void kcore(DeviceBuffer core, uint32_t *order = nullptr, uint32_t *stats = nullptr) {
         barrier_();
         GRAPHLILY_CHECK(gl_kcore(plan_, (uint32_t *)core.ptr(), order, stats));
+        finish_();
+    }
+    // extension (gl_color, graphlily_hip_ext.h): the first-fit greedy colouring of this module's matrix, read as a graph -- rows as
+    // strictly ascending sets N(v), the pattern symmetric (graphlily::io::util_symmetrize_simple prepares it) -- into `color`
+    // (get_num_rows() words), in the order of `prio` (as many device words, larger first, ties to the smaller vertex number;
+    // nullptr: ascending vertex order); stats (optional, 4 host words) receives {num_colors, rounds, launches, widest}.  Only the
+    // (||,&&) layout keeps the rows this pass walks.  The call synchronises.
+    void color(DeviceBuffer color, const uint32_t *prio = nullptr, uint64_t *stats = nullptr) {
+        barrier_();
+        GRAPHLILY_CHECK(gl_color(plan_, prio, (uint32_t *)color.ptr(), stats));
         finish_();
     }
     // extension (gl_bc_accumulate): adds scale x Brandes' dependency of the search whose levels are in `level` (get_num_rows()

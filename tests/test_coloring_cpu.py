@@ -1,0 +1,382 @@
+"""CPU suite of the graph colouring (gl_color, SpMVPlan.color, SpMVModule.color, io.coloring_priorities, app.GraphColoring,
+app.validate_coloring): the export and its bindings exist and are declared where extensions to the ABI go, the priorities are the
+words the definition gives, the host statement of the definitions (greedy_by_priority, kept here) agrees with networkx, the
+validator accepts its colourings and refuses one violation per rule, the driver refuses what it cannot do, and the C++ driver
+compiles against include/ and computes the same priorities.  tests/test_gpu_coloring.py compares the kernels with
+greedy_by_priority bit for bit."""
+import functools
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from graphlily_amd import app, capi, io, module as M
+
+from cpu_backend import CpuBackend
+from helpers import named_matrix
+from test_kcore_cpu import _TwoRanks, _csr
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LIBDIR = os.path.join(ROOT, "graphlily_amd", "lib")
+COLORING_DRIVER = os.path.join(ROOT, "build", "coloring_driver")
+DECL = ("int gl_color(gl_spmv_plan plan, const uint32_t *d_prio /* may be NULL */, uint32_t *d_color, "
+        "uint64_t *h_stats /* may be NULL, 4 words: num_colors, rounds, launches, widest */);")
+ORDERS = ("natural", "random", "largest_first")
+# (num_colors, rounds, widest, sum of the colours) of the graphs padded to 128, seed 0: computed on the CPU by greedy_by_priority,
+# whose colourings test_host_greedy_agrees_with_networkx compares with networkx.greedy_color (3.4.2) on smaller graphs every time;
+# test_records recomputes them
+RECORDS = {
+    "uniform_10K_10": {"natural": (12, 54, 613, 34220), "random": (12, 51, 620, 34027), "largest_first": (11, 48, 416, 34486)},
+    "rmat_20K": {"natural": (99, 398, 7166, 41703), "random": (94, 380, 7020, 41462), "largest_first": (69, 340, 4205, 44593)},
+    "rmat_sym_50K": {"natural": (105, 481, 21335, 79180), "random": (104, 475, 21008, 80012), "largest_first": (73, 440, 14135, 82176)},
+    "gplus_small": {"natural": (223, 771, 2005, 103824), "random": (217, 771, 1970, 104557), "largest_first": (184, 699, 846, 122331)},
+}
+
+
+@functools.lru_cache(maxsize=None)
+def graph(name):
+    """-> (the matrix as given, padded to 128, its symmetric simple form); computed once and shared, never written"""
+    from test_cc_cpu import many_components
+    if name in ("line_8", "eye_10"):
+        raw = io.load_csr_matrix_from_float_npz(os.path.join(ROOT, "tests", "golden", name + "_csr_float32.npz"))
+    elif name == "many":
+        raw = many_components()
+    else:
+        raw = named_matrix(name)
+    m = raw.copy()
+    io.util_round_csr_matrix_dim(m, 128, 128)
+    return raw, m, io.symmetrize_simple(m)[0]
+
+
+def order_of(n, prio):
+    """the vertices in gl_color's order: larger priority first, ties to the smaller vertex number; prio None: every priority 0"""
+    p = np.zeros(n, np.int64) if prio is None else np.asarray(prio).astype(np.int64)
+    assert p.shape == (n,)
+    return np.lexsort((np.arange(n), -p))
+
+
+def greedy_by_priority(sym, prio):
+    """The definitions, one vertex at a time: sequential first-fit greedy in the order of the keys (prio[v], v).  colour[v] = the
+    smallest non-negative integer that no neighbour coloured before v has; round[v] = 1 + the largest round of those neighbours
+    (1 without any).  -> (colours as uint32[n], rounds per vertex as uint32[n]).  `sym` is a symmetric simple CSRMatrix
+    (io.symmetrize_simple), possibly with diagonal entries, which are ignored."""
+    n = sym.num_rows
+    ip, idx = sym.adj_indptr.astype(np.int64).tolist(), sym.adj_indices.astype(np.int64).tolist()
+    colour, rnd = [-1] * n, [0] * n
+    for v in order_of(n, prio).tolist():
+        used, r = set(), 0
+        for u in idx[ip[v]:ip[v + 1]]:
+            c = colour[u]
+            if c >= 0 and u != v:
+                used.add(c)
+                r = max(r, rnd[u])
+        c = 0
+        while c in used:
+            c += 1
+        colour[v], rnd[v] = c, r + 1
+    return np.array(colour, dtype=np.uint32), np.array(rnd, dtype=np.uint32)
+
+
+def summary(colours, rounds):
+    """-> (num_colors, rounds, widest, sum of the colours)"""
+    if colours.shape[0] == 0:
+        return 0, 0, 0, 0
+    return int(colours.max()) + 1, int(rounds.max()), int(np.bincount(rounds).max()), int(colours.sum())
+
+
+@functools.lru_cache(maxsize=None)
+def reference(name, order, seed=0):
+    """-> (priorities or None, colours, rounds per vertex) of a graph of graph() under one of ORDERS; computed
+    once and shared, never written"""
+    _, m, sym = graph(name)
+    prio = io.coloring_priorities(np.diff(sym.adj_indptr.astype(np.int64)), order, seed)
+    colours, rounds = greedy_by_priority(sym, prio)
+    for a in (prio, colours, rounds):
+        if a is not None:
+            a.setflags(write=False)
+    if name in RECORDS:
+        assert summary(colours, rounds) == RECORDS[name][order]
+    return prio, colours, rounds
+
+
+def _ext_names():
+    text = open(os.path.join(ROOT, "include", "graphlily_hip_ext.h")).read()
+    return text, sorted(set(re.findall(r"\b(gl_[a-z0-9_]+)\s*\(", text)))
+
+
+def test_library_exports_and_binds_the_entry_point():
+    L = capi.lib()
+    assert hasattr(L, "gl_color"), "libgraphlily_hip.so does not export gl_color"
+    assert len(L.gl_color.argtypes) == 4
+    ext, names = _ext_names()
+    assert DECL in ext and '#include "graphlily_hip.h"' in ext and 'extern "C"' in ext
+    assert sorted(capi.EXT_EXPORTS) == names == ["gl_color"]
+    assert all(hasattr(L, s) for s in capi.EXT_EXPORTS)
+    # the pinned header and list stay as they are: extensions go to the new header
+    assert "gl_color" not in capi.EXPORTS and "gl_color" not in open(os.path.join(ROOT, "include", "graphlily_hip.h")).read()
+    assert not set(capi.EXPORTS) & set(capi.EXT_EXPORTS)
+    assert callable(capi.SpMVPlan.color) and callable(M.SpMVModule.color) and callable(io.coloring_priorities)
+    assert callable(app.GraphColoring.run) and callable(app.GraphColoring.independent_set) and callable(app.validate_coloring)
+    spmv_h = open(os.path.join(ROOT, "include", "graphlily", "module", "spmv_module.h")).read()
+    assert "color(DeviceBuffer color, const uint32_t *prio = nullptr, uint64_t *stats = nullptr)" in spmv_h
+    assert '#include "graphlily_hip_ext.h"' in spmv_h
+    coloring_h = open(os.path.join(ROOT, "include", "graphlily", "app", "coloring.h")).read()
+    for piece in ("class GraphColoring", "num_colors()", "rounds()", "widest()", "color_sizes()", "util_coloring_priorities", "smallest_last"):
+        assert piece in coloring_h
+    fmt_h = open(os.path.join(ROOT, "include", "graphlily", "io", "data_formatter.h")).read()
+    for piece in ("util_coloring_priorities", "0x9e3779b9", "0x85ebca6b", "0xc2b2ae35", "natural", "random", "largest_first", "smallest_last"):
+        assert piece in fmt_h
+    assert "gl_color.hip" in open(os.path.join(ROOT, "graphlily_amd", "csrc", "Makefile")).read()
+    assert "EXT_EXPORTS" in open(os.path.join(ROOT, "__graft_entry__.py")).read()
+
+
+def test_entry_point_fails_loudly_without_a_gpu():
+    if capi.device_count() == 0:
+        assert capi.lib().gl_color(None, None, None, None) == capi.GL_ERR_NOT_INITIALIZED
+
+
+def test_priorities_on_hand_written_values():
+    # fmix32 of v + 0x9e3779b9 * (seed + 1), worked out by hand (integer arithmetic mod 2^32, outside the function under test)
+    def fmix(v, seed):
+        h = (v + 0x9e3779b9 * (seed + 1)) & 0xFFFFFFFF
+        h ^= h >> 16
+        h = (h * 0x85ebca6b) & 0xFFFFFFFF
+        h ^= h >> 13
+        h = (h * 0xc2b2ae35) & 0xFFFFFFFF
+        h ^= h >> 16
+        return h
+    assert [fmix(v, 0) for v in (0, 1, 2, 1000)] == [2462723854, 2527132011, 3024231355, 661457464]
+    assert [fmix(v, 3) for v in (0, 5)] == [1275600319, 387527240]
+    assert fmix((-0x9e3779b9) & 0xFFFFFFFF, 0) == 0                    # (fmix32 fixes 0)
+    deg = np.array([3, 0, 5000, 4095, 4096, 7], np.uint32)
+    assert io.coloring_priorities(deg, "natural") is None and io.coloring_priorities(deg, "natural", 9) is None
+    r = io.coloring_priorities(deg, "random")
+    assert r.dtype == np.uint32 and r.tolist()[:3] == [2462723854, 2527132011, 3024231355]
+    assert io.coloring_priorities(deg, "random", 3).tolist()[0] == 1275600319 and io.coloring_priorities(deg, "random", 3).tolist()[5] == 387527240
+    assert np.array_equal(io.coloring_hash(np.array([1000]), 0), [661457464])
+    lf = io.coloring_priorities(deg, "largest_first")
+    assert lf.dtype == np.uint32
+    assert lf.tolist() == [(min(int(d), 4095) << 20) | (fmix(v, 0) >> 12) for v, d in enumerate(deg.tolist())]
+    assert (lf >> 20).tolist() == [3, 0, 4095, 4095, 4095, 7]
+    assert lf[0] == (3 << 20) | (2462723854 >> 12)
+    peel = np.array([4, 1, 0, 5, 3, 2], np.uint32)
+    sl = io.coloring_priorities(deg, "smallest_last", peel_order=peel)
+    assert sl.dtype == np.uint32 and sl[peel].tolist() == [0, 1, 2, 3, 4, 5] and sl.tolist() == [2, 1, 5, 4, 0, 3]
+    with pytest.raises(ValueError, match="peel_order"):
+        io.coloring_priorities(deg, "smallest_last")
+    with pytest.raises(ValueError, match="none of natural, random, largest_first, smallest_last"):
+        io.coloring_priorities(deg, "smallest_first")
+
+
+def test_random_is_a_permutation_and_largest_first_orders_by_capped_degree():
+    for seed in (0, 1, 12345):
+        r = io.coloring_priorities(np.zeros(200000, np.uint32), "random", seed)
+        assert np.unique(r).shape[0] == 200000, "a bijection of the vertex numbers: no ties"
+    assert not np.array_equal(io.coloring_priorities(np.zeros(64), "random", 0), io.coloring_priorities(np.zeros(64), "random", 1))
+    _, _, sym = graph("rmat_20K")
+    deg = np.diff(sym.adj_indptr.astype(np.int64))
+    assert deg.max() > 4095 or deg.max() > 100
+    prio = io.coloring_priorities(deg, "largest_first", 7)
+    order = order_of(deg.shape[0], prio)
+    assert np.all(np.diff(np.minimum(deg, 4095)[order]) <= 0), "degrees never ascend along the order"
+    capped = io.coloring_priorities(np.array([4095, 4096, 100000, 4094]), "largest_first")
+    assert (capped >> 20).tolist() == [4095, 4095, 4095, 4094]
+    # ties exist (20 bits of hash for 2^32 vertices) and go to the smaller vertex number
+    same = np.array([5, 5], np.uint32)
+    assert order_of(2, same).tolist() == [0, 1] and order_of(3, np.array([1, 9, 9])).tolist() == [1, 2, 0]
+
+
+def _nx_graph(sym):
+    import networkx as nx
+    G = nx.Graph()
+    G.add_nodes_from(range(sym.num_rows))
+    rows = np.repeat(np.arange(sym.num_rows), np.diff(sym.adj_indptr.astype(np.int64)))
+    keep = rows != sym.adj_indices
+    G.add_edges_from(zip(rows[keep].tolist(), sym.adj_indices[keep].tolist()))
+    return G
+
+
+def _small_graphs():
+    """graphs of a few hundred vertices: random sparse, random dense, a clique with pendants, a path"""
+    rng = np.random.default_rng(11)
+    out = []
+    for n, m in ((300, 900), (200, 4000), (257, 300)):
+        a, b = rng.integers(0, n, m), rng.integers(0, n, m)
+        out.append(io.symmetrize_simple(_csr(n, a, b))[0])
+    iu = np.triu_indices(30, 1)
+    out.append(io.symmetrize_simple(_csr(128, np.concatenate([iu[0], np.arange(30)]), np.concatenate([iu[1], np.arange(40, 70)])))[0])
+    out.append(graph("line_8")[2])
+    return out
+
+
+def test_host_greedy_agrees_with_networkx():
+    import networkx as nx
+    for g, sym in enumerate(_small_graphs()):
+        n = sym.num_rows
+        deg = np.diff(sym.adj_indptr.astype(np.int64))
+        G = _nx_graph(sym)
+        prios = [io.coloring_priorities(deg, o, g) for o in ORDERS] + [np.full(n, 7, np.uint32), (np.arange(n) % 5).astype(np.uint32)]
+        for prio in prios:
+            order = order_of(n, prio).tolist()
+            want = nx.greedy_color(G, strategy=lambda G, colors: order)
+            colours, rounds = greedy_by_priority(sym, prio)
+            assert np.array_equal(colours, np.array([want[v] for v in range(n)], dtype=np.uint32))
+            assert app.validate_coloring(sym, colours, prio) == int(colours.max()) + 1
+            # the rounds: the longest chain of neighbours that go before one another, ending in v
+            pos = np.empty(n, np.int64)
+            pos[order] = np.arange(n)
+            depth = np.zeros(n, np.int64)
+            ip = sym.adj_indptr.astype(np.int64)
+            for v in order:
+                nb = sym.adj_indices[ip[v]:ip[v + 1]].astype(np.int64)
+                nb = nb[pos[nb] < pos[v]]
+                depth[v] = 1 + (depth[nb].max() if nb.size else 0)
+            assert np.array_equal(rounds, depth)
+    # all-equal priorities are the natural order
+    sym = _small_graphs()[0]
+    assert np.array_equal(greedy_by_priority(sym, None)[0], greedy_by_priority(sym, np.full(sym.num_rows, 0xFFFFFFFF, np.uint32))[0])
+
+
+@pytest.mark.parametrize("name", ["uniform_10K_10", "rmat_20K", "rmat_sym_50K", "gplus_small"])
+def test_records(name):
+    _, m, sym = graph(name)
+    for order in ORDERS:
+        prio, colours, rounds = reference(name, order)
+        assert summary(colours, rounds) == RECORDS[name][order]
+        assert app.validate_coloring(m, colours, prio) == RECORDS[name][order][0]
+    # (colours / rounds of the issue's restatement of the definitions)
+    table = {"uniform_10K_10": ((12, 51), (11, 48)), "rmat_20K": ((94, 380), (69, 340)), "rmat_sym_50K": ((104, 475), (73, 440)),
+             "gplus_small": ((217, 771), (184, 699))}
+    assert (RECORDS[name]["random"][:2], RECORDS[name]["largest_first"][:2]) == table[name]
+
+
+def test_validate_coloring_accepts_the_reference_and_refuses_one_violation_per_rule():
+    raw, m, sym = graph("uniform_10K_10")
+    n = sym.num_rows
+    ip = sym.adj_indptr.astype(np.int64)
+    deg = np.diff(ip)
+    for order in ORDERS:
+        prio, colours, _ = reference("uniform_10K_10", order)
+        k = RECORDS["uniform_10K_10"][order][0]
+        assert app.validate_coloring(m, colours) == k and app.validate_coloring(m, colours, prio) == k
+        assert app.validate_coloring(raw, colours, prio) == k            # (arrays longer than the matrix: the drivers pad)
+        if prio is not None:
+            assert app.validate_coloring(raw, colours, prio[:raw.num_rows]) == k
+    prio, colours, _ = reference("uniform_10K_10", "random")
+    with pytest.raises(ValueError, match="colours for a"):
+        app.validate_coloring(m, colours[:100])
+    with pytest.raises(ValueError, match=r"priorities for \d+ colours \(rule 4\)"):
+        app.validate_coloring(m, colours, prio[:100])
+    # rule 1: an improper edge
+    v = int(np.flatnonzero(deg > 0)[0])
+    u = int(sym.adj_indices[ip[v]])
+    bad = colours.copy()
+    bad[v] = bad[u]
+    with pytest.raises(ValueError, match=r"the neighbours \d+ and \d+ both have colour %d \(rule 1\)" % bad[u]):
+        app.validate_coloring(m, bad)
+    # rule 2: a colour above the degree that collides with nobody
+    v = int(np.flatnonzero(deg > 0)[5])
+    bad = colours.copy()
+    bad[v] = 1000
+    with pytest.raises(ValueError, match=r"vertex %d of degree %d is given colour 1000 \(rule 2\)" % (v, deg[v])):
+        app.validate_coloring(m, bad)
+    # rule 3: a vertex of class 0 moved to a colour none of its neighbours has, within its degree: proper, but its place in class 0 is free
+    rows = np.repeat(np.arange(n), deg)
+    for v in np.flatnonzero((colours == 0) & (deg > 0)).tolist():
+        nb = sym.adj_indices[ip[v]:ip[v + 1]]
+        free = [c for c in range(1, int(deg[v]) + 1) if c not in set(colours[nb].tolist())]
+        # ... and every neighbour keeps another neighbour of colour 0, so that v is the only uncovered vertex
+        others = all(np.count_nonzero(colours[sym.adj_indices[ip[w]:ip[w + 1]]] == 0) > 1 for w in nb.tolist())
+        if free and others:
+            break
+    bad = colours.copy()
+    bad[v] = free[0]
+    with pytest.raises(ValueError, match=r"vertex %d of colour %d has no neighbour of colour 0: class 0 is not maximal \(rule 3\)" % (v, free[0])):
+        app.validate_coloring(m, bad)
+    # rule 4: a proper colouring with a maximal class 0 that is not the greedy one of the given order -- the greedy colouring of
+    # ANOTHER order passes rules 1 to 3
+    other, lf, _ = reference("uniform_10K_10", "largest_first")
+    assert not np.array_equal(lf, colours)
+    assert app.validate_coloring(m, lf) == RECORDS["uniform_10K_10"]["largest_first"][0]
+    with pytest.raises(ValueError, match=r"vertex \d+ is given colour \d+, the smallest colour its earlier neighbours leave free is \d+ \(rule 4\)"):
+        app.validate_coloring(m, lf, prio)
+    with pytest.raises(ValueError, match=r"rule 4"):
+        app.validate_coloring(m, lf, None)
+    # ... and a single vertex raised to its next free colour
+    v = int(np.flatnonzero((colours > 0) & (colours + 1 < deg))[0])
+    nb = set(colours[sym.adj_indices[ip[v]:ip[v + 1]]].tolist())
+    up = next(c for c in range(int(colours[v]) + 1, int(deg[v]) + 1) if c not in nb)
+    bad = colours.copy()
+    bad[v] = up
+    with pytest.raises(ValueError, match=r"rule 4"):
+        app.validate_coloring(m, bad, prio)
+
+
+def test_validator_on_closed_forms():
+    for name in ("many", "line_8", "eye_10"):
+        _, m, sym = graph(name)
+        for order in ORDERS:
+            prio, colours, rounds = reference(name, order)
+            assert app.validate_coloring(m, colours, prio) == int(colours.max()) + 1
+    assert reference("line_8", "natural")[1][:8].tolist() == [0, 1, 0, 1, 0, 1, 0, 1]
+    assert not reference("eye_10", "random")[1].any() and summary(*reference("eye_10", "random")[1:])[:3] == (1, 1, 128)
+    assert app.validate_coloring(_csr(0, [], []), np.zeros(0, np.uint32), None) == 0
+
+
+def test_driver_refuses_row_shards_and_runs_before_send(golden_dir):
+    with pytest.raises(NotImplementedError, match="row shards are not supported -- gl_color reads row u for every column u"):
+        app.GraphColoring(comm=_TwoRanks(), backend=CpuBackend())
+    gc = app.GraphColoring(backend=CpuBackend())
+    with pytest.raises(RuntimeError, match="send_matrix_host_to_device"):
+        gc.run()
+    with pytest.raises(RuntimeError, match="run\\(\\) first"):
+        gc.independent_set()
+    gc.load_and_format_matrix(os.path.join(golden_dir, "line_8_csr_float32.npz"))
+    assert (gc.n_, gc.n_real_) == (128, 8) and gc.degrees_.shape == (128,) and gc.degrees_[:8].max() == 2 and not gc.degrees_[8:].any()
+    for kw in ({}, {"order": "natural"}, {"order": "smallest_last"}, {"priorities": np.arange(8, dtype=np.uint32)}):
+        with pytest.raises(RuntimeError, match="send_matrix_host_to_device"):
+            gc.run(**kw)
+    with pytest.raises(RuntimeError, match="run\\(\\) first"):
+        gc.independent_set(0)
+    assert gc.colors_ is None and gc.num_colors_ is None and gc.degeneracy_ is None
+
+
+def build_cpp_driver():
+    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
+    subprocess.check_call(["g++", "-std=c++11", "-O2", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "tests", "cpp", "coloring_driver.cpp"), "-o", COLORING_DRIVER,
+                           "-L", LIBDIR, "-lgraphlily_hip", "-Wl,-rpath," + LIBDIR])
+
+
+def save_npz(path, m):
+    import scipy.sparse as sp
+    A = sp.csr_matrix((m.adj_data, m.adj_indices.astype(np.int32), m.adj_indptr.astype(np.int32)), shape=(m.num_rows, m.num_cols), dtype=np.float32)
+    sp.save_npz(path, A, compressed=False)
+
+
+def test_cpp_driver_compiles_computes_the_same_priorities_and_fails_loudly_without_gpu(tmp_path):
+    build_cpp_driver()
+    raw = graph("uniform_10K_10")[0]
+    path = str(tmp_path / "uniform_csr_float32.npz")
+    save_npz(path, raw)
+    p = raw.copy()
+    io.util_round_csr_matrix_dim(p, 128, 128)
+    _, deg = io.symmetrize_simple(p)
+    for order, seed in (("random", 0), ("random", 5), ("largest_first", 0), ("largest_first", 77), ("natural", 0)):
+        r = subprocess.run([COLORING_DRIVER, "--priorities", path, order, str(seed)], capture_output=True, text=True, timeout=120)   # host only
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        got = {line.split(":")[0]: line.split(":")[1].split() for line in r.stdout.splitlines() if ":" in line}
+        assert [int(x) for x in got["vertices"]] == [deg.shape[0]]
+        want = io.coloring_priorities(deg, order, seed)
+        if want is None:
+            assert got["priorities"] == []
+        else:
+            assert np.array_equal(np.array(got["priorities"], dtype=np.uint32), want)
+    r = subprocess.run([COLORING_DRIVER, "--priorities", path, "smallest_first", "0"], capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and "none of natural, random, largest_first, smallest_last" in r.stdout
+    if capi.device_count() == 0:
+        r = subprocess.run([COLORING_DRIVER, str(tmp_path / "none.npz"), str(tmp_path), "natural", "0"], capture_output=True, text=True)
+        assert r.returncode != 0
+        assert "gl_init" in r.stdout + r.stderr       # print-and-exit convention of the reference
