@@ -448,6 +448,141 @@ def validate_coloring(csr, colors, priorities=False):
     return int(c.max()) + 1 if n else 0
 
 
+def _edges_and_triangles_of(indptr, indices, n, chunk=1 << 22):
+    """The edges and the triangles of a symmetric simple CSR over n vertices, in numpy -> (eid as int64[nnz]: the edge of every
+    entry, the entries with row < column numbered in row order and -1 on the diagonal; eu, ev: the ends of every edge, eu < ev;
+    tri as int64[T, 3]: the edges (u, v), (v, w), (u, w) of every triangle u < v < w, once each).  For every edge (u, v) the
+    neighbours w > v of v are looked up among the neighbours of u."""
+    indptr = np.asarray(indptr).astype(np.int64)
+    cols = np.asarray(indices).astype(np.int64)
+    rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(indptr))
+    up = np.flatnonzero(cols > rows)
+    eu, ev = rows[up], cols[up]
+    m = up.shape[0]
+    key = eu * n + ev                                                    # ascending: row order, ascending rows
+    eid = np.full(cols.shape[0], -1, dtype=np.int64)
+    eid[up] = np.arange(m, dtype=np.int64)
+    low = np.flatnonzero(cols < rows)
+    eid[low] = np.searchsorted(key, cols[low] * n + rows[low])
+    first = np.searchsorted(eu, np.arange(n, dtype=np.int64))           # a vertex's edges to larger neighbours: first, count
+    count = np.bincount(eu, minlength=n)
+    lens = count[ev]
+    ends = np.cumsum(lens)
+    found, lo = [], 0
+    while lo < m:
+        hi = max(lo + 1, int(np.searchsorted(ends, (ends[lo - 1] if lo else 0) + chunk, side="right")))
+        ln = lens[lo:hi]
+        total = int(ln.sum())
+        if total:
+            e = np.repeat(np.arange(lo, hi, dtype=np.int64), ln)
+            vw = np.repeat(first[ev[lo:hi]] - (np.cumsum(ln) - ln), ln) + np.arange(total, dtype=np.int64)    # the edge (v, w)
+            want = eu[e] * n + ev[vw]
+            uw = np.minimum(np.searchsorted(key, want), m - 1)
+            hit = key[uw] == want
+            found.append(np.stack([e[hit], vw[hit], uw[hit]], axis=1))
+        lo = hi
+    tri = np.concatenate(found) if found else np.zeros((0, 3), dtype=np.int64)
+    return eid, eu, ev, tri
+
+
+def _truss_numbers_of(m, tri):
+    """Truss numbers of the m edges of a graph whose triangles are tri (int64[T, 3], edge numbers): a peel by whole SETS in numpy
+    (kept apart from the device's queue: validate_truss checks one with the other) -> (truss as int64[m], support as int64[m],
+    levels, sub_rounds).  At level l every edge still there whose count of remaining triangles is l is removed at once and gets
+    truss l + 2; every triangle that loses an edge takes one from the count of its edges that stay, but never below l; those
+    that arrive at l form the next set of the level.  When nobody qualifies l jumps to the smallest remaining count.  levels =
+    levels that removed an edge; sub_rounds = the sets removed."""
+    T = tri.shape[0]
+    support = np.bincount(tri.ravel(), minlength=m).astype(np.int64)
+    order = np.argsort(tri.ravel(), kind="stable")                       # the triangles of every edge
+    of_edge = order // 3
+    begin = np.concatenate([[0], np.cumsum(support)])
+    S = support.copy()
+    there = np.ones(m, dtype=bool)
+    whole = np.ones(T, dtype=bool)
+    truss = np.zeros(m, dtype=np.int64)
+    left, l, levels, sub_rounds = m, 0, 0, 0
+    while left:
+        cur = np.flatnonzero(there & (S == l))
+        if cur.size == 0:
+            l = int(S[there].min())
+            continue
+        levels += 1
+        while cur.size:
+            sub_rounds += 1
+            there[cur] = False
+            truss[cur] = l + 2
+            left -= cur.size
+            lens = support[cur]
+            total = int(lens.sum())
+            if total == 0 or left == 0:
+                break
+            at = np.repeat(begin[cur] - (np.cumsum(lens) - lens), lens) + np.arange(total, dtype=np.int64)
+            t = np.unique(of_edge[at])
+            t = t[whole[t]]
+            whole[t] = False
+            stay = tri[t].ravel()
+            stay = stay[there[stay]]
+            S = S - np.bincount(stay, minlength=m)
+            hit = np.unique(stay)
+            S[hit] = np.maximum(S[hit], l)
+            cur = hit[S[hit] == l]
+    return truss, support, levels, sub_rounds
+
+
+def validate_truss(csr, truss, peel=True):
+    """Host-side check (numpy) that `truss` are the truss numbers of the undirected simple graph of `csr` -- an edge {u, v} iff
+    u != v and a stored non-zero entry A[v, u] or A[u, v] exists; duplicates, the diagonal, zero values and direction are
+    ignored -- one value per entry of io.symmetrize_simple(csr)[0], as KTruss.run() returns them.  Raises ValueError naming the
+    first offending entry and the rule; returns the largest truss number (0 for a graph without edges).  The rules:
+      1. both entries of an edge carry one value, which is at least 2, and every edge e lies in at least truss[e] - 2 triangles
+         whose other two edges have truss >= truss[e] (the edges of truss >= k then hold together as a k-truss, so no value is
+         too HIGH);
+      2. the array equals an independent host computation, a peel by whole sets over the list of triangles (what is left to
+         refute after rule 1 is a value that is too LOW); peel=False skips this rule."""
+    sym, _ = io.symmetrize_simple(csr)
+    t = np.asarray(truss)
+    if t.ndim != 1 or t.shape[0] != sym.nnz:
+        raise ValueError("validate_truss: %d truss numbers for the %d entries of the symmetric matrix" % (t.shape[0] if t.ndim == 1 else -1, sym.nnz))
+    if sym.nnz == 0:
+        return 0
+    t = t.astype(np.int64)
+    n = sym.num_rows
+    eid, eu, ev, tri = _edges_and_triangles_of(sym.adj_indptr, sym.adj_indices, n)
+    m = eu.shape[0]
+    rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(sym.adj_indptr.astype(np.int64)))
+    cols = sym.adj_indices.astype(np.int64)
+
+    def first(bad):
+        return int(np.flatnonzero(bad)[0])
+
+    per_edge = np.zeros(m, dtype=np.int64)
+    per_edge[eid[cols > rows]] = t[cols > rows]
+    if np.any(per_edge[eid] != t):
+        j = first(per_edge[eid] != t)
+        raise ValueError("validate_truss: entry %d (%d, %d) is given truss %d, its mirror entry %d (rule 1)"
+                         % (j, rows[j], cols[j], t[j], per_edge[eid[j]]))
+    if np.any(t < 2):
+        j = first(t < 2)
+        raise ValueError("validate_truss: entry %d (%d, %d) is given truss %d, an edge has at least 2 (rule 1)" % (j, rows[j], cols[j], t[j]))
+    floor = per_edge[tri].min(axis=1) if tri.shape[0] else np.zeros(0, dtype=np.int64)   # a triangle serves the edges up to its weakest
+    held = np.zeros(m, dtype=np.int64)
+    for c in range(3):
+        np.add.at(held, tri[:, c], floor >= per_edge[tri[:, c]])
+    if np.any(held < per_edge - 2):
+        e = first(held < per_edge - 2)
+        j = first(eid == e)
+        raise ValueError("validate_truss: entry %d (%d, %d) is given truss %d, but only %d of its triangles have two other edges that high "
+                         "(rule 1)" % (j, eu[e], ev[e], per_edge[e], held[e]))
+    own = _truss_numbers_of(m, tri)[0] if peel else per_edge
+    if np.any(own != per_edge):
+        e = first(own != per_edge)
+        j = first(eid == e)
+        raise ValueError("validate_truss: entry %d (%d, %d) is given truss %d, its truss number is %d (rule 2)"
+                         % (j, eu[e], ev[e], per_edge[e], own[e]))
+    return int(per_edge.max())
+
+
 def _pattern_as_scipy(csr, n):
     """the entries of a CSRMatrix as an n x n scipy matrix of f64 ones (the matrix may have fewer rows and columns)"""
     import scipy.sparse as sp
@@ -1422,6 +1557,51 @@ class KCore(_PatternApp):
         mask = self.core_ >= k
         mask[self.n_real_:] = False
         return mask
+
+
+class KTruss(_PatternApp):
+    """k-truss decomposition: gl_truss, the edge-wise counterpart of KCore.  The matrix is read as an undirected
+    simple graph -- duplicates, the diagonal, zero-valued entries and direction are ignored, as in KCore -- and stored in both
+    directions by the host (io.symmetrize_simple); that matrix is kept as graph_, and every result has one word per ENTRY of it,
+    aligned with graph_.adj_indices: both entries of an edge carry the same value."""
+    _no_shards_ = "gl_truss reads row u for every column u of a row, so every rank would need the whole symmetric matrix"
+    degrees_ = graph_ = truss_ = support_ = max_truss_ = levels_ = sub_rounds_ = launches_ = None
+    num_edges_ = num_triangles_ = truss_sizes_ = vertex_truss_ = None
+
+    def _prepare(self, csr):
+        csr, self.degrees_ = io.symmetrize_simple(csr)
+        self.graph_ = csr
+        self.truss_ = None
+        return csr
+
+    def run(self, support=False):
+        """-> uint32[graph_.nnz]: truss[j] = the truss number of the edge of entry j (at least 2).  Leaves truss_, support_
+        (uint32[graph_.nnz], the triangles through every entry's edge, or None without support=True), max_truss_ (0 for a graph
+        without edges), levels_ (distinct truss numbers), sub_rounds_, launches_, num_edges_, num_triangles_, truss_sizes_[k] =
+        edges with truss >= k, k = 0 .. max_truss_, and vertex_truss_ (uint32[n_]: the largest truss number among a vertex's
+        edges, 0 if it has none).  The call waits for the device."""
+        self._require_sent()
+        B, n, nnz = self.backend, self.n_, self.graph_.nnz
+        out = B.alloc(max(1, 2 * nnz if support else nnz), np.float32)   # (32-bit words: the truss numbers, then the supports)
+        stats = self.SpMV_.truss(B.view(out, 0, max(1, nnz), 4), B.view(out, nnz, nnz, 4) if support and nnz else None)
+        B.sync()
+        got = B.download(out, np.uint32, 2 * nnz if support else nnz) if nnz else np.zeros(0, np.uint32)
+        self.truss_ = got[:nnz]
+        self.support_ = got[nnz:] if support else None
+        self.max_truss_, self.levels_, self.sub_rounds_, self.launches_, self.num_edges_, self.num_triangles_ = stats
+        rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(self.graph_.adj_indptr.astype(np.int64)))
+        once = self.graph_.adj_indices.astype(np.int64) > rows
+        counts = np.bincount(self.truss_[once], minlength=self.max_truss_ + 1)
+        self.truss_sizes_ = np.cumsum(counts[::-1])[::-1].astype(np.int64)
+        self.vertex_truss_ = np.zeros(n, dtype=np.uint32)
+        np.maximum.at(self.vertex_truss_, rows, self.truss_)
+        return self.truss_
+
+    def k_truss(self, k):
+        """-> bool[graph_.nnz]: the entries of the k-truss of the last run (truss number >= k)"""
+        if self.truss_ is None:
+            raise RuntimeError("KTruss.k_truss(): run() first")
+        return self.truss_ >= k
 
 
 class GraphColoring(_PatternApp):

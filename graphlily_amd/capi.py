@@ -54,6 +54,9 @@ EXPORTS = [
 # every symbol include/graphlily_hip_ext.h declares: extensions to the ABI are listed here from now on (EXPORTS and its header are
 # pinned by the suite as they are; tests and build() check this list in the same way)
 EXT_EXPORTS = ["gl_color"]
+# ... and one header per extension since (EXT_EXPORTS is pinned as well by now): header under include/ -> the symbols it declares;
+# tests check their own entry, build() checks every list against the library
+EXT_HEADERS = {"graphlily_hip_ext.h": EXT_EXPORTS, "graphlily_hip_truss.h": ["gl_truss"]}
 
 
 class GraphLilyError(RuntimeError):
@@ -121,6 +124,7 @@ def lib():
         "gl_tc_count": [vp, vp, vp],
         "gl_kcore": [vp, vp, vp, P(u32)],
         "gl_color": [vp, vp, vp, P(u64)],
+        "gl_truss": [vp, vp, vp, P(u64)],
         "gl_bc_accumulate": [vp, vp, vp, vp, ctypes.c_double, i32, vp, P(u32)],
         "gl_spmv_run": [vp, vp, vp, vp, i32, f32, i32],
         "gl_prof_begin": [u32, u32], "gl_prof_end": [P(ctypes.c_double), P(u32)], "gl_span_begin": [], "gl_span_end": [P(ctypes.c_double)],
@@ -481,6 +485,18 @@ class SpMVPlan:
         garbage = 0xdeadbeefdeadbeef
         stats = (ctypes.c_uint64 * 4)(garbage, garbage, garbage, garbage)
         check(lib().gl_color(ctypes.c_void_p(self.handle), _p(prio), _p(color), stats))
+        return tuple(int(x) for x in stats)
+
+    def truss(self, truss, support=None):
+        """gl_truss: the truss number of every edge of this plan's graph into `truss` and, optionally, its triangle count into
+        `support` (nnz device words each, entry j = word j of the row copy; both entries of an edge carry the same value, an
+        entry (v, v) gets 0) -> (max_truss, levels = distinct truss values, sub-rounds, launches enqueued, edges, triangles).
+        The plan is square, whole, its rows strictly ascending sets, its pattern symmetric (io.symmetrize_simple prepares
+        it).  Both arrays are fully written by the call, which SYNCHRONISES (it reads a control record back between batches of
+        launches); a plan without entries writes nothing."""
+        garbage = 0xdeadbeefdeadbeef
+        stats = (ctypes.c_uint64 * 6)(*([garbage] * 6))
+        check(lib().gl_truss(ctypes.c_void_p(self.handle), _p(truss), _p(support), stats))
         return tuple(int(x) for x in stats)
 
     def bc_accumulate(self, plan_out, level, bc, scale=1.0, accumulate=False, sigma=None, stats=True):

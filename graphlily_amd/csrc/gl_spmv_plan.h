@@ -253,6 +253,12 @@ struct gl_spmv_plan_s {
     // gl_color (gl_color.hip): the pass's scratch, allocated by the first call -- 256 bytes of control record + num_rows words
     // of queue
     unsigned char *d_color_scratch = nullptr;
+    // gl_truss (gl_truss.hip), set up by the first call: 256 bytes of control record, num_rows + 1 first edge numbers of the
+    // rows, the edge number of each of the nnz entries, then five arrays of nnz / 2 words -- every edge's smaller end and its
+    // entry (these are the cached edge numbering), its support word, the queue and the positions in it -- and the number of
+    // edges (-1: not numbered yet)
+    unsigned char *d_truss_scratch = nullptr;
+    int64_t truss_edges = -1;
     // gl_bc_accumulate (gl_bc.hip), as plan_in, set up by the first call: the pass's scratch -- 256 bytes of control words, two
     // arrays of num_rows + 2 level offsets, num_rows words of queue, num_rows doubles each of sigma and coef -- the page-locked
     // room the offsets are read back to, and the verdict on the last plan_out that was not this plan itself: is it the

@@ -308,6 +308,19 @@ class SpMVModule(BaseModule):
         self._finish(color_buf)
         return stats
 
+    def truss(self, truss_buf, support_buf=None):
+        """Extension (gl_truss): the truss number of every edge of this module's matrix, read as a graph -- rows as strictly
+        ascending sets N(v), the pattern symmetric -- into `truss_buf` and, optionally, the triangles through it into
+        `support_buf` (get_nnz() words each, aligned with the matrix's entries) -> (max_truss, levels, sub-rounds, launches,
+        edges, triangles).  The call synchronises.  Raises GraphLilyError (GL_ERR_UNSUPPORTED) when the plan keeps no row copy
+        (only the (||,&&) layout does), is not square, is a row shard, its rows are no such sets or its pattern is not symmetric
+        (io.symmetrize_simple prepares it)."""
+        if self.plan_ is None:
+            _fatal("SpMVModule.truss: send_matrix_host_to_device first")
+        stats = self.plan_.truss(truss_buf, support_buf)
+        self._finish(truss_buf, support_buf)
+        return stats
+
     def bc_accumulate(self, out_module, level_buf, bc_buf, scale=1.0, accumulate=False, sigma_buf=None, stats=True):
         """Extension (gl_bc_accumulate): adds scale x Brandes' dependency of the search whose levels are in `level_buf`
         (get_num_rows() floats) to `bc_buf` (as many doubles; accumulate=False: overwrites it).  This module's matrix is the

@@ -11,6 +11,7 @@
 
 #include "graphlily/global.h"
 #include "graphlily_hip_ext.h"
+#include "graphlily_hip_truss.h"
 #include "graphlily/io/data_formatter.h"
 #include "graphlily/io/data_loader.h"
 #include "graphlily/module/base_module.h"
@@ -208,6 +209,16 @@ public:
     void color(DeviceBuffer color, const uint32_t *prio = nullptr, uint64_t *stats = nullptr) {
         barrier_();
         GRAPHLILY_CHECK(gl_color(plan_, prio, (uint32_t *)color.ptr(), stats));
+        finish_();
+    }
+    // extension (gl_truss, graphlily_hip_truss.h): the truss number of every edge of this module's matrix, read as a graph -- rows
+    // as strictly ascending sets N(v), the pattern symmetric (graphlily::io::util_symmetrize_simple prepares it) -- into `truss`
+    // and, optionally, the triangles through it into `support` (get_nnz() device words each, aligned with the matrix's entries;
+    // an entry (v, v) gets 0); stats (optional, 6 host words) receives {max_truss, levels, sub_rounds, launches, edges,
+    // triangles}.  Only the (||,&&) layout keeps the rows this pass walks.  The call synchronises.
+    void truss(DeviceBuffer truss, uint32_t *support = nullptr, uint64_t *stats = nullptr) {
+        barrier_();
+        GRAPHLILY_CHECK(gl_truss(plan_, (uint32_t *)truss.ptr(), support, stats));
         finish_();
     }
     // extension (gl_bc_accumulate): adds scale x Brandes' dependency of the search whose levels are in `level` (get_num_rows()

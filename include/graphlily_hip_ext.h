@@ -1,10 +1,11 @@
 /*
  * graphlily_hip_ext.h -- extensions to the C ABI of libgraphlily_hip.so (graphlily_hip.h).
  *
- * EXTENSIONS TO THE ABI GO HERE FROM NOW ON.  graphlily_hip.h is the drop-in boundary of the reference's operator API plus the
- * graph kernels that grew next to it, and its list of entry points is pinned by tests that stay as they are (the CPU suite
- * compares it with capi.EXPORTS, name by name and by count).  A new entry point therefore gets its declaration here and its name
- * in capi.EXT_EXPORTS, which the suite and the build check against this header and against the library in the same way.  The
+ * THE FIRST EXTENSION HEADER; LATER EXTENSIONS GET A HEADER OF THEIR OWN (graphlily_hip_truss.h is the next; capi.EXT_HEADERS
+ * lists them all).  graphlily_hip.h is the drop-in boundary of the reference's operator API plus the graph kernels that grew next
+ * to it, and its list of entry points is pinned by tests that stay as they are (the CPU suite compares it with capi.EXPORTS, name
+ * by name and by count); this header's list, capi.EXT_EXPORTS, has been pinned in the same way since.  The colouring entry point
+ * below is declared here and named in capi.EXT_EXPORTS, which the suite and the build check against this header and the library.  The
  * conventions are those of graphlily_hip.h: a gl_status is returned, gl_last_error gives the message, `d_` parameters are device
  * pointers, `h_` parameters host pointers, work goes to the library's current stream.
  */
