@@ -583,6 +583,94 @@ def validate_truss(csr, truss, peel=True):
     return int(per_edge.max())
 
 
+def _edge_keys(weights):
+    """key(w) of f32 weights as uint32: the monotone map b ^ (b >> 31 ? 0xffffffff : 0x80000000) of the bits b -- gl_msf's order"""
+    b = np.ascontiguousarray(weights, dtype=np.float32).view(np.uint32)
+    return b ^ np.where(b >> 31 != 0, np.uint32(0xffffffff), np.uint32(0x80000000))
+
+
+def _kruskal_of(sym):
+    """Kruskal's algorithm on a symmetric CSRMatrix with weights in adj_data, the edges taken in gl_msf's order (key(w), lo, hi):
+    the entries above the diagonal sorted by (key, entry number), a union-find with path halving on the host (kept apart from the
+    device's Boruvka rounds: validate_spanning_forest checks one with the other) -> bool[nnz], both entries of a forest edge
+    marked.  Only the weights of entries above the diagonal are read."""
+    n = sym.num_rows
+    indptr = sym.adj_indptr.astype(np.int64)
+    rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(indptr))
+    cols = sym.adj_indices.astype(np.int64)
+    up = np.flatnonzero(cols > rows)
+    up = up[np.argsort(_edge_keys(sym.adj_data[up]), kind="stable")]        # (stable: ties stay in entry order = (lo, hi) order)
+    parent = list(range(n))
+    taken = []
+    for j, u, v in zip(up.tolist(), rows[up].tolist(), cols[up].tolist()):
+        while parent[u] != u:
+            parent[u] = parent[parent[u]]
+            u = parent[u]
+        while parent[v] != v:
+            parent[v] = parent[parent[v]]
+            v = parent[v]
+        if u != v:
+            parent[max(u, v)] = min(u, v)
+            taken.append(j)
+    mask = np.zeros(sym.nnz, dtype=bool)
+    taken = np.asarray(taken, dtype=np.int64)
+    mask[taken] = True
+    lo, hi = rows[taken], cols[taken]                                       # the mirror entries: (hi, lo) in row hi
+    entry_key = rows * n + cols                                             # ascending: rows are sorted sets
+    mask[np.searchsorted(entry_key, hi * n + lo)] = True
+    return mask
+
+
+def validate_spanning_forest(csr, in_forest, weighted=True):
+    """Host-side check (numpy) that `in_forest` marks THE minimum spanning forest of the undirected weighted graph of `csr` -- as
+    io.symmetrize_weighted(csr, weighted) reads it -- one word per entry of that symmetric matrix, as MinimumSpanningForest.run()
+    returns them.  Raises ValueError naming the first offending entry and the rule; returns the number of forest edges.  The rules:
+      1. both entries of an edge carry the same mark;
+      2. the marked edges are acyclic and span every component: joined by marked edges alone the vertices fall into exactly
+         n - edges classes (no cycle), and these are the components of the graph (an independent numpy pass finds them);
+      3. the forest is minimal, and the unique one under the order (key(w), lo, hi): it equals, as a whole set, what a host
+         Kruskal taking the edges in that order returns (by the cycle property a spanning forest that differs from it holds an
+         edge that is the largest of a cycle)."""
+    sym, _ = io.symmetrize_weighted(csr, weighted)
+    f = np.asarray(in_forest)
+    if f.ndim != 1 or f.shape[0] != sym.nnz:
+        raise ValueError("validate_spanning_forest: %d marks for the %d entries of the symmetric matrix" % (f.shape[0] if f.ndim == 1 else -1, sym.nnz))
+    n = sym.num_rows
+    f = f != 0
+    indptr = sym.adj_indptr.astype(np.int64)
+    rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(indptr))
+    cols = sym.adj_indices.astype(np.int64)
+
+    def first(bad):
+        return int(np.flatnonzero(bad)[0])
+
+    mirror = np.searchsorted(rows * n + cols, cols * n + rows)               # (the matrix has no diagonal: every entry has one)
+    if np.any(f != f[mirror]):
+        j = first(f != f[mirror])
+        raise ValueError("validate_spanning_forest: entry %d (%d, %d) is marked %d, its mirror entry %d (rule 1)"
+                         % (j, rows[j], cols[j], f[j], f[mirror[j]]))
+    edges = int(np.count_nonzero(f & (cols > rows)))
+    want = _components_of(sym.adj_indptr, sym.adj_indices, None, n)
+    kept = np.flatnonzero(f)
+    kept_indptr = np.concatenate([[0], np.cumsum(np.bincount(rows[kept], minlength=n))])
+    got = _components_of(kept_indptr, cols[kept], None, n)
+    classes, components = int(np.count_nonzero(got == np.arange(n))), int(np.count_nonzero(want == np.arange(n)))
+    if edges + classes != n:
+        raise ValueError("validate_spanning_forest: the %d marked edges join the %d vertices into %d classes: %d of them close a cycle (rule 2)"
+                         % (edges, n, classes, edges + classes - n))
+    if np.any(got != want):
+        v = first(got != want)
+        raise ValueError("validate_spanning_forest: vertex %d is joined to %d by the graph's edges and not by the marked ones: the forest "
+                         "has %d edges and the graph %d components on %d vertices, an edge is missing (rule 2)" % (v, want[v], edges, components, n))
+    own = _kruskal_of(sym)
+    if np.any(own != f):
+        j = first(own != f)
+        raise ValueError("validate_spanning_forest: entry %d (%d, %d) of weight %r is %s, and the minimum spanning forest under the order "
+                         "(key(w), lo, hi) %s it (rule 3)" % (j, rows[j], cols[j], float(sym.adj_data[j]), "marked" if f[j] else "not marked",
+                                                              "leaves out" if f[j] else "holds"))
+    return edges
+
+
 def _pattern_as_scipy(csr, n):
     """the entries of a CSRMatrix as an n x n scipy matrix of f64 ones (the matrix may have fewer rows and columns)"""
     import scipy.sparse as sp
@@ -1602,6 +1690,62 @@ class KTruss(_PatternApp):
         if self.truss_ is None:
             raise RuntimeError("KTruss.k_truss(): run() first")
         return self.truss_ >= k
+
+
+class MinimumSpanningForest(_PatternApp):
+    """Minimum spanning forest: gl_msf, Boruvka's algorithm over the rows with a weight per entry.  The matrix is
+    read as an undirected weighted graph and stored in both directions by the host (io.symmetrize_weighted: the diagonal is
+    dropped, every other stored entry is an edge -- a stored 0 included --, an edge stored more than once gets its smallest
+    value, -0.0 becomes +0.0, NaN is refused; weighted=False: zero values are no edges and every weight is 1).  That matrix is
+    kept as graph_, with the weights in adj_data; an all-ones copy of it is planned (the row copy would store a zero value as
+    no entry).  Every result has one word per ENTRY of graph_, aligned with graph_.adj_indices.  Edges are ordered by (key(w),
+    lo, hi), a strict total order, so the forest is unique: the one Kruskal's algorithm returns taking the edges in that order."""
+    _no_shards_ = ("gl_msf reads the component of every column of a row and the rows of both ends of a chosen edge, so every rank "
+                   "would need the whole symmetric matrix and the whole forest")
+    degrees_ = graph_ = in_forest_ = edges_ = weights_ = total_weight_ = num_edges_ = num_components_ = labels_ = None
+    rounds_ = launches_ = weight_buf_ = None
+    weighted_ = True
+
+    def load_and_format_matrix(self, csr_float_npz_path, skip_empty_rows=True, weighted=True):
+        self.weighted_ = bool(weighted)
+        _PatternApp.load_and_format_matrix(self, csr_float_npz_path, skip_empty_rows)
+
+    def _prepare(self, csr):
+        self.graph_, self.degrees_ = io.symmetrize_weighted(csr, self.weighted_)
+        self.in_forest_ = self.weight_buf_ = None
+        g = self.graph_
+        return io.CSRMatrix(g.num_rows, g.num_cols, np.ones(g.nnz, dtype=np.float32), g.adj_indices, g.adj_indptr)
+
+    def send_matrix_host_to_device(self):
+        _PatternApp.send_matrix_host_to_device(self)
+        self.weight_buf_ = self.backend.alloc(max(1, self.graph_.nnz), np.float32)
+        if self.graph_.nnz:
+            self.backend.upload(self.weight_buf_, self.graph_.adj_data)
+
+    def run(self, labels=False):
+        """-> bool[graph_.nnz]: in_forest[j] = the edge of entry j is in the minimum spanning forest.  Leaves in_forest_, edges_
+        (int64[m, 2]: (lo, hi) of every forest edge, ascending), weights_ (float32[m], aligned with edges_), total_weight_ (the
+        f64 sum of weights_ in that order, added up on the host), num_edges_, num_components_ (over the n_real_ real vertices:
+        padding vertices are singletons), labels_ (uint32[n_]: the smallest vertex of every vertex's component, or None without
+        labels=True), rounds_ (Boruvka rounds in which a component chose an edge) and launches_.  The call waits for the
+        device."""
+        self._require_sent()
+        B, n, nnz = self.backend, self.n_, self.graph_.nnz
+        room = max(1, nnz)
+        out = B.alloc(room + (n if labels else 0), np.float32)          # (32-bit words: the forest words, then the labels)
+        stats = self.SpMV_.msf(self.weight_buf_, B.view(out, 0, room, 4), B.view(out, room, n, 4) if labels and n else None)
+        B.sync()
+        got = B.download(out, np.uint32, room + (n if labels else 0))
+        self.in_forest_ = got[:nnz] != 0
+        self.labels_ = got[room:] if labels else None
+        self.num_edges_, components, self.rounds_, self.launches_ = stats
+        self.num_components_ = components - (n - self.n_real_)
+        rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(self.graph_.adj_indptr.astype(np.int64)))
+        once = np.flatnonzero(self.in_forest_ & (self.graph_.adj_indices.astype(np.int64) > rows))
+        self.edges_ = np.stack([rows[once], self.graph_.adj_indices[once].astype(np.int64)], axis=1)
+        self.weights_ = self.graph_.adj_data[once]
+        self.total_weight_ = float(np.cumsum(self.weights_, dtype=np.float64)[-1]) if once.size else 0.0     # (cumsum: one by one, in order)
+        return self.in_forest_
 
 
 class GraphColoring(_PatternApp):

@@ -56,7 +56,7 @@ EXPORTS = [
 EXT_EXPORTS = ["gl_color"]
 # ... and one header per extension since (EXT_EXPORTS is pinned as well by now): header under include/ -> the symbols it declares;
 # tests check their own entry, build() checks every list against the library
-EXT_HEADERS = {"graphlily_hip_ext.h": EXT_EXPORTS, "graphlily_hip_truss.h": ["gl_truss"]}
+EXT_HEADERS = {"graphlily_hip_ext.h": EXT_EXPORTS, "graphlily_hip_truss.h": ["gl_truss"], "graphlily_hip_msf.h": ["gl_msf"]}
 
 
 class GraphLilyError(RuntimeError):
@@ -125,6 +125,7 @@ def lib():
         "gl_kcore": [vp, vp, vp, P(u32)],
         "gl_color": [vp, vp, vp, P(u64)],
         "gl_truss": [vp, vp, vp, P(u64)],
+        "gl_msf": [vp, vp, vp, vp, P(u64)],
         "gl_bc_accumulate": [vp, vp, vp, vp, ctypes.c_double, i32, vp, P(u32)],
         "gl_spmv_run": [vp, vp, vp, vp, i32, f32, i32],
         "gl_prof_begin": [u32, u32], "gl_prof_end": [P(ctypes.c_double), P(u32)], "gl_span_begin": [], "gl_span_end": [P(ctypes.c_double)],
@@ -497,6 +498,21 @@ class SpMVPlan:
         garbage = 0xdeadbeefdeadbeef
         stats = (ctypes.c_uint64 * 6)(*([garbage] * 6))
         check(lib().gl_truss(ctypes.c_void_p(self.handle), _p(truss), _p(support), stats))
+        return tuple(int(x) for x in stats)
+
+    def msf(self, weight, in_forest, labels=None):
+        """gl_msf: the minimum spanning forest of this plan's graph under the f32 weights `weight` (nnz device words, entry j =
+        word j of the row copy; an edge's weight is the word of its entry ABOVE the diagonal, the mirror entry's word is never
+        read) into `in_forest` (nnz device words: 1 if the entry's edge is in the forest, both entries of an edge alike, an
+        entry (v, v) gets 0) and, optionally, the smallest vertex of every vertex's component into `labels` (num_cols words,
+        bit-equal to cc_labels) -> (forest edges, components, rounds, launches enqueued).  Edges are ordered by (key(w), lo, hi),
+        a strict total order, so the forest is unique: Kruskal's in that order.  The plan is square, whole, its rows strictly
+        ascending sets, its pattern symmetric (io.symmetrize_weighted prepares it; plan all-ones values).  Both arrays are fully
+        written by the call, which SYNCHRONISES (it reads a control record back between batches of launches); a plan without
+        entries writes no forest words."""
+        garbage = 0xdeadbeefdeadbeef
+        stats = (ctypes.c_uint64 * 4)(*([garbage] * 4))
+        check(lib().gl_msf(ctypes.c_void_p(self.handle), _p(weight), _p(in_forest), _p(labels), stats))
         return tuple(int(x) for x in stats)
 
     def bc_accumulate(self, plan_out, level, bc, scale=1.0, accumulate=False, sigma=None, stats=True):

@@ -1,5 +1,6 @@
 // The plain CSR row copy that a GL_PLAN_BOOLEAN plan keeps (gl_spmv_plan.h: d_csr_indptr / d_csr_indices / csr_nz_base), as the
-// graph kernels that walk it see it -- gl_bfs_parents, gl_cc, gl_tc, gl_kcore, gl_color, gl_truss, gl_bc: what a caller may require of it, the
+// graph kernels that walk it see it -- gl_bfs_parents, gl_cc, gl_tc, gl_kcore, gl_color, gl_truss, gl_msf (which also takes a
+// value per entry of the copy from its caller), gl_bc: what a caller may require of it, the
 // verdicts about it that the plan caches, and the few helpers every such kernel wants.  gl_rows.hip holds the check kernels.
 #ifndef GL_ROWS_H_
 #define GL_ROWS_H_

@@ -259,6 +259,10 @@ struct gl_spmv_plan_s {
     // edges (-1: not numbered yet)
     unsigned char *d_truss_scratch = nullptr;
     int64_t truss_edges = -1;
+    // gl_msf (gl_msf.hip): the pass's scratch, allocated by the first call -- 256 bytes of control record, a 64-bit best-edge word
+    // per column, then five arrays of num_cols words: two copies of the components, the rows' first entries above the diagonal
+    // and the list of forest edges {entry, smaller end}
+    unsigned char *d_msf_scratch = nullptr;
     // gl_bc_accumulate (gl_bc.hip), as plan_in, set up by the first call: the pass's scratch -- 256 bytes of control words, two
     // arrays of num_rows + 2 level offsets, num_rows words of queue, num_rows doubles each of sigma and coef -- the page-locked
     // room the offsets are read back to, and the verdict on the last plan_out that was not this plan itself: is it the

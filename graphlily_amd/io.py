@@ -9,6 +9,7 @@ Mirrors (names, argument meaning, in-place behaviour):
   util_normalize_csr_matrix_by_outdegree         io/data_formatter.h:36-51
   triangle_orient                                io/data_formatter.h (util_triangle_orient: an extension, no reference counterpart)
   symmetrize_simple                              io/data_formatter.h (util_symmetrize_simple: an extension, no reference counterpart)
+  symmetrize_weighted                            io/data_formatter.h (util_symmetrize_weighted: an extension, no reference counterpart)
   simple_pattern                                 io/data_formatter.h (util_simple_pattern: an extension, no reference counterpart)
 The FPGA-only formatters (csr2cpsr, formatCSC: io/data_formatter.h:54-721) have no counterpart here:
 the device layout is produced inside gl_spmv_plan_create / gl_spmspv_plan_create.
@@ -125,6 +126,47 @@ def symmetrize_simple(csr_matrix):
     if int(out_indptr[n]) > 0xFFFFFFFF:
         raise ValueError("symmetrize_simple: %d entries do not fit 32-bit offsets" % int(out_indptr[n]))
     sym = CSRMatrix(n, n, np.ones(b.shape[0], dtype=np.float32), b.astype(np.uint32), out_indptr.astype(np.uint32))
+    return sym, deg.astype(np.uint32)
+
+
+def symmetrize_weighted(csr_matrix, weighted=True):
+    """The matrix preparation of MinimumSpanningForest (an extension) -> (symmetric CSRMatrix, degrees as uint32[n]),
+    n = max(num_rows, num_cols): symmetrize_simple's layout with weights.  The diagonal is dropped; every remaining STORED entry
+    is an edge {u, v}, a stored 0 included (weight 0 is a legitimate weight).  An edge stored more than once, or in both
+    directions, gets the SMALLEST of its values, and both entries of the result carry it.  -0.0 becomes +0.0; a NaN raises
+    ValueError naming the first offending entry.  Row v of the result lists the neighbours of v, columns ascending, with the
+    weights in adj_data.  weighted=False is symmetrize_simple's reading: zero values are no edges and every weight is 1.
+    Applied after padding: padding vertices have empty rows."""
+    if not weighted:
+        return symmetrize_simple(csr_matrix)
+    n = max(int(csr_matrix.num_rows), int(csr_matrix.num_cols))
+    indptr = csr_matrix.adj_indptr.astype(np.int64)[:csr_matrix.num_rows + 1]
+    nnz = int(indptr[-1])
+    rows = np.repeat(np.arange(csr_matrix.num_rows, dtype=np.int64), np.diff(indptr))
+    cols = csr_matrix.adj_indices[:nnz].astype(np.int64)
+    w = np.asarray(csr_matrix.adj_data[:nnz], dtype=np.float32)
+    bad = np.isnan(w) & (rows != cols)
+    if np.any(bad):
+        j = int(np.flatnonzero(bad)[0])
+        raise ValueError("symmetrize_weighted: entry %d (%d, %d) is NaN: the order of the edges needs comparable weights" % (j, rows[j], cols[j]))
+    keep = rows != cols
+    rows, cols, w = rows[keep], cols[keep], w[keep] + np.float32(0.0)         # (-0.0 + 0.0 == +0.0)
+    key = np.minimum(rows, cols) * n + np.maximum(rows, cols)
+    order = np.lexsort((w, key))                                              # by edge, the smallest value of each first
+    key, w = key[order], w[order]
+    once = np.ones(key.shape[0], dtype=bool)
+    once[1:] = key[1:] != key[:-1]
+    key, w = key[once], w[once]
+    lo, hi = key // n, key % n
+    a, b, w = np.concatenate([lo, hi]), np.concatenate([hi, lo]), np.concatenate([w, w])
+    order = np.lexsort((b, a))                                                # both directions, sorted by (row, column)
+    a, b, w = a[order], b[order], w[order]
+    deg = np.bincount(a, minlength=n).astype(np.int64)
+    out_indptr = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(deg, out=out_indptr[1:])
+    if int(out_indptr[n]) > 0xFFFFFFFF:
+        raise ValueError("symmetrize_weighted: %d entries do not fit 32-bit offsets" % int(out_indptr[n]))
+    sym = CSRMatrix(n, n, w.astype(np.float32), b.astype(np.uint32), out_indptr.astype(np.uint32))
     return sym, deg.astype(np.uint32)
 
 

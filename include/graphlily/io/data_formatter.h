@@ -114,6 +114,57 @@ CSRMatrix<data_type> util_symmetrize_simple(CSRMatrix<data_type> const &m, std::
     return out;
 }
 
+// The matrix preparation of app::MinimumSpanningForest (an extension): util_symmetrize_simple's layout with weights.  The diagonal
+// is dropped; every remaining STORED entry is an edge {u, v}, a stored 0 included.  An edge stored more than once, or in both
+// directions, gets the SMALLEST of its values, and both entries of the result carry it; -0.0 becomes +0.0; a NaN prints and
+// exits.  weighted = false is util_symmetrize_simple's reading (zero values are no edges, every weight 1).  `degrees` receives the
+// row lengths.  n = max(num_rows, num_cols); apply after padding.
+template <typename data_type>
+CSRMatrix<data_type> util_symmetrize_weighted(CSRMatrix<data_type> const &m, std::vector<uint32_t> &degrees, bool weighted = true) {
+    if (!weighted) return util_symmetrize_simple(m, degrees);
+    const uint64_t n = std::max(m.num_rows, m.num_cols);
+    std::vector<std::pair<uint64_t, data_type>> edge;          // {lo * n + hi, weight}
+    edge.reserve((size_t)m.adj_indptr[m.num_rows]);
+    for (uint32_t v = 0; v < m.num_rows; v++)
+        for (uint32_t i = m.adj_indptr[v]; i < m.adj_indptr[v + 1]; i++) {
+            const uint64_t u = m.adj_indices[i];
+            if (u == v) continue;
+            const data_type w = m.adj_data[i] + data_type(0);   // (-0.0 + 0.0 == +0.0)
+            if (w != w) {
+                printf("util_symmetrize_weighted: entry %u (%u, %u) is NaN: the order of the edges needs comparable weights\n", i, v, (uint32_t)u);
+                exit(EXIT_FAILURE);
+            }
+            edge.push_back(std::make_pair(std::min<uint64_t>(u, v) * n + std::max<uint64_t>(u, v), w));
+        }
+    std::sort(edge.begin(), edge.end());                        // by edge, the smallest value of each first
+    std::vector<std::pair<uint64_t, data_type>> entry;          // {row * n + column, weight}, both directions
+    entry.reserve(2 * edge.size());
+    for (size_t i = 0; i < edge.size(); i++) {
+        if (i != 0 && edge[i].first == edge[i - 1].first) continue;
+        const uint64_t lo = edge[i].first / n, hi = edge[i].first % n;
+        entry.push_back(std::make_pair(lo * n + hi, edge[i].second));
+        entry.push_back(std::make_pair(hi * n + lo, edge[i].second));
+    }
+    std::sort(entry.begin(), entry.end());
+    if (entry.size() > 0xffffffffull) {
+        printf("util_symmetrize_weighted: %zu entries do not fit 32-bit offsets\n", entry.size());
+        exit(EXIT_FAILURE);
+    }
+    degrees.assign(n, 0);
+    CSRMatrix<data_type> out;
+    out.num_rows = out.num_cols = (uint32_t)n;
+    out.adj_indptr.assign(n + 1, 0);
+    out.adj_indices.reserve(entry.size());
+    out.adj_data.reserve(entry.size());
+    for (size_t i = 0; i < entry.size(); i++) {                 // (sorted by (row, column): the columns of a row ascend)
+        degrees[entry[i].first / n]++;
+        out.adj_indices.push_back((uint32_t)(entry[i].first % n));
+        out.adj_data.push_back(entry[i].second);
+    }
+    for (uint64_t v = 0; v < n; v++) out.adj_indptr[v + 1] = out.adj_indptr[v] + degrees[v];
+    return out;
+}
+
 // murmur3's fmix32 of (v + 0x9e3779b9 * (seed + 1)) mod 2^32, all arithmetic mod 2^32: a bijection of the 32-bit words, so the
 // hashes of distinct vertices never tie (io.coloring_hash computes the same word)
 inline uint32_t util_coloring_hash(uint32_t v, uint32_t seed) {

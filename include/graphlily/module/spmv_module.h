@@ -12,6 +12,7 @@
 #include "graphlily/global.h"
 #include "graphlily_hip_ext.h"
 #include "graphlily_hip_truss.h"
+#include "graphlily_hip_msf.h"
 #include "graphlily/io/data_formatter.h"
 #include "graphlily/io/data_loader.h"
 #include "graphlily/module/base_module.h"
@@ -219,6 +220,17 @@ public:
     void truss(DeviceBuffer truss, uint32_t *support = nullptr, uint64_t *stats = nullptr) {
         barrier_();
         GRAPHLILY_CHECK(gl_truss(plan_, (uint32_t *)truss.ptr(), support, stats));
+        finish_();
+    }
+    // extension (gl_msf, graphlily_hip_msf.h): the minimum spanning forest of this module's matrix, read as a graph -- rows as
+    // strictly ascending sets N(v), the pattern symmetric (graphlily::io::util_symmetrize_weighted prepares it) -- under the f32
+    // weights in `weight` (get_nnz() device words aligned with the matrix's entries; only the words of entries above the diagonal
+    // are read), into `in_forest` (as many words: 1 for the entries of forest edges) and, optionally, the components' smallest
+    // vertices into `labels` (get_num_cols() device words); stats (optional, 4 host words) receives {forest edges, components,
+    // rounds, launches}.  Only the (||,&&) layout keeps the rows this pass walks.  The call synchronises.
+    void msf(DeviceBuffer weight, DeviceBuffer in_forest, uint32_t *labels = nullptr, uint64_t *stats = nullptr) {
+        barrier_();
+        GRAPHLILY_CHECK(gl_msf(plan_, (const float *)weight.rptr(), (uint32_t *)in_forest.ptr(), labels, stats));
         finish_();
     }
     // extension (gl_bc_accumulate): adds scale x Brandes' dependency of the search whose levels are in `level` (get_num_rows()
