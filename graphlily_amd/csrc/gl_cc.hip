@@ -17,15 +17,14 @@
 // per step; a row longer than `cut` entries is taken over by the whole wavefront, 256 entries per step with coalesced index
 // loads; shards index through row_begin and csr_nz_base.  For an edge (v, u): find both roots; if they differ,
 // atomicCAS(&parent[hi], hi, lo) with hi = max, lo = min.
-// MEMORY RULES inside the hook launch (gfx950: eight XCDs with private L2s -- a plain store is not seen across them within a
-// launch):
-//   * every access to parent[] is an agent-scope atomic on a global pointer: a relaxed atomic load, an atomic min or a
-//     compare-and-swap; there is no plain load or store of that array;
+// MEMORY RULE: gl_rounds.h.  Inside the hook launch:
+//   * parent[] is atomic-only: a relaxed atomic load, an atomic min or a compare-and-swap; there is no plain load or store of
+//     that array;
 //   * a failed compare-and-swap continues from the value it RETURNED (never a re-read): that value is below hi, so every
 //     retry strictly descends and progress rests on atomic return values alone -- a stale load can at worst name a vertex
 //     that is no longer a root, which the compare-and-swap then refuses;
 //   * path shortening is atomicMin(&parent[x], grandparent) only, which keeps the invariant;
-//   * no spin-waits, no tickets, no hand-offs between workgroups: the only loops are the descending find and the retry.
+//   * the only loops are the descending find and the retry.
 // Finish runs behind a launch boundary (plain loads): pointer doubling, ping-pong between parent and labels with one device
 // "changed" word per round.  A round at least halves the depth, so ceil(log2 n) + 1 rounds suffice; that many are enqueued
 // and a round returns at once when its predecessor changed nothing (both arrays then hold the result).  A thread-per-vertex
@@ -33,34 +32,19 @@
 // one ballot and one atomic add per wavefront.  No call synchronises with the host.
 // NO ROW SKIPPING: entries are stored one way only (row v lists the vertices v is pulled from), so a row skipped because its
 // vertex already sits in the giant component (Afforest's shortcut) may hold the only copy of an edge that leaves it.
-#include "gl_rows.h"
+#include "gl_rounds.h"
 
 namespace gl {
 
 constexpr uint32_t kCcMaxRounds = 36;      // ceil(log2 2^32) + 1, made odd, with room
 constexpr uint32_t kCcCtlBytes = 256;      // one "changed" word per finish round
 
-typedef __attribute__((address_space(1))) uint32_t cc_gu32;
-
-__device__ __forceinline__ uint32_t cc_load(uint32_t *parent, uint32_t x) {
-    return __hip_atomic_load((cc_gu32 *)parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void cc_min(uint32_t *parent, uint32_t x, uint32_t v) {
-    (void)__hip_atomic_fetch_min((cc_gu32 *)parent + x, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// -> the value found at parent[x]: `expect` if the swap took place
-__device__ __forceinline__ uint32_t cc_cas(uint32_t *parent, uint32_t x, uint32_t expect, uint32_t desired) {
-    __hip_atomic_compare_exchange_strong((cc_gu32 *)parent + x, &expect, desired, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                         __HIP_MEMORY_SCOPE_AGENT);
-    return expect;
-}
-
 // the root below x (as far as this thread's loads can tell); every vertex passed on the way is pointed at its grandparent
 __device__ __forceinline__ uint32_t cc_find(uint32_t *parent, uint32_t x) {
-    uint32_t p = cc_load(parent, x);
+    uint32_t p = ga_load(parent + x);
     while (p < x) {
-        const uint32_t g = cc_load(parent, p);
-        if (g < p) cc_min(parent, x, g);
+        const uint32_t g = ga_load(parent + p);
+        if (g < p) ga_min(parent + x, g);
         x = p;
         p = g;
     }
@@ -74,8 +58,8 @@ __device__ __forceinline__ uint32_t cc_unite(uint32_t *parent, uint32_t a, uint3
         b = cc_find(parent, b);
         if (a == b) return a;
         const uint32_t hi = max(a, b), lo = min(a, b);
-        const uint32_t seen = cc_cas(parent, hi, hi, lo);
-        if (seen == hi) return lo;
+        uint32_t seen = hi;
+        if (ga_cas(parent + hi, seen, lo)) return lo;
         // hi was hooked by somebody else meanwhile: go on from where it points now (seen < hi)
         if (a == hi) a = seen;
         else b = seen;

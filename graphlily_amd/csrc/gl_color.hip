@@ -33,19 +33,15 @@
 // across the lanes once per pass: its first pass re-reads the entries the thread had done (colours only), decrements behind
 // them, and collects window 0; a full window is followed by a pass that only reads colours, for the next 256.  The decrements
 // are never repeated.  A hub of d entries whose colour is c costs 1 + c / 256 passes over its row.
-// MEMORY RULES inside a launch, as in gl_kcore.hip and gl_cc.hip: every access to a state word, to tail and to the running
-// maximum is an agent-scope atomic on a global pointer; plain loads and stores only behind a launch boundary (the queue slice and
-// the record were written by earlier launches; queue words written now are read by later ones; prio is never written).  No
-// spin-waits, no tickets, no hand-offs between workgroups.
-// GATING: a launch that finds `done` returns at once, so the host enqueues (round, turn) x color_batch blindly, copies the
-// record to page-locked memory and waits ONCE per batch.  The result does not depend on color_batch.  Every round that runs
-// colours a vertex, so at most n exist and the loop is capped at n + 1 steps.
-#include "gl_rows.h"
+// MEMORY RULE and GATING: gl_rounds.h.  Atomic-only inside a round launch: the state words, the tail and the running maximum
+// (the queue slice and the record were written by earlier launches; queue words written now are read by later ones; prio is
+// never written).  The host enqueues (round, turn) x color_batch; a launch that finds `done` returns at once.  Every round that
+// runs colours a vertex, so at most n exist and the loop is capped at n + 1 steps.
+#include "gl_rounds.h"
 #include "graphlily_hip_ext.h"
 
 namespace gl {
 
-constexpr uint32_t kColCtlBytes = 256;
 // the control record (words); tail and the running maximum sit in the second 128-byte line
 enum : uint32_t { kColLo = 0, kColHi = 1, kColRounds = 2, kColWidest = 3, kColDone = 4, kColRecordWords = 8, kColTail = 32, kColMax = 33,
                   kColReadWords = 34 };
@@ -53,22 +49,6 @@ enum : uint32_t { kColRunning = 0, kColFinished = 1, kColStuck = 2 };
 constexpr uint32_t kColWait = 0x80000000u;       // the top bit of an uncoloured vertex's word
 constexpr uint32_t kColNobody = 0x7fffffffu;     // stands for the word of an entry that is no neighbour: a colour in no window
 constexpr uint32_t kColInitCut = 32;             // entries of a row that init counts in one thread (a guess that was not measured)
-
-typedef __attribute__((address_space(1))) uint32_t col_gu32;
-
-__device__ __forceinline__ uint32_t col_load(uint32_t *p) { return __hip_atomic_load((col_gu32 *)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void col_store(uint32_t *p, uint32_t v) {
-    __hip_atomic_store((col_gu32 *)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ uint32_t col_add(uint32_t *p, uint32_t v) {
-    return __hip_atomic_fetch_add((col_gu32 *)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ uint32_t col_sub(uint32_t *p, uint32_t v) {
-    return __hip_atomic_fetch_sub((col_gu32 *)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void col_max(uint32_t *p, uint32_t v) {
-    (void)__hip_atomic_fetch_max((col_gu32 *)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 // does u go before v?  (u != v)
 __device__ __forceinline__ bool col_before(uint32_t pu, uint32_t u, uint32_t pv, uint32_t v) { return pu > pv || (pu == pv && u < v); }
@@ -117,13 +97,7 @@ __global__ __launch_bounds__(256) void color_init_kernel(const uint32_t *__restr
         }
         if (in) state[v] = kColWait | count;                      // (plain: nobody reads it in this launch)
         const bool hit = in && count == 0u;
-        const unsigned long long m = __ballot(hit);
-        if (m == 0ull) continue;
-        const int leader = __ffsll(m) - 1;
-        uint32_t base = 0;
-        if ((int)lane == leader) base = col_add(ctl + kColTail, (uint32_t)__popcll(m));
-        base = __shfl(base, leader);
-        const uint32_t pos = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+        const uint32_t pos = wave_append(hit, ctl + kColTail, lane);
         if (hit && pos < n) queue[pos] = v;                       // (pos < n: every vertex is appended once)
     }
 }
@@ -136,7 +110,7 @@ struct ColRoundArgs {
 
 // u's last earlier neighbour has just been coloured (the decrement that returned 0x80000001): u joins the queue
 __device__ __forceinline__ void col_append(const ColRoundArgs &a, uint32_t u) {
-    const uint32_t pos = col_add(a.ctl + kColTail, 1u);
+    const uint32_t pos = ga_add(a.ctl + kColTail, 1u);
     if (pos < a.n) a.queue[pos] = u;
 }
 
@@ -177,9 +151,9 @@ __global__ __launch_bounds__(256) void color_round_kernel(ColRoundArgs a) {
                 for (int u = 0; u < 4; u++) c[u] = end - beg > (uint32_t)u ? a.row_idx[beg + u] : 0xffffffffu;   // (no wrap near 2^32 entries)
                 uint32_t w[4], old[4];
 #pragma unroll
-                for (int u = 0; u < 4; u++) w[u] = (c[u] < a.n && c[u] != v) ? col_load(a.state + c[u]) : kColNobody;
+                for (int u = 0; u < 4; u++) w[u] = (c[u] < a.n && c[u] != v) ? ga_load(a.state + c[u]) : kColNobody;
 #pragma unroll
-                for (int u = 0; u < 4; u++) old[u] = (w[u] & kColWait) ? col_sub(a.state + c[u], 1u) : 0u;
+                for (int u = 0; u < 4; u++) old[u] = (w[u] & kColWait) ? ga_sub(a.state + c[u], 1u) : 0u;
 #pragma unroll
                 for (int u = 0; u < 4; u++) {
                     if (old[u] == (kColWait | 1u)) col_append(a, c[u]);
@@ -191,7 +165,7 @@ __global__ __launch_bounds__(256) void color_round_kernel(ColRoundArgs a) {
         // a row finished here has at most 4 cut_steps <= 64 entries, so its colour is at most 64: the mask decides
         if (in && beg >= end) {
             const uint32_t colour = ~used ? (uint32_t)__ffsll(~used) - 1u : 64u;
-            col_store(a.state + v, colour);
+            ga_store(a.state + v, colour);
             top = max(top, colour);
         }
         // rows still unfinished are taken over by the whole wavefront, 256 entries per step (coalesced index loads)
@@ -211,10 +185,10 @@ __global__ __launch_bounds__(256) void color_round_kernel(ColRoundArgs a) {
                     // the four words, then the four decrements, then the appends: each kind in flight together
                     uint32_t w[4], old[4];
 #pragma unroll
-                    for (int u = 0; u < 4; u++) w[u] = (c[u] < a.n && c[u] != row) ? col_load(a.state + c[u]) : kColNobody;
+                    for (int u = 0; u < 4; u++) w[u] = (c[u] < a.n && c[u] != row) ? ga_load(a.state + c[u]) : kColNobody;
 #pragma unroll
                     for (int u = 0; u < 4; u++)
-                        old[u] = ((w[u] & kColWait) && base + 64u * u + lane >= release_from) ? col_sub(a.state + c[u], 1u) : 0u;
+                        old[u] = ((w[u] & kColWait) && base + 64u * u + lane >= release_from) ? ga_sub(a.state + c[u], 1u) : 0u;
 #pragma unroll
                     for (int u = 0; u < 4; u++) {
                         if (old[u] == (kColWait | 1u)) col_append(a, c[u]);
@@ -239,7 +213,7 @@ __global__ __launch_bounds__(256) void color_round_kernel(ColRoundArgs a) {
                 else if (~m3) colour = wbase + 192u + (uint32_t)__ffsll(~m3) - 1u;
                 if (colour != 0xffffffffu) {                      // (uniform: every lane holds the same masks)
                     if ((int)lane == src) {
-                        col_store(a.state + row, colour);
+                        ga_store(a.state + row, colour);
                         top = max(top, colour);
                     }
                     break;
@@ -250,7 +224,7 @@ __global__ __launch_bounds__(256) void color_round_kernel(ColRoundArgs a) {
     // one atomic max per wavefront that coloured somebody above 0
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) top = max(top, (uint32_t)__shfl_xor(top, d));
-    if (lane == 0u && top != 0u) col_max(a.ctl + kColMax, top);
+    if (lane == 0u && top != 0u) ga_max(a.ctl + kColMax, top);
 }
 
 // behind a round (or init): plain loads and stores, a launch of its own
@@ -272,7 +246,7 @@ __global__ void color_turn_kernel(uint32_t *ctl, uint32_t n) {
 static int color_prepare(gl_spmv_plan p, const char *who) {
     const int rc = rows_require(p, kRowsSymmetric, who, "the plan", "io.symmetrize_simple");
     if (rc != GL_OK || p->nnz == 0) return rc;
-    return plan_scratch(p->d_color_scratch, kColCtlBytes + 4u * (size_t)p->num_rows, who, "control record and queue");
+    return plan_scratch(p->d_color_scratch, kRoundsCtlBytes + 4u * (size_t)p->num_rows, who, "control record and queue");
 }
 
 static int color(gl_spmv_plan p, const uint32_t *d_prio, uint32_t *d_color, uint64_t *h_stats, const char *who) {
@@ -303,38 +277,40 @@ static int color(gl_spmv_plan p, const uint32_t *d_prio, uint32_t *d_color, uint
     a.row_ptr = p->d_csr_indptr;
     a.row_idx = p->d_csr_indices;
     a.state = d_color;
-    a.queue = ctl + kColCtlBytes / 4u;
+    a.queue = ctl + kRoundsCtlBytes / 4u;
     a.ctl = ctl;
     a.n = n;
     a.nz_base = p->csr_nz_base;
     a.cut_steps = (uint32_t)std::max<long>(0, std::min<long>(cut, 64)) / 4u;
     const unsigned stream_grid = rows_stream_grid(n);
     const unsigned round_grid = std::max(1u, std::min<unsigned>(cdiv(n, 256u), (unsigned)ctx().num_cus * per_cu));
-    uint32_t *&w = ctx().pinned_word;
-    if (!w) GL_HIP(hipHostMalloc((void **)&w, 64, hipHostMallocDefault));
+    uint32_t *w = nullptr;
+    GL_HIP(staging_words(&w));
     static_assert((kColRecordWords + kColReadWords - kColTail) * 4u <= 64u, "the record fits the page-locked staging words");
-    GL_HIP(hipMemsetAsync(ctl, 0, kColCtlBytes, s));
+    GL_HIP(hipMemsetAsync(ctl, 0, kRoundsCtlBytes, s));
     color_init_kernel<<<stream_grid, 256, 0, s>>>(a.row_ptr, a.row_idx, d_prio, n, a.nz_base, d_color, a.queue, ctl);
     color_turn_kernel<<<1, 64, 0, s>>>(ctl, n);
     GL_LAUNCH_CHECK();
-    uint64_t launches = 2, steps = 0;
-    const uint64_t max_steps = (uint64_t)n + 1ull;                // every round that runs colours a vertex
-    for (;;) {
-        for (uint32_t i = 0; i < batch; i++) {
-            color_round_kernel<<<round_grid, 256, 0, s>>>(a);
-            color_turn_kernel<<<1, 64, 0, s>>>(ctl, n);
-        }
-        GL_LAUNCH_CHECK();
-        launches += 2ull * batch;
-        steps += batch;
-        GL_HIP(hipMemcpyAsync(w, ctl, kColRecordWords * 4u, hipMemcpyDeviceToHost, s));
-        GL_HIP(hipMemcpyAsync(w + kColRecordWords, ctl + kColTail, (kColReadWords - kColTail) * 4u, hipMemcpyDeviceToHost, s));
-        GL_HIP(hipStreamSynchronize(s));
-        if (w[kColDone] == kColFinished) break;
-        if (w[kColDone] == kColStuck || steps >= max_steps)
+    uint64_t launches = 2;
+    rc = rounds_run(
+        batch, (uint64_t)n + 1ull, launches,                      // every round that runs colours a vertex
+        [&] {
+            for (uint32_t i = 0; i < batch; i++) {
+                color_round_kernel<<<round_grid, 256, 0, s>>>(a);
+                color_turn_kernel<<<1, 64, 0, s>>>(ctl, n);
+            }
+            return 2ull * batch;
+        },
+        [&] {
+            const hipError_t e = hipMemcpyAsync(w, ctl, kColRecordWords * 4u, hipMemcpyDeviceToHost, s);
+            return e != hipSuccess ? e : hipMemcpyAsync(w + kColRecordWords, ctl + kColTail, (kColReadWords - kColTail) * 4u, hipMemcpyDeviceToHost, s);
+        },
+        [&] { return w[kColDone] == kColFinished ? kRoundsDone : w[kColDone] == kColStuck ? kRoundsStuck : kRoundsGoOn; },
+        [&](uint64_t steps) {
             return set_error(GL_ERR_HIP, "%s: internal error: not done after %llu steps on %u vertices (%u rounds, %u vertices queued)", who,
                              (unsigned long long)steps, n, w[kColRounds], w[kColRecordWords]);
-    }
+        });
+    if (rc != GL_OK) return rc;
     if (h_stats) {
         h_stats[0] = (uint64_t)w[kColRecordWords + 1u] + 1u;
         h_stats[1] = w[kColRounds];

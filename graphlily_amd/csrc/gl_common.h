@@ -59,7 +59,7 @@ struct Context {
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;  // current stream (own or adopted)
     int num_cus = 256;
-    uint32_t *pinned_word = nullptr;   // page-locked staging word for small device->host control reads
+    uint32_t *pinned_word = nullptr;   // page-locked staging words for small device->host control reads (staging_words below)
     uint32_t *cc_ctl = nullptr;        // gl_cc_finish (gl_cc.hip): one "changed" word per pointer-doubling round, on first use
     // gl_graph_begin_capture .. gl_graph_end_capture: the communicators (their counters of recorded graphs) whose exchanges
     // were recorded -- RCCL's communicator destroy WAITS for every graph holding its operations, so gl_dist_destroy refuses
@@ -145,6 +145,15 @@ static inline hipError_t d2h_word_sync(uint32_t *h_dst, const void *d_src, hipSt
     const hipError_t e = hipMemcpyAsync(h_dst, d_src, sizeof(uint32_t), hipMemcpyDeviceToHost, s);
     const hipError_t w = hipStreamSynchronize(s);
     return e != hipSuccess ? e : w;
+}
+
+// *w = the 16 page-locked staging words of the small device->host control reads (ctx().pinned_word), allocated on first use: a
+// page-locked destination makes such a read one DMA and one wait
+static inline hipError_t staging_words(uint32_t **w) {
+    uint32_t *&slot = ctx().pinned_word;
+    const hipError_t e = slot ? hipSuccess : hipHostMalloc((void **)&slot, 64, hipHostMallocDefault);
+    *w = slot;
+    return e;
 }
 
 static inline unsigned cdiv(uint64_t a, uint64_t b) { return (unsigned)((a + b - 1) / b); }

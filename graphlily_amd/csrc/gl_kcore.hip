@@ -23,33 +23,15 @@
 // The peel takes the launch shape of cc_hook_kernel (gl_cc.hip): a thread per queued vertex, four entries per step; a row
 // still unfinished after kcore_cut = 8 entries is taken over by the whole wavefront, 256 entries per step with coalesced index
 // loads (late levels consist of hub rows).  A slice shorter than the launch has wavefronts gives every wavefront fewer vertices.
-// MEMORY RULES inside a peel launch (gfx950: eight XCDs with private L2s), as in gl_cc.hip: every access to deg[] and to tail is
-// an agent-scope atomic on a global pointer; plain loads and stores only behind a launch boundary (the queue slice and the
-// control record were written by earlier launches; queue words written now are read by later ones).  No spin-waits, no tickets,
-// no hand-offs between workgroups.
-// GATING: every launch is correct whatever the previous one left in the control record -- a scan that finds the phase "peel"
-// returns at once and vice versa, everything returns once the phase is "done" -- so the host enqueues (scan, peel, turn) x
-// kcore_batch blindly, of which exactly one of scan / peel runs per triple, copies the record to page-locked memory and waits
-// ONCE per batch.  The result does not depend on kcore_batch.  At most n sub-rounds and n + 1 levels exist, so the loop is capped.
-#include "gl_rows.h"
+// MEMORY RULE and GATING: gl_rounds.h.  Atomic-only inside a peel launch: deg[] and the tail (the queue slice and the control
+// record were written by earlier launches; queue words written now are read by later ones).  The host enqueues (scan, peel,
+// turn) x kcore_batch, of which exactly one of scan / peel runs per triple -- a scan that finds the phase "peel" returns at once
+// and vice versa.  At most n sub-rounds and n + 1 levels exist, so the loop is capped.
+// The control record is gl_rounds.h's peel record (kPeelLevel = k, kPeelTop = the degeneracy); the tail is the only word of it that a
+// scan or peel launch writes.
+#include "gl_rounds.h"
 
 namespace gl {
-
-constexpr uint32_t kKcCtlBytes = 256;
-// the control record (words); the tail sits in the second 128-byte line: it is the only word a scan or peel launch writes
-enum : uint32_t { kKcK = 0, kKcLo = 1, kKcHi = 2, kKcPhase = 3, kKcLevels = 4, kKcSubRounds = 5, kKcLevelStart = 6, kKcDegeneracy = 7,
-                  kKcRecordWords = 8, kKcTail = 32 };
-enum : uint32_t { kKcScan = 0, kKcPeel = 1, kKcDone = 2 };
-
-typedef __attribute__((address_space(1))) uint32_t kc_gu32;
-
-__device__ __forceinline__ uint32_t kc_load(uint32_t *p) { return __hip_atomic_load((kc_gu32 *)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ uint32_t kc_add(uint32_t *p, uint32_t v) {
-    return __hip_atomic_fetch_add((kc_gu32 *)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ uint32_t kc_sub(uint32_t *p, uint32_t v) {
-    return __hip_atomic_fetch_sub((kc_gu32 *)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 // deg[v] = entries of row v other than v itself (the rows are sets of columns < n), the control record of level 0
 __global__ __launch_bounds__(256) void kcore_init_kernel(const uint32_t *__restrict__ row_ptr, const uint32_t *__restrict__ row_idx,
@@ -63,24 +45,14 @@ __global__ __launch_bounds__(256) void kcore_init_kernel(const uint32_t *__restr
     }
 }
 
-__global__ __launch_bounds__(256) void kcore_iota_kernel(uint32_t *__restrict__ out, uint32_t n) {
-    for (uint64_t v = blockIdx.x * 256u + threadIdx.x; v < n; v += gridDim.x * 256u) out[v] = (uint32_t)v;
-}
-
 __global__ __launch_bounds__(256) void kcore_scan_kernel(const uint32_t *__restrict__ deg, uint32_t *__restrict__ queue, uint32_t *ctl,
                                                          uint32_t n) {
-    if (ctl[kKcPhase] != kKcScan) return;
-    const uint32_t k = ctl[kKcK], lane = threadIdx.x & 63u;
+    if (ctl[kPeelPhase] != kPeelScan) return;
+    const uint32_t k = ctl[kPeelLevel], lane = threadIdx.x & 63u;
     const uint64_t nround = ((uint64_t)n + 255u) & ~255ull;       // whole wavefronts take every trip
     for (uint64_t v = blockIdx.x * 256u + threadIdx.x; v < nround; v += gridDim.x * 256u) {
         const bool hit = v < n && deg[v] == k;
-        const unsigned long long m = __ballot(hit);
-        if (m == 0ull) continue;
-        const int leader = __ffsll(m) - 1;
-        uint32_t base = 0;
-        if ((int)lane == leader) base = kc_add(ctl + kKcTail, (uint32_t)__popcll(m));
-        base = __shfl(base, leader);
-        const uint32_t pos = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+        const uint32_t pos = wave_append(hit, ctl + kPeelTail, lane);
         if (hit && pos < n) queue[pos] = (uint32_t)v;             // (pos < n: every vertex is appended once)
     }
 }
@@ -93,19 +65,19 @@ struct KcPeelArgs {
 
 // one neighbour u of a vertex peeled at level k
 __device__ __forceinline__ void kc_relax(const KcPeelArgs &a, uint32_t u, uint32_t k) {
-    if (kc_load(a.deg + u) <= k) return;                          // peeled before, or queued at this level
-    const uint32_t old = kc_sub(a.deg + u, 1u);
+    if (ga_load(a.deg + u) <= k) return;                          // peeled before, or queued at this level
+    const uint32_t old = ga_sub(a.deg + u, 1u);
     if (old == k + 1u) {
-        const uint32_t pos = kc_add(a.ctl + kKcTail, 1u);
+        const uint32_t pos = ga_add(a.ctl + kPeelTail, 1u);
         if (pos < a.n) a.queue[pos] = u;
     } else if (old <= k) {
-        (void)kc_add(a.deg + u, 1u);
+        (void)ga_add(a.deg + u, 1u);
     }
 }
 
 __global__ __launch_bounds__(256) void kcore_peel_kernel(KcPeelArgs a) {
-    if (a.ctl[kKcPhase] != kKcPeel) return;
-    const uint32_t k = a.ctl[kKcK], lo = a.ctl[kKcLo], hi = a.ctl[kKcHi];
+    if (a.ctl[kPeelPhase] != kPeelPeel) return;
+    const uint32_t k = a.ctl[kPeelLevel], lo = a.ctl[kPeelLo], hi = a.ctl[kPeelHi];
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t count = hi - lo, nwaves = gridDim.x * 4u;
@@ -155,25 +127,25 @@ __global__ __launch_bounds__(256) void kcore_peel_kernel(KcPeelArgs a) {
 // behind exactly one scan or peel that ran (plain loads and stores: a launch of its own)
 __global__ void kcore_turn_kernel(uint32_t *ctl, uint32_t n) {
     if (threadIdx.x != 0u || blockIdx.x != 0u) return;
-    const uint32_t phase = ctl[kKcPhase];
-    if (phase == kKcDone) return;
-    const uint32_t k = ctl[kKcK], lo = ctl[kKcHi], hi = ctl[kKcTail];
-    if (phase == kKcPeel) ctl[kKcSubRounds] += 1u;
-    ctl[kKcLo] = lo;
-    ctl[kKcHi] = hi;
+    const uint32_t phase = ctl[kPeelPhase];
+    if (phase == kPeelDone) return;
+    const uint32_t k = ctl[kPeelLevel], lo = ctl[kPeelHi], hi = ctl[kPeelTail];
+    if (phase == kPeelPeel) ctl[kPeelSubRounds] += 1u;
+    ctl[kPeelLo] = lo;
+    ctl[kPeelHi] = hi;
     const bool done = hi >= n, over = lo == hi;
-    if ((done || over) && hi != ctl[kKcLevelStart]) {             // the level queued somebody: its vertices have core k
-        ctl[kKcLevels] += 1u;
-        ctl[kKcLevelStart] = hi;
-        ctl[kKcDegeneracy] = k;
+    if ((done || over) && hi != ctl[kPeelLevelStart]) {             // the level queued somebody: its vertices have core k
+        ctl[kPeelLevels] += 1u;
+        ctl[kPeelLevelStart] = hi;
+        ctl[kPeelTop] = k;
     }
     if (done) {
-        ctl[kKcPhase] = kKcDone;
+        ctl[kPeelPhase] = kPeelDone;
     } else if (over) {
-        ctl[kKcK] = k + 1u;
-        ctl[kKcPhase] = kKcScan;
+        ctl[kPeelLevel] = k + 1u;
+        ctl[kPeelPhase] = kPeelScan;
     } else {
-        ctl[kKcPhase] = kKcPeel;
+        ctl[kPeelPhase] = kPeelPeel;
     }
 }
 
@@ -182,7 +154,7 @@ static int kcore_prepare(gl_spmv_plan p, const char *who) {
     const int rc = rows_require(p, kRowsSymmetric, who, "the plan", "io.symmetrize_simple");
     if (rc != GL_OK || p->nnz == 0) return rc;
     // the control record, then the queue of a call without d_order
-    return plan_scratch(p->d_kcore_scratch, kKcCtlBytes + 4u * (size_t)p->num_rows, who, "control record and queue");
+    return plan_scratch(p->d_kcore_scratch, kRoundsCtlBytes + 4u * (size_t)p->num_rows, who, "control record and queue");
 }
 
 static int kcore(gl_spmv_plan p, uint32_t *d_core, uint32_t *d_order, uint32_t *h_stats, const char *who) {
@@ -194,11 +166,7 @@ static int kcore(gl_spmv_plan p, uint32_t *d_core, uint32_t *d_order, uint32_t *
     if (n == 0u) return GL_OK;
     if (p->nnz == 0) {                                            // an empty graph: nobody has a neighbour, any order will do
         GL_HIP(hipMemsetAsync(d_core, 0, 4u * (size_t)n, s));
-        if (d_order) {
-            kcore_iota_kernel<<<rows_stream_grid(n), 256, 0, s>>>(d_order, n);
-            GL_LAUNCH_CHECK();
-        }
-        return GL_OK;
+        return d_order ? rows_iota(d_order, n) : GL_OK;
     }
     // A/B knobs (GRAPHLILY_DEBUG, read per call): kcore_cut = entries a thread reads before the wavefront takes the row over,
     // kcore_batch = (scan, peel, turn) triples enqueued between two read-backs of the control record (8 and 64: the best of
@@ -212,42 +180,42 @@ static int kcore(gl_spmv_plan p, uint32_t *d_core, uint32_t *d_order, uint32_t *
     a.row_ptr = p->d_csr_indptr;
     a.row_idx = p->d_csr_indices;
     a.deg = d_core;
-    a.queue = d_order ? d_order : ctl + kKcCtlBytes / 4u;
+    a.queue = d_order ? d_order : ctl + kRoundsCtlBytes / 4u;
     a.ctl = ctl;
     a.n = n;
     a.nz_base = p->csr_nz_base;
     a.cut_steps = (uint32_t)std::max<long>(0, std::min<long>(cut, 1l << 30)) / 4u;
     const unsigned stream_grid = rows_stream_grid(n);
     const unsigned peel_grid = std::max(1u, std::min<unsigned>(cdiv(n, 256u), (unsigned)ctx().num_cus * per_cu));
-    uint32_t *&w = ctx().pinned_word;
-    if (!w) GL_HIP(hipHostMalloc((void **)&w, 64, hipHostMallocDefault));
-    static_assert(kKcRecordWords * 4u <= 64u, "the record fits the page-locked staging words");
+    uint32_t *w = nullptr;
+    GL_HIP(staging_words(&w));
+    static_assert(kPeelRecordWords * 4u <= 64u, "the record fits the page-locked staging words");
     kcore_init_kernel<<<stream_grid, 256, 0, s>>>(a.row_ptr, a.row_idx, n, a.nz_base, d_core, ctl);
     GL_LAUNCH_CHECK();
-    uint64_t launches = 1, steps = 0;
+    uint64_t launches = 1;
     // every step that runs is a scan (one per level, and k never passes the degeneracy < n) or a sub-round over a slice that is
     // not empty (every vertex is in one slice): at most 2 n + 1 steps
-    const uint64_t max_steps = 2ull * n + 1ull;
-    for (;;) {
-        for (uint32_t i = 0; i < batch; i++) {
-            kcore_scan_kernel<<<stream_grid, 256, 0, s>>>(d_core, a.queue, ctl, n);
-            kcore_peel_kernel<<<peel_grid, 256, 0, s>>>(a);
-            kcore_turn_kernel<<<1, 64, 0, s>>>(ctl, n);
-        }
-        GL_LAUNCH_CHECK();
-        launches += 3ull * batch;
-        steps += batch;
-        GL_HIP(hipMemcpyAsync(w, ctl, kKcRecordWords * 4u, hipMemcpyDeviceToHost, s));
-        GL_HIP(hipStreamSynchronize(s));
-        if (w[kKcPhase] == kKcDone) break;
-        if (steps >= max_steps)
+    rc = rounds_run(
+        batch, 2ull * n + 1ull, launches,
+        [&] {
+            for (uint32_t i = 0; i < batch; i++) {
+                kcore_scan_kernel<<<stream_grid, 256, 0, s>>>(d_core, a.queue, ctl, n);
+                kcore_peel_kernel<<<peel_grid, 256, 0, s>>>(a);
+                kcore_turn_kernel<<<1, 64, 0, s>>>(ctl, n);
+            }
+            return 3ull * batch;
+        },
+        [&] { return hipMemcpyAsync(w, ctl, kPeelRecordWords * 4u, hipMemcpyDeviceToHost, s); },
+        [&] { return w[kPeelPhase] == kPeelDone ? kRoundsDone : kRoundsGoOn; },
+        [&](uint64_t steps) {
             return set_error(GL_ERR_HIP, "%s: internal error: not done after %llu steps on %u vertices (level %u, %u sub-rounds)", who,
-                             (unsigned long long)steps, n, w[kKcK], w[kKcSubRounds]);
-    }
+                             (unsigned long long)steps, n, w[kPeelLevel], w[kPeelSubRounds]);
+        });
+    if (rc != GL_OK) return rc;
     if (h_stats) {
-        h_stats[0] = w[kKcDegeneracy];
-        h_stats[1] = w[kKcLevels];
-        h_stats[2] = w[kKcSubRounds];
+        h_stats[0] = w[kPeelTop];
+        h_stats[1] = w[kPeelLevels];
+        h_stats[2] = w[kPeelSubRounds];
         h_stats[3] = (uint32_t)std::min<uint64_t>(launches, 0xffffffffull);
     }
     return GL_OK;

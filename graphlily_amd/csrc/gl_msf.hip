@@ -32,35 +32,29 @@
 //           clears best[].
 // AFTER done: the mirror entry (hi, lo) of every listed edge is found by rows_lower_bound in row hi and marked; with d_labels, every
 // vertex lowers its root's word of B to itself (an atomic min) and the labels are gathered through A; the roots are counted.
-// MEMORY RULES (gfx950: eight XCDs with private L2s -- a plain store is not seen across them within a launch):
-//   * inside the scan launch best[] is touched ONLY by agent-scope atomics on a global pointer (a relaxed atomic load, an atomic
-//     min); comp[], first[], the rows and the weights are read-only in it (plain loads of words written by earlier launches);
+// MEMORY RULE and GATING: gl_rounds.h.  What is atomic-only in which launch:
+//   * inside the scan launch best[] (a relaxed atomic load, an atomic min); comp[], first[], the rows and the weights are read-only
+//     in it (plain loads of words written by earlier launches);
 //   * a word of best[] only descends within a launch, so the filter's load, however stale, can cost a needless atomic and never a
 //     wrong skip: it skips only what is not below a value the word held at some time, hence not below its final value;
 //   * the hook reads A and best[] plainly (written by earlier launches) and writes B, the marks and the list; no word it writes is
 //     read in the same launch.  The list's tail is an agent-scope atomic add, one per wavefront;
 //   * the "changed" word of a pointer-doubling step is touched only by agent-scope atomics (a load, an OR: once per workgroup) in
 //     the launch that raises it, and read plainly by the next;
-//   * the label pass lowers B[root] by agent-scope atomic mins only and reads A plainly; the gather runs behind a launch boundary;
-//   * no spin-waits, no tickets, no hand-offs between workgroups.
-// GATING: every launch returns at once when the record says done, the closing passes unless it does, so the host enqueues
-// msf_batch rounds and the closing passes blindly, copies the record to page-locked memory and waits ONCE per batch.  The result
-// does not depend on msf_batch.  A round that hooks at least halves the components that still have an edge, so at most
+//   * the label pass lowers B[root] by agent-scope atomic mins only and reads A plainly; the gather runs behind a launch boundary.
+// Every launch returns at once when the record says done, the closing passes unless it does: the host enqueues msf_batch rounds
+// and the closing passes behind them.  A round that hooks at least halves the components that still have an edge, so at most
 // ceil(log2 n) rounds hook and one more finds nothing.
 // The jump and count kernels are private copies of gl_cc.hip's (they are gated and the first jump clears best[]): gl_cc is untouched.
-#include "gl_rows.h"
+#include "gl_rounds.h"
 #include "graphlily_hip_msf.h"
 
 namespace gl {
 
-constexpr uint32_t kMsfCtlBytes = 256;
 // the control record (words); the "changed" words of the pointer-doubling steps start at kMsfChanged
 enum : uint32_t { kMsfDone = 0, kMsfRounds = 1, kMsfEdges = 2, kMsfSeen = 3, kMsfCount = 4, kMsfRecordWords = 5, kMsfChanged = 16 };
 constexpr uint32_t kMsfMaxJumps = 36;      // ceil(log2 2^32) + 1, with room
 constexpr unsigned long long kMsfNone = ~0ull;
-
-typedef __attribute__((address_space(1))) uint32_t msf_gu32;
-typedef __attribute__((address_space(1))) unsigned long long msf_gu64;
 
 __device__ __forceinline__ unsigned long long msf_word(uint32_t bits, uint32_t j) {
     const uint32_t key = bits ^ ((bits >> 31) ? 0xffffffffu : 0x80000000u);
@@ -77,11 +71,11 @@ __device__ __forceinline__ void msf_offer(unsigned long long *best, uint32_t c, 
     if (filter) {
         if (c == hc && hv <= word) return;
         hc = c;
-        hv = __hip_atomic_load((msf_gu64 *)best + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        hv = ga_load(best + c);
         if (hv <= word) return;
         hv = word;
     }
-    (void)__hip_atomic_fetch_min((msf_gu64 *)best + c, word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    ga_min(best + c, word);
 }
 
 __device__ __forceinline__ unsigned long long msf_shfl_xor(unsigned long long x, int d) {
@@ -111,10 +105,6 @@ __global__ __launch_bounds__(256) void msf_begin_kernel(const uint32_t *__restri
         best[v] = kMsfNone;
         first[v] = b + at;
     }
-}
-
-__global__ __launch_bounds__(256) void msf_iota_kernel(uint32_t *__restrict__ out, uint32_t n) {
-    for (uint64_t v = blockIdx.x * 256u + threadIdx.x; v < n; v += gridDim.x * 256u) out[v] = (uint32_t)v;
 }
 
 __global__ __launch_bounds__(256) void msf_scan_kernel(MsfArgs a) {
@@ -222,14 +212,7 @@ __global__ __launch_bounds__(256) void msf_hook_kernel(const uint32_t *__restric
             }
             B[c] = to;
         }
-        const unsigned long long mask = __ballot(hooks);
-        if (mask == 0ull) continue;
-        const int leader = __ffsll(mask) - 1;
-        uint32_t base = 0;
-        if ((int)lane == leader)
-            base = __hip_atomic_fetch_add((msf_gu32 *)(ctl + kMsfEdges), (uint32_t)__popcll(mask), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        base = __shfl(base, leader);
-        const uint32_t at = base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
+        const uint32_t at = wave_append(hooks, ctl + kMsfEdges, lane);
         if (hooks && at < n) {                                        // (at < n: a forest has fewer edges than vertices)
             in_forest[j] = 1u;
             list[2u * at] = j;
@@ -264,9 +247,7 @@ __global__ __launch_bounds__(256) void msf_jump_kernel(const uint32_t *__restric
     }
     // one word for the whole launch, raised once per workgroup and only if a load finds it down: thousands of atomics on one
     // address were most of a step's time (EXPERIMENTS.md Round 19).  The word only rises, so a stale load costs a needless atomic
-    if (__syncthreads_or(moved) && threadIdx.x == 0u &&
-        __hip_atomic_load((msf_gu32 *)(ctl + kMsfChanged + step), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u)
-        atomicOr(ctl + kMsfChanged + step, 1u);
+    if (__syncthreads_or(moved) && threadIdx.x == 0u && ga_load(ctl + kMsfChanged + step) == 0u) atomicOr(ctl + kMsfChanged + step, 1u);
 }
 
 // the closing passes: each runs once, in the batch whose turn said done
@@ -287,7 +268,7 @@ __global__ __launch_bounds__(256) void msf_label_min_kernel(const uint32_t *__re
     if (ctl[kMsfDone] == 0u) return;
     for (uint64_t v = blockIdx.x * 256u + threadIdx.x; v < n; v += gridDim.x * 256u) {
         const uint32_t r = A[v];
-        if ((uint32_t)v < r) (void)__hip_atomic_fetch_min((msf_gu32 *)B + r, (uint32_t)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if ((uint32_t)v < r) ga_min(B + r, (uint32_t)v);
     }
 }
 
@@ -318,12 +299,12 @@ static MsfLayout msf_layout(gl_spmv_plan p) {
     const size_t n = std::max<size_t>(p->num_cols, 1u);
     MsfLayout t;
     t.ctl = reinterpret_cast<uint32_t *>(p->d_msf_scratch);
-    t.best = reinterpret_cast<unsigned long long *>(p->d_msf_scratch + kMsfCtlBytes);
+    t.best = reinterpret_cast<unsigned long long *>(p->d_msf_scratch + kRoundsCtlBytes);
     t.A = reinterpret_cast<uint32_t *>(t.best + n);
     t.B = t.A + n;
     t.first = t.B + n;
     t.list = t.first + n;
-    t.bytes = kMsfCtlBytes + 28u * n;
+    t.bytes = kRoundsCtlBytes + 28u * n;
     return t;
 }
 
@@ -336,10 +317,7 @@ static int msf(gl_spmv_plan p, const float *d_weight, uint32_t *d_in_forest, uin
     // the launches that end in an atomic on ONE word per wavefront or workgroup (the jumps, the count) take fewer workgroups
     const unsigned word_grid = std::min<unsigned>(vertex_grid, (unsigned)ctx().num_cus * 2u);
     if (n == 0u || p->nnz == 0) {                                 // no entries: no forest words, every vertex its own component
-        if (d_labels && n) {
-            msf_iota_kernel<<<vertex_grid, 256, 0, s>>>(d_labels, n);
-            GL_LAUNCH_CHECK();
-        }
+        if (d_labels && n && (rc = rows_iota(d_labels, n)) != GL_OK) return rc;
         GL_HIP(hipStreamSynchronize(s));
         if (h_stats) {
             h_stats[0] = 0;
@@ -375,42 +353,42 @@ static int msf(gl_spmv_plan p, const float *d_weight, uint32_t *d_in_forest, uin
     const unsigned scan_grid = std::max(1u, std::min<unsigned>((nwords + 3u) / 4u, (unsigned)ctx().num_cus * per_cu));
     uint32_t jumps = 1;                                           // ceil(log2 n) + 1
     while ((1ull << (jumps - 1u)) < n) jumps++;
-    static_assert(kMsfChanged * 4u + kMsfMaxJumps * 4u <= kMsfCtlBytes && kMsfMaxJumps >= 33u, "one word per step");
+    static_assert(kMsfChanged * 4u + kMsfMaxJumps * 4u <= kRoundsCtlBytes && kMsfMaxJumps >= 33u, "one word per step");
     static_assert(kMsfRecordWords <= 16u, "the record fits the page-locked staging words");
-    uint32_t *&w = ctx().pinned_word;
-    if (!w) GL_HIP(hipHostMalloc((void **)&w, 64, hipHostMallocDefault));
-    GL_HIP(hipMemsetAsync(t.ctl, 0, kMsfCtlBytes, s));
+    uint32_t *w = nullptr;
+    GL_HIP(staging_words(&w));
+    GL_HIP(hipMemsetAsync(t.ctl, 0, kRoundsCtlBytes, s));
     GL_HIP(hipMemsetAsync(d_in_forest, 0, 4u * (size_t)nnz, s));
     msf_begin_kernel<<<vertex_grid, 256, 0, s>>>(a.row_ptr, a.row_idx, n, a.nz_base, t.A, t.B, t.best, t.first);
     GL_LAUNCH_CHECK();
-    uint64_t launches = 1, rounds = 0;
+    uint64_t launches = 1;
     // every round that hooks at least halves the components that still have an edge: ceil(log2 n) such rounds and one that finds
     // nothing, jumps of them; a batch more for room
-    const uint64_t max_rounds = (uint64_t)jumps + batch;
-    for (;;) {
-        for (uint32_t i = 0; i < batch; i++) {
-            msf_scan_kernel<<<scan_grid, 256, 0, s>>>(a);
-            msf_hook_kernel<<<vertex_grid, 256, 0, s>>>(a.row_ptr, a.row_idx, n, a.nz_base, t.A, t.B, t.best, d_in_forest, t.list, t.ctl);
-            msf_turn_kernel<<<1, 64, 0, s>>>(t.ctl, jumps);
-            uint32_t *in = t.B, *out = t.A;
-            for (uint32_t r = 0; r < jumps; r++) {
-                msf_jump_kernel<<<word_grid, 256, 0, s>>>(in, out, n, t.ctl, r, r == 0u ? t.best : nullptr);
-                std::swap(in, out);
+    rc = rounds_run(
+        batch, (uint64_t)jumps + batch, launches,
+        [&] {
+            for (uint32_t i = 0; i < batch; i++) {
+                msf_scan_kernel<<<scan_grid, 256, 0, s>>>(a);
+                msf_hook_kernel<<<vertex_grid, 256, 0, s>>>(a.row_ptr, a.row_idx, n, a.nz_base, t.A, t.B, t.best, d_in_forest, t.list, t.ctl);
+                msf_turn_kernel<<<1, 64, 0, s>>>(t.ctl, jumps);
+                uint32_t *in = t.B, *out = t.A;
+                for (uint32_t r = 0; r < jumps; r++) {
+                    msf_jump_kernel<<<word_grid, 256, 0, s>>>(in, out, n, t.ctl, r, r == 0u ? t.best : nullptr);
+                    std::swap(in, out);
+                }
             }
-        }
-        msf_mirror_kernel<<<vertex_grid, 256, 0, s>>>(a.row_ptr, a.row_idx, n, a.nz_base, t.list, d_in_forest, t.ctl);
-        if (d_labels) msf_label_min_kernel<<<vertex_grid, 256, 0, s>>>(t.A, t.B, n, t.ctl);
-        msf_finish_kernel<<<word_grid, 256, 0, s>>>(t.A, t.B, n, d_labels, t.ctl);
-        GL_LAUNCH_CHECK();
-        launches += (uint64_t)batch * (3u + jumps) + (d_labels ? 3u : 2u);
-        rounds += batch;
-        GL_HIP(hipMemcpyAsync(w, t.ctl, kMsfRecordWords * 4u, hipMemcpyDeviceToHost, s));
-        GL_HIP(hipStreamSynchronize(s));
-        if (w[kMsfDone] != 0u) break;
-        if (rounds >= max_rounds)
+            msf_mirror_kernel<<<vertex_grid, 256, 0, s>>>(a.row_ptr, a.row_idx, n, a.nz_base, t.list, d_in_forest, t.ctl);
+            if (d_labels) msf_label_min_kernel<<<vertex_grid, 256, 0, s>>>(t.A, t.B, n, t.ctl);
+            msf_finish_kernel<<<word_grid, 256, 0, s>>>(t.A, t.B, n, d_labels, t.ctl);
+            return (uint64_t)batch * (3u + jumps) + (d_labels ? 3u : 2u);
+        },
+        [&] { return hipMemcpyAsync(w, t.ctl, kMsfRecordWords * 4u, hipMemcpyDeviceToHost, s); },
+        [&] { return w[kMsfDone] != 0u ? kRoundsDone : kRoundsGoOn; },
+        [&](uint64_t rounds) {
             return set_error(GL_ERR_HIP, "%s: internal error: not done after %llu rounds on %u vertices (%u rounds hooked, %u forest edges)", who,
                              (unsigned long long)rounds, n, w[kMsfRounds], w[kMsfEdges]);
-    }
+        });
+    if (rc != GL_OK) return rc;
     if ((uint64_t)w[kMsfEdges] + w[kMsfCount] != n)
         return set_error(GL_ERR_HIP, "%s: internal error: %u forest edges and %u components on %u vertices", who, w[kMsfEdges], w[kMsfCount], n);
     if (h_stats) {

@@ -2,6 +2,8 @@
 // graph kernels that walk it see it -- gl_bfs_parents, gl_cc, gl_tc, gl_kcore, gl_color, gl_truss, gl_msf (which also takes a
 // value per entry of the copy from its caller), gl_bc: what a caller may require of it, the
 // verdicts about it that the plan caches, and the few helpers every such kernel wants.  gl_rows.hip holds the check kernels.
+// gl_rounds.h, on top of this, holds what the kernels that run in rounds over a queue share: the atomics of their memory rule,
+// the queue append, the peel record and the gated host loop.
 #ifndef GL_ROWS_H_
 #define GL_ROWS_H_
 
@@ -39,6 +41,8 @@ int rows_check_transpose(gl_spmv_plan p, gl_spmv_plan partner, bool *ok);
 
 // the grid of a streaming pass, a thread per vertex
 inline unsigned rows_stream_grid(uint32_t n) { return std::max(1u, std::min<unsigned>(cdiv(n, 256u), (unsigned)ctx().num_cus * 8u)); }
+// d_out[v] = v for v < n, n >= 1: one launch (the answer of the calls that find a graph without entries)
+int rows_iota(uint32_t *d_out, uint32_t n);
 
 // scratch that its first user allocates and its owner (a plan, the context) frees
 template <typename T>

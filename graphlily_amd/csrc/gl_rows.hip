@@ -1,6 +1,6 @@
 // The contract of the row copy (gl_rows.h): the refusals, and the three kernels that establish what the plan caches about its
 // rows -- rows_sorted, rows_are_sets, rows_symmetric.  Each check runs once per plan, over four control words of its own, and
-// waits for its answer.
+// waits for its answer.  Also the one kernel that numbers an array (rows_iota).
 #include "gl_rows.h"
 
 namespace gl {
@@ -66,6 +66,16 @@ __global__ __launch_bounds__(256) void rows_transpose_kernel(const uint32_t *__r
         }
     }
     if (bad) atomicOr(verdict, 1u);
+}
+
+__global__ __launch_bounds__(256) void rows_iota_kernel(uint32_t *__restrict__ out, uint32_t n) {
+    for (uint64_t v = blockIdx.x * 256u + threadIdx.x; v < n; v += gridDim.x * 256u) out[v] = (uint32_t)v;
+}
+
+int rows_iota(uint32_t *d_out, uint32_t n) {
+    rows_iota_kernel<<<rows_stream_grid(n), 256, 0, ctx().stream>>>(d_out, n);
+    GL_LAUNCH_CHECK();
+    return GL_OK;
 }
 
 // launch(ctl, stream) enqueues one check kernel over four zeroed control words; -> their values (one synchronisation)

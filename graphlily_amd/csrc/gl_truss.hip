@@ -39,37 +39,19 @@
 // workgroups -- the peel reduces nothing, so a group need not share a wavefront: late sub-rounds hold a few hub edges, and one
 // group walking a row of thousands of entries alone was the whole step (EXPERIMENTS.md Round 18: 4.5 times on the call).  Rows are
 // not staged in LDS (gl_tc does): the edge (hub, hub) has two rows beyond any cap, and the variant was not built, so not measured.
-// MEMORY RULES inside a peel launch (gfx950: eight XCDs with private L2s), as in gl_kcore.hip: every access to S[], pos[] and tail
-// is an agent-scope atomic on a global pointer; plain loads and stores only behind a launch boundary (rows, eid, the queue slice
-// and the control record were written by earlier launches; queue words written now are read by later ones).  No spin-waits, no
-// tickets, no hand-offs between workgroups.
-// GATING: every launch is correct whatever the previous one left in the control record -- a scan that finds the phase "peel"
-// returns at once and vice versa, everything returns once the phase is "done" -- so the host enqueues (scan, peel, turn) x
-// truss_batch blindly, then the pass that writes d_truss (gated on "done"), copies the record to page-locked memory and waits
-// ONCE per batch.  The result does not depend on truss_batch.  At most m sub-rounds exist and at most max support + 1 <= m levels
-// are scanned, so the loop is capped.
-#include "gl_rows.h"
+// MEMORY RULE and GATING: gl_rounds.h.  Atomic-only inside a peel launch: S[], pos[] and the tail (rows, eid, the queue slice and
+// the control record were written by earlier launches; queue words written now are read by later ones); inside a scan launch the
+// tail and the record's `next` word, inside the support pass its 64-bit sum.  The host enqueues (scan, peel, turn) x truss_batch
+// -- a scan that finds the phase "peel" returns at once and vice versa -- and then the pass that writes d_truss, gated on "done".
+// At most m sub-rounds exist and at most max support + 1 <= m levels are scanned, so the loop is capped.
+// The control record is gl_rounds.h's peel record (kPeelLevel = l, kPeelTop = the last level that removed an edge) and two
+// words more: kTrussNext, and the 64-bit kTrussSum behind the tail in the second 128-byte line.
+#include "gl_rounds.h"
 #include "graphlily_hip_truss.h"
 
 namespace gl {
 
-constexpr uint32_t kTrCtlBytes = 256;
-// the control record (words); the tail sits in the second 128-byte line with the 64-bit sum of the supports behind it
-enum : uint32_t { kTrL = 0, kTrLo = 1, kTrHi = 2, kTrPhase = 3, kTrLevels = 4, kTrSubRounds = 5, kTrLevelStart = 6, kTrTop = 7,
-                  kTrNext = 8, kTrRecordWords = 9, kTrTail = 32, kTrSum = 34 };
-enum : uint32_t { kTrScan = 0, kTrPeel = 1, kTrDone = 2 };
 constexpr uint32_t kTrNone = 0xffffffffu;
-
-typedef __attribute__((address_space(1))) uint32_t tr_gu32;
-typedef __attribute__((address_space(1))) unsigned long long tr_gu64;
-
-__device__ __forceinline__ uint32_t tr_load(uint32_t *p) { return __hip_atomic_load((tr_gu32 *)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void tr_store(uint32_t *p, uint32_t v) {
-    __hip_atomic_store((tr_gu32 *)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ uint32_t tr_add(uint32_t *p, uint32_t v) {
-    return __hip_atomic_fetch_add((tr_gu32 *)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 // the plan's cached part, then the words of one call
 struct TrArgs {
@@ -150,7 +132,7 @@ __global__ __launch_bounds__(256) void truss_number_kernel(const uint32_t *__res
 }
 
 __global__ void truss_init_kernel(uint32_t *ctl) {
-    if (blockIdx.x == 0u && threadIdx.x < 64u) ctl[threadIdx.x] = threadIdx.x == kTrNext ? kTrNone : 0u;   // l = 0, phase scan, tail 0
+    if (blockIdx.x == 0u && threadIdx.x < 64u) ctl[threadIdx.x] = threadIdx.x == kTrussNext ? kTrNone : 0u;   // l = 0, phase scan, tail 0
 }
 
 // the two rows of edge e, the shorter first: (owner, begin, length) each
@@ -191,13 +173,12 @@ __global__ __launch_bounds__(256) void truss_support_kernel(TrArgs a) {
         if (sub == 0u && e < a.m) a.S[e] = of_group;
         sum += count;
     }
-    if (lane == 0u && sum != 0ull)
-        (void)__hip_atomic_fetch_add((tr_gu64 *)(a.ctl + kTrSum), sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (lane == 0u && sum != 0ull) ga_add((unsigned long long *)(a.ctl + kTrussSum), sum);
 }
 
 __global__ __launch_bounds__(256) void truss_scan_kernel(TrArgs a) {
-    if (a.ctl[kTrPhase] != kTrScan) return;
-    const uint32_t l = a.ctl[kTrL], lane = threadIdx.x & 63u;
+    if (a.ctl[kPeelPhase] != kPeelScan) return;
+    const uint32_t l = a.ctl[kPeelLevel], lane = threadIdx.x & 63u;
     const uint64_t mround = ((uint64_t)a.m + 255u) & ~255ull;     // whole wavefronts take every trip
     uint32_t next = kTrNone;
     for (uint64_t e = blockIdx.x * 256u + threadIdx.x; e < mround; e += gridDim.x * 256u) {
@@ -205,13 +186,7 @@ __global__ __launch_bounds__(256) void truss_scan_kernel(TrArgs a) {
         const uint32_t s = open ? a.S[e] : 0u;
         const bool hit = open && s == l;
         if (open && s > l) next = min(next, s);
-        const unsigned long long mask = __ballot(hit);
-        if (mask == 0ull) continue;
-        const int leader = __ffsll(mask) - 1;
-        uint32_t base = 0;
-        if ((int)lane == leader) base = tr_add(a.ctl + kTrTail, (uint32_t)__popcll(mask));
-        base = __shfl(base, leader);
-        const uint32_t at = base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
+        const uint32_t at = wave_append(hit, a.ctl + kPeelTail, lane);
         if (hit && at < a.m) {                                       // (at < m: every edge is appended once)
             a.queue[at] = (uint32_t)e;
             a.pos[e] = at;
@@ -219,21 +194,20 @@ __global__ __launch_bounds__(256) void truss_scan_kernel(TrArgs a) {
     }
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) next = min(next, (uint32_t)__shfl_xor(next, d));
-    if (lane == 0u && next != kTrNone)
-        (void)__hip_atomic_fetch_min((tr_gu32 *)(a.ctl + kTrNext), next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (lane == 0u && next != kTrNone) ga_min(a.ctl + kTrussNext, next);
 }
 
 // one triangle less for edge x, at level l
 __device__ __forceinline__ void tr_decrement(const TrArgs &a, uint32_t x, uint32_t l) {
-    uint32_t old = tr_load(a.S + x);
+    uint32_t old = ga_load(a.S + x);
     while (old > l) {
-        if (__hip_atomic_compare_exchange_strong((tr_gu32 *)(a.S + x), &old, old - 1u, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                                 __HIP_MEMORY_SCOPE_AGENT)) {
-            if (old - 1u == l) {
-                const uint32_t at = tr_add(a.ctl + kTrTail, 1u);
+        const uint32_t less = old - 1u;
+        if (ga_cas(a.S + x, old, less)) {
+            if (less == l) {
+                const uint32_t at = ga_add(a.ctl + kPeelTail, 1u);
                 if (at < a.m) {
                     a.queue[at] = x;
-                    tr_store(a.pos + x, at);
+                    ga_store(a.pos + x, at);
                 }
             }
             return;
@@ -242,8 +216,8 @@ __device__ __forceinline__ void tr_decrement(const TrArgs &a, uint32_t x, uint32
 }
 
 __global__ __launch_bounds__(256) void truss_peel_kernel(TrArgs a) {
-    if (a.ctl[kTrPhase] != kTrPeel) return;
-    const uint32_t l = a.ctl[kTrL], lo = a.ctl[kTrLo], hi = a.ctl[kTrHi];
+    if (a.ctl[kPeelPhase] != kPeelPeel) return;
+    const uint32_t l = a.ctl[kPeelLevel], lo = a.ctl[kPeelLo], hi = a.ctl[kPeelHi];
     // lanes per edge: truss_group, and more while the slice leaves half the launch idle (late sub-rounds hold a few hub edges whose
     // rows one group would walk alone) -- up to 1 << truss_spread lanes, across wavefronts and workgroups: nothing is reduced here
     const uint64_t threads = (uint64_t)gridDim.x * 256u, me = (uint64_t)blockIdx.x * 256u + threadIdx.x;
@@ -260,7 +234,7 @@ __global__ __launch_bounds__(256) void truss_peel_kernel(TrArgs a) {
             const uint32_t at = rows_lower_bound(a.row_idx + r.bb, r.blen, w);
             if (a.row_idx[r.bb + at] != w) continue;
             const uint32_t e1 = a.eid[r.ab + i], e2 = a.eid[r.bb + at];
-            const uint32_t p1 = tr_load(a.pos + e1), p2 = tr_load(a.pos + e2);
+            const uint32_t p1 = ga_load(a.pos + e1), p2 = ga_load(a.pos + e2);
             if (p1 < lo || p2 < lo) continue;
             const bool in1 = p1 < hi, in2 = p2 < hi;
             if (in1 && in2) continue;
@@ -279,34 +253,34 @@ __global__ __launch_bounds__(256) void truss_peel_kernel(TrArgs a) {
 // behind exactly one scan or peel that ran (plain loads and stores: a launch of its own)
 __global__ void truss_turn_kernel(uint32_t *ctl, uint32_t m) {
     if (threadIdx.x != 0u || blockIdx.x != 0u) return;
-    const uint32_t phase = ctl[kTrPhase];
-    if (phase == kTrDone) return;
-    const uint32_t l = ctl[kTrL], lo = ctl[kTrHi], hi = min(ctl[kTrTail], m), next = ctl[kTrNext];
-    ctl[kTrLo] = lo;
-    ctl[kTrHi] = hi;
-    ctl[kTrNext] = kTrNone;
-    if (hi != lo) ctl[kTrSubRounds] += 1u;
+    const uint32_t phase = ctl[kPeelPhase];
+    if (phase == kPeelDone) return;
+    const uint32_t l = ctl[kPeelLevel], lo = ctl[kPeelHi], hi = min(ctl[kPeelTail], m), next = ctl[kTrussNext];
+    ctl[kPeelLo] = lo;
+    ctl[kPeelHi] = hi;
+    ctl[kTrussNext] = kTrNone;
+    if (hi != lo) ctl[kPeelSubRounds] += 1u;
     const bool done = hi >= m, over = lo == hi;
-    if ((done || over) && hi != ctl[kTrLevelStart]) {             // the level queued somebody: its edges have truss l + 2
-        ctl[kTrLevels] += 1u;
-        ctl[kTrLevelStart] = hi;
-        ctl[kTrTop] = l;
+    if ((done || over) && hi != ctl[kPeelLevelStart]) {             // the level queued somebody: its edges have truss l + 2
+        ctl[kPeelLevels] += 1u;
+        ctl[kPeelLevelStart] = hi;
+        ctl[kPeelTop] = l;
     }
     if (done) {
-        ctl[kTrPhase] = kTrDone;
+        ctl[kPeelPhase] = kPeelDone;
     } else if (over) {
         // a scan that queued nobody saw every open edge, and nothing was decremented since: jump to the smallest word it saw
-        ctl[kTrL] = phase == kTrScan && next != kTrNone ? next : l + 1u;
-        ctl[kTrPhase] = kTrScan;
+        ctl[kPeelLevel] = phase == kPeelScan && next != kTrNone ? next : l + 1u;
+        ctl[kPeelPhase] = kPeelScan;
     } else {
-        ctl[kTrPhase] = kTrPeel;
+        ctl[kPeelPhase] = kPeelPeel;
     }
 }
 
 // out[j] = S[eid[j]] + add for every entry, 0 on the diagonal; with `gate` (the control record) only once the phase is "done"
 __global__ __launch_bounds__(256) void truss_write_kernel(const uint32_t *__restrict__ eid, const uint32_t *__restrict__ S, uint64_t nnz,
                                                           uint32_t add, uint32_t *__restrict__ out, const uint32_t *gate) {
-    if (gate && gate[kTrPhase] != kTrDone) return;
+    if (gate && gate[kPeelPhase] != kPeelDone) return;
     for (uint64_t j = blockIdx.x * 256u + threadIdx.x; j < nnz; j += gridDim.x * 256u) {
         const uint32_t e = eid[j];
         out[j] = e == kTrNone ? 0u : S[e] + add;
@@ -322,14 +296,14 @@ static TrLayout truss_layout(gl_spmv_plan p) {
     const size_t n = p->num_rows, nnz = (size_t)p->nnz, cap = nnz / 2u;
     TrLayout t;
     t.ctl = reinterpret_cast<uint32_t *>(p->d_truss_scratch);
-    t.off = t.ctl + kTrCtlBytes / 4u;
+    t.off = t.ctl + kRoundsCtlBytes / 4u;
     t.eid = t.off + n + 1u;
     t.esrc = t.eid + nnz;
     t.eent = t.esrc + cap;
     t.S = t.eent + cap;
     t.queue = t.S + cap;
     t.pos = t.queue + cap;
-    t.bytes = kTrCtlBytes + 4u * (n + 1u + nnz + 5u * cap);
+    t.bytes = kRoundsCtlBytes + 4u * (n + 1u + nnz + 5u * cap);
     return t;
 }
 
@@ -347,8 +321,8 @@ static int truss_prepare(gl_spmv_plan p, const char *who) {
     truss_number_kernel<<<std::max(1u, std::min<unsigned>(cdiv(n, 4u), (unsigned)ctx().num_cus * 8u)), 256, 0, s>>>(
         p->d_csr_indptr, p->d_csr_indices, n, p->csr_nz_base, t.off, t.eid, t.esrc, t.eent);
     GL_LAUNCH_CHECK();
-    uint32_t *&w = ctx().pinned_word;
-    if (!w) GL_HIP(hipHostMalloc((void **)&w, 64, hipHostMallocDefault));
+    uint32_t *w = nullptr;
+    GL_HIP(staging_words(&w));
     GL_HIP(hipMemcpyAsync(w, t.off + n, 4u, hipMemcpyDeviceToHost, s));
     GL_HIP(hipStreamSynchronize(s));
     if ((uint64_t)w[0] > p->nnz / 2u)
@@ -402,19 +376,19 @@ static int truss(gl_spmv_plan p, uint32_t *d_truss, uint32_t *d_support, uint64_
     const unsigned edge_grid = std::max(1u, std::min<unsigned>(cdiv(m, 256u), (unsigned)ctx().num_cus * 8u));
     const unsigned group_grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((((uint64_t)m << a.g_shift) + 255u) / 256u, cap_grid));
     const unsigned entry_grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nnz + 255u) / 256u, (uint64_t)ctx().num_cus * 8u));
-    uint32_t *&w = ctx().pinned_word;
-    if (!w) GL_HIP(hipHostMalloc((void **)&w, 64, hipHostMallocDefault));
-    static_assert(kTrRecordWords <= 12u, "the record and the 64-bit sum fit the page-locked staging words");
+    uint32_t *w = nullptr;
+    GL_HIP(staging_words(&w));
+    static_assert(kTrussRecordWords <= 12u, "the record and the 64-bit sum fit the page-locked staging words");
     truss_init_kernel<<<1, 64, 0, s>>>(t.ctl);
     GL_HIP(hipMemsetAsync(t.pos, 0xff, 4u * (size_t)m, s));
     truss_support_kernel<<<group_grid, 256, 0, s>>>(a);
     if (d_support) truss_write_kernel<<<entry_grid, 256, 0, s>>>(t.eid, t.S, nnz, 0u, d_support, nullptr);
     GL_LAUNCH_CHECK();
-    uint64_t launches = d_support ? 3 : 2, steps = 0;
+    uint64_t launches = d_support ? 3 : 2;
     if (debug_knob("truss_support_only", 0) != 0) {
         truss_write_kernel<<<entry_grid, 256, 0, s>>>(t.eid, t.S, nnz, 2u, d_truss, nullptr);
         GL_LAUNCH_CHECK();
-        GL_HIP(hipMemcpyAsync(w + 12, t.ctl + kTrSum, 8u, hipMemcpyDeviceToHost, s));
+        GL_HIP(hipMemcpyAsync(w + 12, t.ctl + kTrussSum, 8u, hipMemcpyDeviceToHost, s));
         GL_HIP(hipStreamSynchronize(s));
         if (h_stats) {
             uint64_t sum;
@@ -427,31 +401,33 @@ static int truss(gl_spmv_plan p, uint32_t *d_truss, uint32_t *d_support, uint64_
     }
     // every step that runs is a scan (one per level looked at: at most max support + 1 <= m of them) or a sub-round over a slice
     // that is not empty (every edge is in one slice): at most 2 m + 1 steps
-    const uint64_t max_steps = 2ull * m + 1ull;
-    for (;;) {
-        for (uint32_t i = 0; i < batch; i++) {
-            truss_scan_kernel<<<edge_grid, 256, 0, s>>>(a);
-            truss_peel_kernel<<<group_grid, 256, 0, s>>>(a);
-            truss_turn_kernel<<<1, 64, 0, s>>>(t.ctl, m);
-        }
-        truss_write_kernel<<<entry_grid, 256, 0, s>>>(t.eid, t.S, nnz, 2u, d_truss, t.ctl);   // (runs in the batch that ends the peel)
-        GL_LAUNCH_CHECK();
-        launches += 3ull * batch + 1ull;
-        steps += batch;
-        GL_HIP(hipMemcpyAsync(w, t.ctl, kTrRecordWords * 4u, hipMemcpyDeviceToHost, s));
-        GL_HIP(hipMemcpyAsync(w + 12, t.ctl + kTrSum, 8u, hipMemcpyDeviceToHost, s));
-        GL_HIP(hipStreamSynchronize(s));
-        if (w[kTrPhase] == kTrDone) break;
-        if (steps >= max_steps)
+    rc = rounds_run(
+        batch, 2ull * m + 1ull, launches,
+        [&] {
+            for (uint32_t i = 0; i < batch; i++) {
+                truss_scan_kernel<<<edge_grid, 256, 0, s>>>(a);
+                truss_peel_kernel<<<group_grid, 256, 0, s>>>(a);
+                truss_turn_kernel<<<1, 64, 0, s>>>(t.ctl, m);
+            }
+            truss_write_kernel<<<entry_grid, 256, 0, s>>>(t.eid, t.S, nnz, 2u, d_truss, t.ctl);   // (runs in the batch that ends the peel)
+            return 3ull * batch + 1ull;
+        },
+        [&] {
+            const hipError_t e = hipMemcpyAsync(w, t.ctl, kTrussRecordWords * 4u, hipMemcpyDeviceToHost, s);
+            return e != hipSuccess ? e : hipMemcpyAsync(w + 12, t.ctl + kTrussSum, 8u, hipMemcpyDeviceToHost, s);
+        },
+        [&] { return w[kPeelPhase] == kPeelDone ? kRoundsDone : kRoundsGoOn; },
+        [&](uint64_t steps) {
             return set_error(GL_ERR_HIP, "%s: internal error: not done after %llu steps on %u edges (level %u, slice [%u, %u), %u sub-rounds)",
-                             who, (unsigned long long)steps, m, w[kTrL], w[kTrLo], w[kTrHi], w[kTrSubRounds]);
-    }
+                             who, (unsigned long long)steps, m, w[kPeelLevel], w[kPeelLo], w[kPeelHi], w[kPeelSubRounds]);
+        });
+    if (rc != GL_OK) return rc;
     if (h_stats) {
         uint64_t sum;
         std::memcpy(&sum, w + 12, 8);
-        h_stats[0] = (uint64_t)w[kTrTop] + 2u;
-        h_stats[1] = w[kTrLevels];
-        h_stats[2] = w[kTrSubRounds];
+        h_stats[0] = (uint64_t)w[kPeelTop] + 2u;
+        h_stats[1] = w[kPeelLevels];
+        h_stats[2] = w[kPeelSubRounds];
         h_stats[3] = launches;
         h_stats[4] = m;
         h_stats[5] = sum / 3u;
