@@ -18,6 +18,7 @@
 //             gather and one add, no division); the bc update is fused into the same launch.  Level D only stores its coef.
 //             Every backward launch is gated by the count of non-finite sigmas on the device (path counts overflow f64 on
 //             lattice-like graphs): bc then stays as accumulate ? bc : 0.
+// The sweeps walk the rows of a level's queue slice, a thread per queued vertex, as gl_rows.h states the walk (a copy: see there).
 // DETERMINISM: no floating-point atomics.  Every vertex's sum is formed by ONE owner in an order that depends only on the row and
 // on bc_cut: the vertex's thread adds the first bc_cut entries in row order; a row still unfinished is taken over by its
 // wavefront -- lane l adds the entries b + l, b + 64 + l, ... in that order, the 64 partial sums meet in a fixed xor tree -- and
@@ -181,6 +182,8 @@ __global__ __launch_bounds__(256) void bc_sweep_kernel(BcSweepArgs a) {
             }
         }
         double acc = 0.0;
+        // the walk of gl_rows.h in a copy of this kernel's own (through rows_walk_* the sweeps were 1 - 2 % slower on one stand-in
+        // in two visits, EXPERIMENTS.md Round 21): the same wrap-free forms, the same padding column
         for (uint32_t step = 0; step < a.cut_steps && __any(beg < end); step++) {
             if (beg < end) {
                 uint32_t c[4];
@@ -265,8 +268,8 @@ static int bc_accumulate(gl_spmv_plan pin, gl_spmv_plan pout, const float *d_lev
     // A/B knobs (GRAPHLILY_DEBUG, read per call): bc_cut = entries a thread adds before the wavefront takes the row over (8, the
     // k-core peel's value; on two stand-ins 0 was 12 - 17 % slower and 64 within 2 %: profiles/bc.jsonl, EXPERIMENTS.md Round
     // 14), bc_grid = workgroups per compute unit of a sweep launch (4: an unmeasured guess)
-    const long cut = debug_knob("bc_cut", 8);
-    const unsigned per_cu = (unsigned)std::max<long>(1, std::min<long>(debug_knob("bc_grid", 4), 1024));
+    const long cut = debug_knob("bc_cut", 8), per_cu = debug_knob("bc_grid", 4);
+    auto shape_for = [&](uint32_t count) { return rows_walk_shape(count, cut, 1l << 30, per_cu); };   // (a launch per level)
     const BcScratch sc = bc_carve(pin->d_bc_scratch, n);
     double *sigma = d_sigma ? d_sigma : sc.sigma;
     // page-locked landing room of the read-backs: the control words, then the offsets
@@ -319,8 +322,7 @@ static int bc_accumulate(gl_spmv_plan pin, gl_spmv_plan pout, const float *d_lev
     a.bc = d_bc;
     a.scale = scale;
     a.n = n;
-    a.cut_steps = (uint32_t)std::max<long>(0, std::min<long>(cut, 1l << 30)) / 4u;
-    auto grid_for = [&](uint32_t count) { return std::max(1u, std::min<unsigned>(cdiv(count, 256u), (unsigned)ctx().num_cus * per_cu)); };
+    a.cut_steps = shape_for(n).cut_steps;
     a.row_ptr = pin->d_csr_indptr;
     a.row_idx = pin->d_csr_indices;
     a.nz_base = pin->csr_nz_base;
@@ -330,7 +332,7 @@ static int bc_accumulate(gl_spmv_plan pin, gl_spmv_plan pout, const float *d_lev
         if (a.count == 0u) continue;                              // (not a BFS result)
         a.queue = sc.queue + off[L];
         a.want = (float)(L - 1u);
-        bc_sweep_kernel<true><<<grid_for(a.count), 256, 0, s>>>(a);
+        bc_sweep_kernel<true><<<shape_for(a.count).grid, 256, 0, s>>>(a);
     }
     GL_LAUNCH_CHECK();
     a.row_ptr = pout->d_csr_indptr;
@@ -342,7 +344,7 @@ static int bc_accumulate(gl_spmv_plan pin, gl_spmv_plan pout, const float *d_lev
         a.queue = sc.queue + off[L];
         a.want = (float)(L + 1u);
         a.walk = L < D ? 1u : 0u;
-        bc_sweep_kernel<false><<<grid_for(a.count), 256, 0, s>>>(a);
+        bc_sweep_kernel<false><<<shape_for(a.count).grid, 256, 0, s>>>(a);
     }
     GL_LAUNCH_CHECK();
     if (h_stats) {

@@ -7,9 +7,8 @@
 //
 // The result depends on the levels alone, not on the push / pull / bottom-up mix that produced them, so nothing in the step
 // kernels or the recorded schedule changes.  Shape of the pass (EXPERIMENTS.md R7.*):
-//   * 64 rows per wavefront, a thread per row, four entries per step (the bottom-up scan's shape, gl_spmspv.hip); a row still
-//     undecided after `cut` entries is finished by the whole wavefront, 256 entries per step with coalesced index loads and
-//     one butterfly min per row -- the stand-ins have rows of 1e5 entries;
+//   * the walk of gl_rows.h over every row that is searched; a row still undecided after `cut` entries is finished by the whole
+//     wavefront with one butterfly min per row -- the stand-ins have rows of 1e5 entries;
 //   * where every row's columns ascend (established once per plan, gl_rows.h: rows_sorted) the first
 //     match is the minimum and the scan stops there; otherwise every entry is read;
 //   * the levels are gathered from a one-byte copy (3 MB instead of 12 MB for 3 M vertices: it stays in the L2) that a
@@ -88,39 +87,28 @@ __device__ __forceinline__ void parents_body(const ParentsArgs &a, const T *__re
             beg = a.row_ptr[local] - a.nz_base;
             end = a.row_ptr[local + 1u] - a.nz_base;
         }
-        bool done = !search;
-        for (uint32_t step = 0; step < a.cut_steps && __any(!done && beg < end); step++) {
-            if (!done && beg < end) {
-                uint32_t c[4];
+        // (a row that is not searched keeps beg == end; on sorted rows the first match decides: the row is finished)
+        rows_walk_thread(a.row_idx, beg, end, a.cut_steps, [&](const uint32_t(&c)[4], uint32_t at) {
 #pragma unroll
-                for (int u = 0; u < 4; u++) c[u] = beg + u < end ? a.row_idx[beg + u] : kNoParent;
-#pragma unroll
-                for (int u = 0; u < 4; u++)
-                    if (c[u] < a.num_cols && (W)lev[c[u]] == want) best = min(best, c[u]);
-                if (COUNT) reads += min(4u, end - beg);
-                beg += 4u;
-                if (SORTED && best != kNoParent) done = true;
-            }
-        }
-        // rows still undecided are finished by the whole wavefront, 256 entries per step (coalesced index loads)
-        for (uint64_t pending = __ballot(!done && beg < end); pending; pending &= pending - 1ull) {
-            const int src = __ffsll((unsigned long long)pending) - 1;
-            const uint32_t b = __shfl(beg, src), e = __shfl(end, src);
+            for (int u = 0; u < 4; u++)
+                if (c[u] < a.num_cols && (W)lev[c[u]] == want) best = min(best, c[u]);
+            if (COUNT) reads += min(4u, end - at);
+            return SORTED && best != kNoParent;
+        });
+        // rows still undecided: one butterfly min per row
+        rows_walk_takeover(beg, end, [&](int src, uint32_t b, uint32_t e) {
             const W w = __shfl(want, src);
             uint32_t m = kNoParent;
-            for (uint32_t base = b; base < e; base += 256u) {
+            rows_walk_wave(a.row_idx, b, e, lane, [&](const uint32_t(&c)[4], uint64_t base) {
 #pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    const uint32_t k = base + 64u * u + lane;
-                    const uint32_t c = k < e ? a.row_idx[k] : kNoParent;
-                    if (c < a.num_cols && (W)lev[c] == w) m = min(m, c);
-                }
-                if (COUNT && lane == 0) reads += min(256u, e - base);
-                if (SORTED && __any(m != kNoParent)) break;
-            }
+                for (int u = 0; u < 4; u++)
+                    if (c[u] < a.num_cols && (W)lev[c[u]] == w) m = min(m, c[u]);
+                if (COUNT && lane == 0) reads += min((uint64_t)256u, e - base);
+                return SORTED && __any(m != kNoParent);
+            });
             m = wave_min_u32(m);
             if ((int)lane == src) best = min(best, m);
-        }
+        });
         if (in) a.parent[local] = lv == (W)0 ? kNoParent : lv == (W)1 ? row : best;
         orphans += search && best == kNoParent ? 1u : 0u;
     }
@@ -154,8 +142,9 @@ static int parents_run(gl_spmv_plan p, const float *d_distance, uint32_t *d_pare
     if (d_orphans) GL_HIP(hipMemsetAsync(d_orphans, 0, 4, s));
     if (!rows) return GL_OK;
     // A/B knobs (GRAPHLILY_DEBUG, read per call): parents_cut = entries a thread reads before the wavefront takes the row
-    // over, parents_u8 = 0 gathers the floats, parents_early = 0 takes the full-scan path on sorted rows too
-    const long cut = debug_knob("parents_cut", 32);
+    // over, parents_grid = workgroups per compute unit, parents_u8 = 0 gathers the floats, parents_early = 0 takes the full-scan
+    // path on sorted rows too
+    const RowsWalkShape shape = rows_walk_shape(rows, debug_knob("parents_cut", 32), 1l << 30, debug_knob("parents_grid", 64));
     const bool u8 = debug_knob("parents_u8", 1) != 0 && ((uintptr_t)d_distance & 15u) == 0;
     const bool sorted = p->rows_sorted == 1 && debug_knob("parents_early", 1) != 0;
     if (u8) {
@@ -176,9 +165,8 @@ static int parents_run(gl_spmv_plan p, const float *d_distance, uint32_t *d_pare
     a.rows = rows;
     a.num_cols = p->num_cols;
     a.nz_base = p->csr_nz_base;
-    a.cut_steps = (uint32_t)std::max<long>(0, std::min<long>(cut, 1l << 30)) / 4u;
-    const unsigned nwords = (rows + 63u) / 64u;
-    const unsigned grid = std::min<unsigned>((nwords + 3u) / 4u, (unsigned)ctx().num_cus * (unsigned)std::max<long>(1, debug_knob("parents_grid", 64)));
+    a.cut_steps = shape.cut_steps;
+    const unsigned grid = shape.grid;
     if (sorted) {
         if (count) bfs_parents_kernel<true, true><<<grid, 256, 0, s>>>(a);
         else bfs_parents_kernel<true, false><<<grid, 256, 0, s>>>(a);

@@ -13,9 +13,8 @@
 // THE INVARIANT: parent[x] <= x at all times, and parent[x] lies in x's component.  Chains strictly descend, so they cannot
 // cycle; once every edge is united each component has exactly one root (parent[r] == r), its minimum.
 //
-// Hook, in the launch shape of gl_bfs_parents.hip: 64 rows per wavefront, a thread per row, four entries
-// per step; a row longer than `cut` entries is taken over by the whole wavefront, 256 entries per step with coalesced index
-// loads; shards index through row_begin and csr_nz_base.  For an edge (v, u): find both roots; if they differ,
+// Hook: the walk of gl_rows.h over every row, the wavefront taking over a row longer than `cut` entries;
+// shards index through row_begin and csr_nz_base.  For an edge (v, u): find both roots; if they differ,
 // atomicCAS(&parent[hi], hi, lo) with hi = max, lo = min.
 // MEMORY RULE: gl_rounds.h.  Inside the hook launch:
 //   * parent[] is atomic-only: a relaxed atomic load, an atomic min or a compare-and-swap; there is no plain load or store of
@@ -86,34 +85,22 @@ __global__ __launch_bounds__(256) void cc_hook_kernel(CcHookArgs a) {
             end = a.row_ptr[local + 1u] - a.nz_base;
         }
         uint32_t anc = row;                           // an ancestor-or-self of `row`: only ever descends
-        for (uint32_t step = 0; step < a.cut_steps && __any(beg < end); step++) {
-            if (beg < end) {
-                uint32_t c[4];
+        rows_walk_thread(a.row_idx, beg, end, a.cut_steps, [&](const uint32_t(&c)[4], uint32_t) {
 #pragma unroll
-                for (int u = 0; u < 4; u++) c[u] = beg + u < end ? a.row_idx[beg + u] : 0xffffffffu;
-#pragma unroll
-                for (int u = 0; u < 4; u++)
-                    if (c[u] < a.n && c[u] != row) anc = cc_unite(a.parent, anc, c[u]);
-                beg += 4u;
-            }
-        }
-        // rows still unfinished are taken over by the whole wavefront, 256 entries per step (coalesced index loads)
-        for (uint64_t pending = __ballot(beg < end); pending; pending &= pending - 1ull) {
-            const int src = __ffsll((unsigned long long)pending) - 1;
-            const uint32_t b = __shfl(beg, src), e = __shfl(end, src), v = __shfl(row, src);
-            uint32_t av = __shfl(anc, src);
-            for (uint32_t base = b; base < e; base += 256u) {
-                uint32_t c[4];
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    const uint32_t k = base + 64u * u + lane;
-                    c[u] = k < e ? a.row_idx[k] : 0xffffffffu;
-                }
+            for (int u = 0; u < 4; u++)
+                if (c[u] < a.n && c[u] != row) anc = cc_unite(a.parent, anc, c[u]);
+            return false;
+        });
+        rows_walk_takeover(beg, end, [&](int src, uint32_t b, uint32_t e) {
+            const uint32_t v = __shfl(row, src);
+            uint32_t av = __shfl(anc, src);                       // (every lane unites from the row's ancestor on its own)
+            rows_walk_wave(a.row_idx, b, e, lane, [&](const uint32_t(&c)[4], uint64_t) {
 #pragma unroll
                 for (int u = 0; u < 4; u++)
                     if (c[u] < a.n && c[u] != v) av = cc_unite(a.parent, av, c[u]);
-            }
-        }
+                return false;
+            });
+        });
     }
 }
 
@@ -155,7 +142,7 @@ static int cc_hook(gl_spmv_plan p, uint32_t *d_parent) {
     if (!rows) return GL_OK;
     // A/B knobs (GRAPHLILY_DEBUG, read per call): cc_cut = entries a thread reads before the wavefront takes the row over,
     // cc_grid = workgroups per compute unit
-    const long cut = debug_knob("cc_cut", 32);
+    const RowsWalkShape shape = rows_walk_shape(rows, debug_knob("cc_cut", 32), 1l << 30, debug_knob("cc_grid", 64));
     CcHookArgs a;
     a.row_ptr = p->d_csr_indptr;
     a.row_idx = p->d_csr_indices;
@@ -164,11 +151,8 @@ static int cc_hook(gl_spmv_plan p, uint32_t *d_parent) {
     a.rows = rows;
     a.n = p->num_cols;
     a.nz_base = p->csr_nz_base;
-    a.cut_steps = (uint32_t)std::max<long>(0, std::min<long>(cut, 1l << 30)) / 4u;
-    const unsigned per_cu = (unsigned)std::max<long>(1, std::min<long>(debug_knob("cc_grid", 64), 1024));
-    const unsigned nwords = (rows + 63u) / 64u;
-    const unsigned grid = std::max(1u, std::min<unsigned>((nwords + 3u) / 4u, (unsigned)ctx().num_cus * per_cu));
-    cc_hook_kernel<<<grid, 256, 0, ctx().stream>>>(a);
+    a.cut_steps = shape.cut_steps;
+    cc_hook_kernel<<<shape.grid, 256, 0, ctx().stream>>>(a);
     GL_LAUNCH_CHECK();
     return GL_OK;
 }

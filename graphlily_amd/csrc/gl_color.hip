@@ -24,9 +24,9 @@
 //          vertices are only decremented and keep their top bit: the per-vertex steps may run in any order.
 //   turn   (one thread)  lo = hi, hi = tail; a slice that is not empty is a round: rounds += 1, widest = max(widest, hi - lo);
 //          an empty one ends the run: done (with tail < n that cannot happen; it is flagged and reported as an internal error)
-// The round takes the launch shape of kcore_peel_kernel (gl_kcore.hip): a thread per queued vertex, four entries per step; a
-// row still unfinished after color_cut = 8 entries is taken over by the whole wavefront, 256 entries per step with coalesced
-// index loads; a wavefront that holds ONE vertex (most rounds are that narrow) hands the row to all its lanes at once.  Every
+// The round is the walk of gl_rows.h over the rows of the queued vertices, a thread per queued vertex; the wavefront takes over
+// a row still unfinished after color_cut = 8 entries, and walks it once per window (below); a wavefront that holds ONE vertex
+// (most rounds are that narrow) hands the row to all its lanes at once.  Every
 // step issues its state loads together, then its decrements, then its appends, so that up to four of each are in flight per
 // lane.  FREE COLOUR: a thread that finishes its row alone saw at most 64 entries, so a 64-bit mask decides (a row of d
 // entries cannot force a colour above d).  The wavefront searches in WINDOWS of 256 colours, four 64-bit masks per lane OR-ed
@@ -144,44 +144,32 @@ __global__ __launch_bounds__(256) void color_round_kernel(ColRoundArgs a) {
             end = a.row_ptr[v + 1u] - a.nz_base;
         }
         unsigned long long used = 0ull;                           // colours 0 .. 63 of the neighbours seen so far
-        for (uint32_t step = 0; step < thread_steps && __any(beg < end); step++) {
-            if (beg < end) {
-                uint32_t c[4];
+        rows_walk_thread(a.row_idx, beg, end, thread_steps, [&](const uint32_t(&c)[4], uint32_t) {
+            uint32_t w[4], old[4];
 #pragma unroll
-                for (int u = 0; u < 4; u++) c[u] = end - beg > (uint32_t)u ? a.row_idx[beg + u] : 0xffffffffu;   // (no wrap near 2^32 entries)
-                uint32_t w[4], old[4];
+            for (int u = 0; u < 4; u++) w[u] = (c[u] < a.n && c[u] != v) ? ga_load(a.state + c[u]) : kColNobody;
 #pragma unroll
-                for (int u = 0; u < 4; u++) w[u] = (c[u] < a.n && c[u] != v) ? ga_load(a.state + c[u]) : kColNobody;
+            for (int u = 0; u < 4; u++) old[u] = (w[u] & kColWait) ? ga_sub(a.state + c[u], 1u) : 0u;
 #pragma unroll
-                for (int u = 0; u < 4; u++) old[u] = (w[u] & kColWait) ? ga_sub(a.state + c[u], 1u) : 0u;
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    if (old[u] == (kColWait | 1u)) col_append(a, c[u]);
-                    if (w[u] < 64u) used |= 1ull << w[u];
-                }
-                beg += min(4u, end - beg);
+            for (int u = 0; u < 4; u++) {
+                if (old[u] == (kColWait | 1u)) col_append(a, c[u]);
+                if (w[u] < 64u) used |= 1ull << w[u];
             }
-        }
+            return false;
+        });
         // a row finished here has at most 4 cut_steps <= 64 entries, so its colour is at most 64: the mask decides
         if (in && beg >= end) {
             const uint32_t colour = ~used ? (uint32_t)__ffsll(~used) - 1u : 64u;
             ga_store(a.state + v, colour);
             top = max(top, colour);
         }
-        // rows still unfinished are taken over by the whole wavefront, 256 entries per step (coalesced index loads)
-        for (uint64_t pending = __ballot(beg < end); pending; pending &= pending - 1ull) {
-            const int src = __ffsll((unsigned long long)pending) - 1;
-            const uint32_t f = __shfl(first, src), b = __shfl(beg, src), e = __shfl(end, src), row = __shfl(v, src);
+        // a row taken over is walked from its FIRST entry, once per window
+        rows_walk_takeover(beg, end, [&](int src, uint32_t b, uint32_t e) {
+            const uint32_t f = __shfl(first, src), row = __shfl(v, src);
             // window `wbase`: the colours wbase .. wbase + 255; the first pass also does the decrements behind b
             for (uint32_t wbase = 0, release_from = b;; wbase += 256u, release_from = e) {
                 unsigned long long m0 = 0ull, m1 = 0ull, m2 = 0ull, m3 = 0ull;
-                for (uint64_t base = f; base < e; base += 256u) {
-                    uint32_t c[4];
-#pragma unroll
-                    for (int u = 0; u < 4; u++) {
-                        const uint64_t j = base + 64u * u + lane;
-                        c[u] = j < e ? a.row_idx[j] : 0xffffffffu;
-                    }
+                rows_walk_wave(a.row_idx, f, e, lane, [&](const uint32_t(&c)[4], uint64_t base) {
                     // the four words, then the four decrements, then the appends: each kind in flight together
                     uint32_t w[4], old[4];
 #pragma unroll
@@ -201,7 +189,8 @@ __global__ __launch_bounds__(256) void color_round_kernel(ColRoundArgs a) {
                             m3 |= (k >> 6) == 3u ? bit : 0ull;
                         }
                     }
-                }
+                    return false;
+                });
                 m0 = col_wave_or(m0);
                 m1 = col_wave_or(m1);
                 m2 = col_wave_or(m2);
@@ -219,7 +208,7 @@ __global__ __launch_bounds__(256) void color_round_kernel(ColRoundArgs a) {
                     break;
                 }
             }
-        }
+        });
     }
     // one atomic max per wavefront that coloured somebody above 0
 #pragma unroll
@@ -269,9 +258,8 @@ static int color(gl_spmv_plan p, const uint32_t *d_prio, uint32_t *d_color, uint
     // were 13 - 95 % slower; color_batch = (round, turn) pairs enqueued between two read-backs of the control record -- 64: the
     // best of 1 / 4 / 16 / 64 / 256 (256 equals it within 1 % and enqueues more idle launches); color_grid = workgroups per compute
     // unit of a round launch -- 4: 1 / 2 / 16 are within 1 %, most rounds do not fill one workgroup per unit
-    const long cut = debug_knob("color_cut", 8);
+    const RowsWalkShape shape = rows_walk_shape(n, debug_knob("color_cut", 8), 64, debug_knob("color_grid", 4));
     const uint32_t batch = (uint32_t)std::max<long>(1, std::min<long>(debug_knob("color_batch", 64), 4096));
-    const unsigned per_cu = (unsigned)std::max<long>(1, std::min<long>(debug_knob("color_grid", 4), 1024));
     uint32_t *ctl = reinterpret_cast<uint32_t *>(p->d_color_scratch);
     ColRoundArgs a;
     a.row_ptr = p->d_csr_indptr;
@@ -281,9 +269,8 @@ static int color(gl_spmv_plan p, const uint32_t *d_prio, uint32_t *d_color, uint
     a.ctl = ctl;
     a.n = n;
     a.nz_base = p->csr_nz_base;
-    a.cut_steps = (uint32_t)std::max<long>(0, std::min<long>(cut, 64)) / 4u;
-    const unsigned stream_grid = rows_stream_grid(n);
-    const unsigned round_grid = std::max(1u, std::min<unsigned>(cdiv(n, 256u), (unsigned)ctx().num_cus * per_cu));
+    a.cut_steps = shape.cut_steps;
+    const unsigned stream_grid = rows_stream_grid(n), round_grid = shape.grid;
     uint32_t *w = nullptr;
     GL_HIP(staging_words(&w));
     static_assert((kColRecordWords + kColReadWords - kColTail) * 4u <= 64u, "the record fits the page-locked staging words");

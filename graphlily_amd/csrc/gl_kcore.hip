@@ -20,9 +20,9 @@
 //                          tail == n: done (everything still queued has only queued neighbours)
 // The transient dip below k is harmless: a vertex's word never rises above k again -- it is raised only by the restore that is
 // paired with a dip -- so `old == k + 1` is seen once, and it never wraps: a vertex is decremented at most once per neighbour.
-// The peel takes the launch shape of cc_hook_kernel (gl_cc.hip): a thread per queued vertex, four entries per step; a row
-// still unfinished after kcore_cut = 8 entries is taken over by the whole wavefront, 256 entries per step with coalesced index
-// loads (late levels consist of hub rows).  A slice shorter than the launch has wavefronts gives every wavefront fewer vertices.
+// The peel is the walk of gl_rows.h over the rows of the queued vertices, a thread per queued vertex; the wavefront takes over
+// a row still unfinished after kcore_cut = 8 entries (late levels consist of hub rows).  A slice shorter than the launch has
+// wavefronts gives every wavefront fewer vertices.
 // MEMORY RULE and GATING: gl_rounds.h.  Atomic-only inside a peel launch: deg[] and the tail (the queue slice and the control
 // record were written by earlier launches; queue words written now are read by later ones).  The host enqueues (scan, peel,
 // turn) x kcore_batch, of which exactly one of scan / peel runs per triple -- a scan that finds the phase "peel" returns at once
@@ -94,33 +94,21 @@ __global__ __launch_bounds__(256) void kcore_peel_kernel(KcPeelArgs a) {
             beg = a.row_ptr[v] - a.nz_base;
             end = a.row_ptr[v + 1u] - a.nz_base;
         }
-        for (uint32_t step = 0; step < a.cut_steps && __any(beg < end); step++) {
-            if (beg < end) {
-                uint32_t c[4];
+        rows_walk_thread(a.row_idx, beg, end, a.cut_steps, [&](const uint32_t(&c)[4], uint32_t) {
 #pragma unroll
-                for (int u = 0; u < 4; u++) c[u] = end - beg > (uint32_t)u ? a.row_idx[beg + u] : 0xffffffffu;   // (no wrap near 2^32 entries)
-#pragma unroll
-                for (int u = 0; u < 4; u++)
-                    if (c[u] < a.n && c[u] != v) kc_relax(a, c[u], k);
-                beg += min(4u, end - beg);
-            }
-        }
-        // rows still unfinished are taken over by the whole wavefront, 256 entries per step (coalesced index loads)
-        for (uint64_t pending = __ballot(beg < end); pending; pending &= pending - 1ull) {
-            const int src = __ffsll((unsigned long long)pending) - 1;
-            const uint32_t b = __shfl(beg, src), e = __shfl(end, src), row = __shfl(v, src);
-            for (uint64_t base = b; base < e; base += 256u) {
-                uint32_t c[4];
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    const uint64_t j = base + 64u * u + lane;
-                    c[u] = j < e ? a.row_idx[j] : 0xffffffffu;
-                }
+            for (int u = 0; u < 4; u++)
+                if (c[u] < a.n && c[u] != v) kc_relax(a, c[u], k);
+            return false;
+        });
+        rows_walk_takeover(beg, end, [&](int src, uint32_t b, uint32_t e) {
+            const uint32_t row = __shfl(v, src);
+            rows_walk_wave(a.row_idx, b, e, lane, [&](const uint32_t(&c)[4], uint64_t) {
 #pragma unroll
                 for (int u = 0; u < 4; u++)
                     if (c[u] < a.n && c[u] != row) kc_relax(a, c[u], k);
-            }
-        }
+                return false;
+            });
+        });
     }
 }
 
@@ -172,9 +160,8 @@ static int kcore(gl_spmv_plan p, uint32_t *d_core, uint32_t *d_order, uint32_t *
     // kcore_batch = (scan, peel, turn) triples enqueued between two read-backs of the control record (8 and 64: the best of
     // 8 / 32 / 128 and of 1 / 4 / 16 / 64, EXPERIMENTS.md Round 13), kcore_grid = workgroups per compute unit of a peel launch
     // (4: an unmeasured guess, no A/B was run)
-    const long cut = debug_knob("kcore_cut", 8);
+    const RowsWalkShape shape = rows_walk_shape(n, debug_knob("kcore_cut", 8), 1l << 30, debug_knob("kcore_grid", 4));
     const uint32_t batch = (uint32_t)std::max<long>(1, std::min<long>(debug_knob("kcore_batch", 64), 4096));
-    const unsigned per_cu = (unsigned)std::max<long>(1, std::min<long>(debug_knob("kcore_grid", 4), 1024));
     uint32_t *ctl = reinterpret_cast<uint32_t *>(p->d_kcore_scratch);
     KcPeelArgs a;
     a.row_ptr = p->d_csr_indptr;
@@ -184,9 +171,8 @@ static int kcore(gl_spmv_plan p, uint32_t *d_core, uint32_t *d_order, uint32_t *
     a.ctl = ctl;
     a.n = n;
     a.nz_base = p->csr_nz_base;
-    a.cut_steps = (uint32_t)std::max<long>(0, std::min<long>(cut, 1l << 30)) / 4u;
-    const unsigned stream_grid = rows_stream_grid(n);
-    const unsigned peel_grid = std::max(1u, std::min<unsigned>(cdiv(n, 256u), (unsigned)ctx().num_cus * per_cu));
+    a.cut_steps = shape.cut_steps;
+    const unsigned stream_grid = rows_stream_grid(n), peel_grid = shape.grid;
     uint32_t *w = nullptr;
     GL_HIP(staging_words(&w));
     static_assert(kPeelRecordWords * 4u <= 64u, "the record fits the page-locked staging words");

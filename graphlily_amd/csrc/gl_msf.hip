@@ -14,9 +14,9 @@
 // ones: none), first[n] (the first entry above the diagonal of every row, found once per call), a LIST of the forest edges
 // {entry, smaller end} and a CONTROL RECORD {done, rounds, forest edges, ...} + one "changed" word per pointer-doubling step.
 // ONE ROUND:
-//   scan    (the hot path) streams the entries above the diagonal in the launch shape of cc_hook_kernel: a thread per row, four
-//           entries per step; a row longer than `cut` entries is taken over by the whole wavefront, 256 entries per step with
-//           coalesced loads.  An entry whose ends lie in different components is a candidate for both.  The row's own side is
+//   scan    (the hot path) streams the entries above the diagonal with the walk of gl_rows.h, the wavefront taking over a row
+//           longer than `cut` such entries; a weight word is loaded beside every column.
+//           An entry whose ends lie in different components is a candidate for both.  The row's own side is
 //           reduced in registers (across the wavefront by shuffles for a taken-over row): one atomic min per row; the far side
 //           costs one atomic min per candidate, filtered by a relaxed atomic load of the word it would lower (msf_offer: a thread
 //           also remembers an upper bound of the word it last offered to, and skips what is not below it without a load).
@@ -123,60 +123,51 @@ __global__ __launch_bounds__(256) void msf_scan_kernel(MsfArgs a) {
         unsigned long long mine = kMsfNone;               // the smallest candidate of this row
         uint32_t hc = 0xffffffffu;                        // (no component: vertices are below n <= 2^32 - 1)
         unsigned long long hv = 0;
-        for (uint32_t step = 0; step < a.cut_steps && __any(beg < end); step++) {
-            if (beg < end) {
-                uint32_t c[4], w[4];
+        // the weight words first: nothing sits between them and the index loads, so a step's loads are in flight together
+        rows_walk_thread(a.row_idx, beg, end, a.cut_steps, [&](const uint32_t(&c)[4], uint32_t at) {
+            uint32_t w[4];
 #pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    const bool in = beg + u < end;
-                    c[u] = in ? a.row_idx[beg + u] : 0xffffffffu;
-                    w[u] = in ? a.weight[beg + u] : 0u;
-                }
+            for (int u = 0; u < 4; u++) w[u] = end - at > (uint32_t)u ? a.weight[at + u] : 0u;
 #pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    if (c[u] >= a.n) continue;
-                    const uint32_t cu = a.comp[c[u]];
-                    if (cu == cv) continue;
-                    const unsigned long long word = msf_word(w[u], beg + u);
-                    mine = min(mine, word);
-                    msf_offer(a.best, cu, word, a.filter, hc, hv);
-                }
-                beg += 4u;
+            for (int u = 0; u < 4; u++) {
+                if (c[u] >= a.n) continue;
+                const uint32_t cu = a.comp[c[u]];
+                if (cu == cv) continue;
+                const unsigned long long word = msf_word(w[u], at + u);
+                mine = min(mine, word);
+                msf_offer(a.best, cu, word, a.filter, hc, hv);
             }
-        }
-        // rows still unfinished are taken over by the whole wavefront, 256 entries per step (coalesced loads)
-        for (uint64_t pending = __ballot(beg < end); pending; pending &= pending - 1ull) {
-            const int src = __ffsll((unsigned long long)pending) - 1;
-            const uint32_t b = __shfl(beg, src), e = __shfl(end, src), cr = __shfl(cv, src);
+            return false;
+        });
+        rows_walk_takeover(beg, end, [&](int src, uint32_t b, uint32_t e) {
+            const uint32_t cr = __shfl(cv, src);
             unsigned long long low = kMsfNone;
             if ((int)lane == src) {                       // (what its own thread found joins the wavefront's minimum)
                 low = mine;
                 mine = kMsfNone;
             }
-            for (uint32_t base = b; base < e; base += 256u) {
-                uint32_t c[4], w[4];
+            rows_walk_wave(a.row_idx, b, e, lane, [&](const uint32_t(&c)[4], uint64_t base) {
+                uint32_t w[4];
 #pragma unroll
                 for (int u = 0; u < 4; u++) {
-                    const uint32_t k = base + 64u * u + lane;
-                    const bool in = k < e && k >= base;   // (k >= base: no wrap at the end of the 32-bit range)
-                    c[u] = in ? a.row_idx[k] : 0xffffffffu;
-                    w[u] = in ? a.weight[k] : 0u;
+                    const uint64_t j = base + 64u * u + lane;
+                    w[u] = j < e ? a.weight[j] : 0u;
                 }
 #pragma unroll
                 for (int u = 0; u < 4; u++) {
                     if (c[u] >= a.n) continue;
                     const uint32_t cu = a.comp[c[u]];
                     if (cu == cr) continue;
-                    const unsigned long long word = msf_word(w[u], base + 64u * u + lane);
+                    const unsigned long long word = msf_word(w[u], (uint32_t)base + 64u * u + lane);   // (an entry: below 2^32)
                     low = min(low, word);
                     msf_offer(a.best, cu, word, a.filter, hc, hv);
                 }
-                if (base + 256u < base) break;
-            }
+                return false;
+            });
 #pragma unroll
             for (int d = 1; d < 64; d <<= 1) low = min(low, msf_shfl_xor(low, d));
             if (lane == 0u && low != kMsfNone) msf_offer(a.best, cr, low, a.filter, hc, hv);
-        }
+        });
         if (mine != kMsfNone) msf_offer(a.best, cv, mine, a.filter, hc, hv);
     }
 }
@@ -330,8 +321,7 @@ static int msf(gl_spmv_plan p, const float *d_weight, uint32_t *d_in_forest, uin
     // A/B knobs (GRAPHLILY_DEBUG, read per call; EXPERIMENTS.md Round 19): msf_cut = entries above the diagonal a thread reads before
     // the wavefront takes the row over, msf_grid = workgroups per compute unit of a scan launch, msf_batch = rounds enqueued between
     // two read-backs of the control record, msf_filter = 0 sends every candidate's atomic min without the load in front of it
-    const long cut = debug_knob("msf_cut", 32);
-    const unsigned per_cu = (unsigned)std::max<long>(1, std::min<long>(debug_knob("msf_grid", 64), 1024));
+    const RowsWalkShape shape = rows_walk_shape(n, debug_knob("msf_cut", 32), 1l << 30, debug_knob("msf_grid", 64));
     const uint32_t batch = (uint32_t)std::max<long>(1, std::min<long>(debug_knob("msf_batch", 4), 64));
     rc = plan_scratch(p->d_msf_scratch, msf_layout(p).bytes, who, "control record, best edges, two component arrays, row starts and edge list");
     if (rc != GL_OK) return rc;
@@ -347,10 +337,9 @@ static int msf(gl_spmv_plan p, const float *d_weight, uint32_t *d_in_forest, uin
     a.best = t.best;
     a.n = n;
     a.nz_base = p->csr_nz_base;
-    a.cut_steps = (uint32_t)std::max<long>(0, std::min<long>(cut, 1l << 30)) / 4u;
+    a.cut_steps = shape.cut_steps;
     a.filter = debug_knob("msf_filter", 1) != 0 ? 1u : 0u;
-    const unsigned nwords = (n + 63u) / 64u;
-    const unsigned scan_grid = std::max(1u, std::min<unsigned>((nwords + 3u) / 4u, (unsigned)ctx().num_cus * per_cu));
+    const unsigned scan_grid = shape.grid;
     uint32_t jumps = 1;                                           // ceil(log2 n) + 1
     while ((1ull << (jumps - 1u)) < n) jumps++;
     static_assert(kMsfChanged * 4u + kMsfMaxJumps * 4u <= kRoundsCtlBytes && kMsfMaxJumps >= 33u, "one word per step");

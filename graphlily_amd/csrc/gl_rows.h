@@ -1,7 +1,8 @@
 // The plain CSR row copy that a GL_PLAN_BOOLEAN plan keeps (gl_spmv_plan.h: d_csr_indptr / d_csr_indices / csr_nz_base), as the
 // graph kernels that walk it see it -- gl_bfs_parents, gl_cc, gl_tc, gl_kcore, gl_color, gl_truss, gl_msf (which also takes a
 // value per entry of the copy from its caller), gl_bc: what a caller may require of it, the
-// verdicts about it that the plan caches, and the few helpers every such kernel wants.  gl_rows.hip holds the check kernels.
+// verdicts about it that the plan caches, the few helpers every such kernel wants, and the walk over a row -- a thread per row,
+// then the wavefront -- that five of them run (rows_walk_*, at the end).  gl_rows.hip holds the check kernels.
 // gl_rounds.h, on top of this, holds what the kernels that run in rounds over a queue share: the atomics of their memory rule,
 // the queue append, the peel record and the gated host loop.
 #ifndef GL_ROWS_H_
@@ -41,6 +42,16 @@ int rows_check_transpose(gl_spmv_plan p, gl_spmv_plan partner, bool *ok);
 
 // the grid of a streaming pass, a thread per vertex
 inline unsigned rows_stream_grid(uint32_t n) { return std::max(1u, std::min<unsigned>(cdiv(n, 256u), (unsigned)ctx().num_cus * 8u)); }
+// the launch of a walk (below) over `items` rows, 64 per wavefront, from its caller's two A/B knobs: `cut` = entries a thread reads
+// before the wavefront takes the row over (0 .. cut_cap, in steps of four), `per_cu` = workgroups per compute unit (1 .. 1024)
+struct RowsWalkShape {
+    uint32_t cut_steps;
+    unsigned grid;
+};
+inline RowsWalkShape rows_walk_shape(uint32_t items, long cut, long cut_cap, long per_cu) {
+    const unsigned most = (unsigned)ctx().num_cus * (unsigned)std::max<long>(1, std::min<long>(per_cu, 1024));
+    return {(uint32_t)std::max<long>(0, std::min<long>(cut, cut_cap)) / 4u, std::max(1u, std::min<unsigned>(cdiv(items, 256u), most))};
+}
 // d_out[v] = v for v < n, n >= 1: one launch (the answer of the calls that find a graph without entries)
 int rows_iota(uint32_t *d_out, uint32_t n);
 
@@ -63,6 +74,55 @@ __device__ __forceinline__ uint32_t rows_lower_bound(P s, uint32_t n, uint32_t w
         n -= half;
     }
     return lo;
+}
+
+// THE WALK over the entries [beg, end) of one row per lane, 64 rows per wavefront (gl_bfs_parents, gl_cc, gl_kcore, gl_msf and
+// gl_color run it; DESIGN.md 4.13.  bc_sweep_kernel of gl_bc keeps a copy of its own, in the same forms: through these templates
+// its accumulate figure on one stand-in was 1 - 2 % above the parent's worse run in two visits, EXPERIMENTS.md Round 21):
+//   rows_walk_thread    a thread per row, four entries per step, for at most cut_steps steps while any lane of the wavefront has
+//                       entries left: body(c, beg) gets the columns of the entries beg .. beg + 3 and returns true when the row
+//                       needs no further entry (the row is then finished: beg = end); beg moves on behind what was read
+//   rows_walk_takeover  every row still unfinished (beg < end) is taken over by the whole wavefront, one row after the other in
+//                       lane order: per_row(src, b, e) gets the lane that owns the row and that lane's beg and end; whatever
+//                       else of that lane the caller needs it shuffles from src itself
+//   rows_walk_wave      the wavefront reads [b, e) 256 entries per step, lane l the entries base + l, base + 64 + l, base + 128 + l
+//                       and base + 192 + l (coalesced index loads): body(c, base) returns true -- the same in every lane -- to stop
+// PADDING: a position at or behind the row's end reads no memory and has the column 0xffffffff, which is also the column of a
+// zero-valued entry and is below no num_cols: a body's test `c[u] < n` drops both.
+// NO WRAP, whatever the offsets (a row may end at entry 2^32 - 1): the thread tests `end - beg > u` (never beg + u < end) and
+// advances by min(4, end - beg), so no offset is formed behind end; the wavefront's base and positions are 64-bit, below 2^32 + 256.
+// Everything a body loads beside the columns (levels, weights) it loads first thing, so that those loads and the index loads of
+// the step are in flight together; a body that never stops early returns a constant false, which costs nothing.
+template <typename Body>
+__device__ __forceinline__ void rows_walk_thread(const uint32_t *__restrict__ row_idx, uint32_t &beg, uint32_t end, uint32_t cut_steps,
+                                                 Body &&body) {
+    for (uint32_t step = 0; step < cut_steps && __any(beg < end); step++) {
+        if (beg < end) {
+            uint32_t c[4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) c[u] = end - beg > (uint32_t)u ? row_idx[beg + u] : 0xffffffffu;
+            beg = body(c, beg) ? end : beg + min(4u, end - beg);
+        }
+    }
+}
+template <typename PerRow>
+__device__ __forceinline__ void rows_walk_takeover(uint32_t beg, uint32_t end, PerRow &&per_row) {
+    for (uint64_t pending = __ballot(beg < end); pending; pending &= pending - 1ull) {
+        const int src = __ffsll((unsigned long long)pending) - 1;
+        per_row(src, (uint32_t)__shfl(beg, src), (uint32_t)__shfl(end, src));
+    }
+}
+template <typename Body>
+__device__ __forceinline__ void rows_walk_wave(const uint32_t *__restrict__ row_idx, uint32_t b, uint32_t e, uint32_t lane, Body &&body) {
+    for (uint64_t base = b; base < e; base += 256u) {
+        uint32_t c[4];
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            const uint64_t j = base + 64u * u + lane;
+            c[u] = j < e ? row_idx[j] : 0xffffffffu;
+        }
+        if (body(c, base)) break;
+    }
 }
 
 }  // namespace gl
