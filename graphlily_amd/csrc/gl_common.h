@@ -33,6 +33,9 @@ static inline long env_long(const char *name, long dflt) {
 // decision the planner would otherwise take from the matrix (row blocks x column segments, hot table size, helper mode, load
 // width, SpMSpV tile height, the BFS schedule's work thresholds ...), so that a test can drive every code path on one small
 // matrix.  Read at the call that takes the decision (plan creation, mostly).
+// The boolean stream (gl_spmv_bool.hip), both read when the plan is created: bool_compress = 0 keeps the 4-byte entries, 1 (default)
+// codes by the planner's rule, 2 also reports the group counts, 3 takes the 10-bit decoder wherever the groups can be coded;
+// bool_keep = 0 / 1 forces the kernels' non-temporal / cache-keeping load twin (absent or -1: by the plan's size).
 static inline long debug_knob(const char *key, long dflt) {
     const char *e = getenv("GRAPHLILY_DEBUG");
     if (!e) return dflt;

@@ -128,7 +128,8 @@ struct BoolElem {   // one lane's share of a group
     uint32_t v[kBoolLane];
 };
 constexpr uint32_t kBoolGroupBytesC = kBoolGroup * 3u;   // compressed group: 2 B of row slot + 1 B of delta per entry
-// KEEP bit 0: no non-temporal hint -- plans that fit the Infinity Cache stay there between runs (gl_common.h);
+// KEEP bit 0: no non-temporal hint -- plans that fit the Infinity Cache stay there between runs (gl_common.h); chosen by the plan's
+// size unless GRAPHLILY_DEBUG bool_keep = 0 / 1 was set when the plan was created (gl_spmv_plan_s::bool_keep);
 // KEEP bit 1: the delta-coded 3-byte stream (v[0], v[1]: four 16-bit row slots, v[2]: four 8-bit deltas, v[3] unused; 12 bytes per lane);
 // KEEP bit 2 (with bit 1): some delta of the plan needs 10 bits, and bits 8..9 sit on top of the 14-bit row slots
 template <int KEEP>
@@ -626,7 +627,7 @@ static int launch_bool_variant(gl_spmv_plan p, const BoolArgs &a, hipStream_t s)
     // (the CSR copy for the bottom-up BFS step is not streamed by this kernel)
     const size_t rows_bytes = p->d_csr_indptr ? ((size_t)(p->row_end - p->row_begin) + 1u) * 4u + (size_t)p->nnz * 4u : 0u;
     const size_t streamed = p->device_bytes - std::min<size_t>(rows_bytes, p->device_bytes);
-    const bool keep = streamed <= keep_bytes && streamed >= keep_min;
+    const bool keep = p->bool_keep >= 0 ? p->bool_keep != 0 : (streamed <= keep_bytes && streamed >= keep_min);
     if (p->bool_compressed == 2) return keep ? launch_bool_keep<MASK, FUSED, 7>(p, a, s) : launch_bool_keep<MASK, FUSED, 6>(p, a, s);
     if (p->bool_compressed) return keep ? launch_bool_keep<MASK, FUSED, 3>(p, a, s) : launch_bool_keep<MASK, FUSED, 2>(p, a, s);
     return keep ? launch_bool_keep<MASK, FUSED, 1>(p, a, s) : launch_bool_keep<MASK, FUSED, 0>(p, a, s);
@@ -731,7 +732,7 @@ int bool_plan_bfs_shard_step(gl_spmv_plan p, BfsPushArgs pa, BfsShardArgs sa, hi
     static const size_t keep_min = (size_t)64 << 20;
     const size_t rows_bytes = p->d_csr_indptr ? ((size_t)(p->row_end - p->row_begin) + 1u) * 4u + (size_t)p->nnz * 4u : 0u;
     const size_t streamed = p->device_bytes - std::min<size_t>(rows_bytes, p->device_bytes);
-    const bool keep = streamed <= keep_bytes && streamed >= keep_min;
+    const bool keep = p->bool_keep >= 0 ? p->bool_keep != 0 : (streamed <= keep_bytes && streamed >= keep_min);
     if (p->bool_compressed == 2) {
         if (p->segments > 1) return keep ? launch_shard_step<2, 7>(grid, a, pa, sa, s) : launch_shard_step<2, 6>(grid, a, pa, sa, s);
         return keep ? launch_shard_step<1, 7>(grid, a, pa, sa, s) : launch_shard_step<1, 6>(grid, a, pa, sa, s);

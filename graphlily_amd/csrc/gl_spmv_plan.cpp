@@ -832,6 +832,8 @@ int gl_spmv_plan_create_ex(gl_spmv_plan *plan, uint32_t num_rows, uint32_t num_c
         p->values_finite = gl::values_finite_host(a);
         rc = gl::bool_plan_build(p.get(), h_indptr, h_indices, h_data);
         if (rc == GL_OK) rc = gl::bool_plan_compress(p.get());
+        const long keep = gl::debug_knob("bool_keep", -1);
+        p->bool_keep = (keep == 0 || keep == 1) ? (int8_t)keep : (int8_t)-1;
     } else {
         rc = gl::plan_general(p.get(), a, k);
     }

@@ -223,6 +223,7 @@ struct gl_spmv_plan_s {
     // (||,&&)-only layout (GL_PLAN_BOOLEAN): 4-byte pattern entries, x packed to bits once per run
     bool boolean = false;
     int bool_compressed = 0;       // the groups are delta-coded, 3 bytes per entry (bool_plan_compress): 1 = 8-bit deltas, 2 = 10-bit
+    int8_t bool_keep = -1;         // the stream kernels' cache-hint twin: -1 by the plan's size, 0 / 1 forced (GRAPHLILY_DEBUG bool_keep, at creation)
     uint32_t nphases = 0;
     uint4 *d_spans = nullptr;      // {first word of the phase in xbits, first group, end group, lo4 | hi4 << 16}
     uint32_t *d_xbits = nullptr;   // nphases * kBoolPhaseWords words

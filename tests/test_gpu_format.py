@@ -14,6 +14,7 @@ from graphlily_amd import capi, datasets, io
 from oracle import oracle as O
 
 from helpers import named_matrix, to_oracle, set_knob
+from test_bool_stream_cpu import coder, expected_form
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -239,6 +240,11 @@ def test_plan_creation_refuses_a_malformed_matrix(gpu, where, monkeypatch):
     assert capi.SpMSpVPlan(c.num_rows, c.num_cols, c.adj_indptr, c.adj_indices, c.adj_data).info()["nnz"] == m.nnz
 
 
+# the form of the boolean stream (0: 4-byte entries, 1: 8-bit deltas, 2: 10-bit deltas) each named matrix takes under
+# bool_compress = 1 and = 3: rmat_sym_50K and uniform_10K_10 hold a few groups with a delta above 255, which a stream this small keeps raw
+NAMED_FORMS = {"rmat_sym_50K": {1: 0, 3: 2}, "gplus_small": {1: 1, 3: 2}, "dense_1K": {1: 1, 3: 2}, "uniform_10K_10": {1: 0, 3: 2}}
+
+
 def _bool_plan(m, data, knob, monkeypatch):
     set_knob(monkeypatch, "bool_compress", knob)
     return capi.SpMVPlan(m.num_rows, m.num_cols, m.adj_indptr, m.adj_indices, data, 0, m.num_rows, flags=capi.GL_PLAN_BOOLEAN)
@@ -249,47 +255,60 @@ def _bool_plan(m, data, knob, monkeypatch):
 def test_boolean_stream_delta_coding_decodes_to_the_4_byte_entries(gpu, name, where, monkeypatch):
     """csrc/gl_spmv_bool.hip bool_plan_compress: the 3-byte stream (16-bit row slots + 8-bit column deltas, 768 bytes per group of
     256) names exactly the entries of the 4-byte stream it was made from -- padding entries keep the ghost row slot and repeat
-    their predecessor's column -- and both plans compute the oracle's result."""
+    their predecessor's column -- and every plan computes the oracle's result.  Which form a matrix takes under bool_compress = 1
+    and = 3 is what the coder's restatement (tests/test_bool_stream_cpu.py) predicts from the 4-byte stream: coded under 1 only
+    if no group has a delta above 255 (these streams are far below the 224 MB from which the 10-bit decoder pays), coded under 3
+    unless some group cannot be coded at all; the coded bytes are the restatement's, bit for bit."""
     m = named_matrix(name)
     io.util_round_csr_matrix_dim(m, 128, 128)
     rng = np.random.default_rng(11)
     data = (rng.random(m.nnz) < 0.9).astype(np.float32)
     set_knob(monkeypatch, "bool_compress", 0)
     raw = capi.SpMVPlan(m.num_rows, m.num_cols, m.adj_indptr, m.adj_indices, data, 0, m.num_rows, flags=capi.GL_PLAN_BOOLEAN | where)
-    set_knob(monkeypatch, "bool_compress", 1)
-    cod = capi.SpMVPlan(m.num_rows, m.num_cols, m.adj_indptr, m.adj_indices, data, 0, m.num_rows, flags=capi.GL_PLAN_BOOLEAN | where)
     groups = raw.info()["groups"]
-    assert cod.info()["groups"] == groups
-    er, ec = raw.export("entries"), cod.export("entries")
+    er = raw.export("entries")
     assert er.nbytes == groups * 1024
-    for nm in ("bases", "units", "hub_rows", "spans"):
-        assert np.array_equal(raw.export(nm), cod.export(nm)), nm
+    predicted, bad, wide = coder(er)
     om = to_oracle(m)
     om.adj_data = data
     x = (rng.random(m.num_cols) < 0.05).astype(np.float32)
     dx = capi.DeviceBuffer.from_host(x)
     want = O.spmv(om, x, 1, 0.0)
-    for p in (raw, cod):
+    dy = capi.DeviceBuffer(4 * m.num_rows)
+    raw.run(dx, None, dy, 1, 0.0, 0)
+    assert np.array_equal(dy.read(np.float32, m.num_rows), want)
+    for knob in (1, 3):
+        set_knob(monkeypatch, "bool_compress", knob)
+        cod = capi.SpMVPlan(m.num_rows, m.num_cols, m.adj_indptr, m.adj_indices, data, 0, m.num_rows, flags=capi.GL_PLAN_BOOLEAN | where)
+        assert cod.info()["groups"] == groups
+        ec = cod.export("entries")
+        for nm in ("bases", "units", "hub_rows", "spans"):
+            assert np.array_equal(raw.export(nm), cod.export(nm)), nm
         dy = capi.DeviceBuffer(4 * m.num_rows)
-        p.run(dx, None, dy, 1, 0.0, 0)
-        assert np.array_equal(dy.read(np.float32, m.num_rows), want)
-    if ec.nbytes == er.nbytes:       # a gap of more than 255 columns somewhere: the plan keeps the 4-byte stream
-        assert np.array_equal(er, ec)
-        return
-    assert ec.nbytes == groups * 768 and cod.info()["device_bytes"] == raw.info()["device_bytes"] - groups * 256
-    g = ec.view(np.uint8).reshape(groups, 64, 12)                   # lane l: 8 bytes of row slots, 4 of deltas: entries 4 l .. 4 l + 3
-    slots = g[:, :, :8].copy().view(np.uint16).reshape(groups, 256).astype(np.uint32)
-    delta = g[:, :, 8:].reshape(groups, 256).astype(np.uint32) | ((slots >> 14) << 8)      # bits 8..9 of a delta ride on its row slot
-    slots &= 0x3fff
-    idx = np.cumsum(delta, axis=1)
-    r = er.reshape(groups, 256)
-    r_row, r_idx = (r >> 5) & 0x3fff, ((r >> 19) << 5) | (r & 31)
-    assert np.array_equal(slots, r_row)
-    real = r_row != 0x3fff
-    assert np.array_equal(idx[real], r_idx[real])
-    # padding: the predecessor's column again
-    prev = np.concatenate([np.zeros((groups, 1), np.uint32), idx[:, :-1].astype(np.uint32)], axis=1)
-    assert np.array_equal(idx[~real], prev[~real])
+        cod.run(dx, None, dy, 1, 0.0, 0)
+        assert np.array_equal(dy.read(np.float32, m.num_rows), want), knob
+        form = expected_form(bad, wide, knob)
+        assert form == NAMED_FORMS[name][knob], "%s bool_compress=%d: of %d groups %d cannot be coded, %d need 10-bit deltas" % (name, knob, groups, bad, wide)
+        if form == 0:                    # a group that cannot be coded, or (knob 1) a delta above 255 somewhere: the 4-byte stream stays
+            assert np.array_equal(er, ec), (name, knob)
+            assert cod.info()["device_bytes"] == raw.info()["device_bytes"]
+            continue
+        assert ec.nbytes == groups * 768 and cod.info()["device_bytes"] == raw.info()["device_bytes"] - groups * 256
+        g = ec.view(np.uint8).reshape(groups, 64, 12)                   # lane l: 8 bytes of row slots, 4 of deltas: entries 4 l .. 4 l + 3
+        assert np.array_equal(g, predicted), (name, knob)
+        slots = g[:, :, :8].copy().view(np.uint16).reshape(groups, 256).astype(np.uint32)
+        assert bool((slots >> 14).any()) == (wide > 0), (name, knob)
+        delta = g[:, :, 8:].reshape(groups, 256).astype(np.uint32) | ((slots >> 14) << 8)      # bits 8..9 of a delta ride on its row slot
+        slots &= 0x3fff
+        idx = np.cumsum(delta, axis=1)
+        r = er.reshape(groups, 256)
+        r_row, r_idx = (r >> 5) & 0x3fff, ((r >> 19) << 5) | (r & 31)
+        assert np.array_equal(slots, r_row)
+        real = r_row != 0x3fff
+        assert np.array_equal(idx[real], r_idx[real])
+        # padding: the predecessor's column again
+        prev = np.concatenate([np.zeros((groups, 1), np.uint32), idx[:, :-1].astype(np.uint32)], axis=1)
+        assert np.array_equal(idx[~real], prev[~real])
 
 
 def test_boolean_stream_with_wide_column_gaps_keeps_4_byte_entries(gpu, monkeypatch):
