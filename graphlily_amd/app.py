@@ -671,6 +671,97 @@ def validate_spanning_forest(csr, in_forest, weighted=True):
     return edges
 
 
+MATCH_FREE = np.uint32(0xffffffff)      # gl_match: mate[v] of a vertex that stays free
+
+
+def _matching_graph_of(csr, weighted=True, drop_nonpositive=False):
+    """the undirected weighted graph Matching reads out of `csr` -> (symmetric CSRMatrix, degrees): io.symmetrize_weighted with
+    keep="largest" (an edge stored more than once gets its largest value); drop_nonpositive removes the edges of weight <= 0"""
+    sym, deg = io.symmetrize_weighted(csr, weighted, keep="largest")
+    if drop_nonpositive and sym.nnz and np.any(sym.adj_data <= 0):
+        n = sym.num_rows
+        rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(sym.adj_indptr.astype(np.int64)))
+        keep = sym.adj_data > 0
+        deg = np.bincount(rows[keep], minlength=n).astype(np.uint32)
+        indptr = np.concatenate([[0], np.cumsum(deg, dtype=np.int64)]).astype(np.uint32)
+        sym = io.CSRMatrix(n, n, sym.adj_data[keep], sym.adj_indices[keep], indptr)
+    return sym, deg
+
+
+def _greedy_matching_of(sym):
+    """The greedy matching of a symmetric CSRMatrix with weights in adj_data, the edges taken in gl_match's order (~key(w), lo, hi)
+    -- heaviest first, among equal weights the smallest (lo, hi) first: the entries above the diagonal sorted by (~key, entry
+    number), one pass on the host that keeps an edge iff both its ends are free (kept apart from the device's pointer rounds:
+    validate_matching checks one with the other) -> uint32[n] mates, MATCH_FREE for a free vertex."""
+    n = sym.num_rows
+    indptr = sym.adj_indptr.astype(np.int64)
+    rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(indptr))
+    cols = sym.adj_indices.astype(np.int64)
+    up = np.flatnonzero(cols > rows)
+    up = up[np.argsort(~_edge_keys(sym.adj_data[up]), kind="stable")]       # (stable: ties stay in entry order = (lo, hi) order)
+    mate = [-1] * n
+    for u, v in zip(rows[up].tolist(), cols[up].tolist()):
+        if mate[u] < 0 and mate[v] < 0:
+            mate[u], mate[v] = v, u
+    return (np.asarray(mate, dtype=np.int64) & 0xffffffff).astype(np.uint32)
+
+
+def validate_matching(csr, mate, weighted=True, drop_nonpositive=False):
+    """Host-side check (numpy) that `mate` is THE greedy matching of the undirected weighted graph of `csr` -- as Matching reads
+    it: io.symmetrize_weighted(csr, weighted, keep="largest"), without the edges of weight <= 0 with drop_nonpositive -- one word
+    per vertex of that symmetric matrix, as Matching.run() returns them.  Raises ValueError naming the first offending vertex
+    or edge and the rule; returns the number of matched edges.  The rules:
+      1. mate is an involution without fixed points: mate[v] is MATCH_FREE or a vertex u != v with mate[u] == v;
+      2. every pair {v, mate[v]} is a stored edge;
+      3. the matching is maximal: no edge has two free ends;
+      4. it is the unique greedy one under the order (~key(w), lo, hi): it equals, vertex for vertex, what a host pass taking the
+         edges in that order returns."""
+    sym, _ = _matching_graph_of(csr, weighted, drop_nonpositive)
+    m = np.asarray(mate)
+    n = sym.num_rows
+    if m.ndim != 1 or m.shape[0] != n:
+        raise ValueError("validate_matching: %d mates for the %d vertices of the symmetric matrix" % (m.shape[0] if m.ndim == 1 else -1, n))
+    m = m.astype(np.int64)
+    free = m == int(MATCH_FREE)
+    v = np.arange(n, dtype=np.int64)
+
+    def first(bad):
+        return int(np.flatnonzero(bad)[0])
+
+    back = np.where(free, v, m[np.where(free | (m >= n), 0, m)])
+    bad = ~free & ((m >= n) | (m == v) | (back != v))
+    if np.any(bad):
+        x = first(bad)
+        if m[x] >= n:
+            what = "is no vertex"
+        elif m[x] == x:
+            what = "is itself"
+        else:
+            what = "is free" if back[x] == int(MATCH_FREE) else "is matched to %d" % back[x]
+        raise ValueError("validate_matching: vertex %d is matched to %d, which %s (rule 1)" % (x, m[x], what))
+    rows = np.repeat(v, np.diff(sym.adj_indptr.astype(np.int64)))
+    cols = sym.adj_indices.astype(np.int64)
+    stored = np.zeros(n, dtype=bool)
+    stored[rows[m[rows] == cols]] = True
+    if np.any(~free & ~stored):
+        x = first(~free & ~stored)
+        raise ValueError("validate_matching: vertex %d is matched to %d, and (%d, %d) is no edge of the graph (rule 2)" % (x, m[x], x, m[x]))
+    open_ = free[rows] & free[cols]
+    if np.any(open_):
+        j = first(open_)
+        raise ValueError("validate_matching: both ends of edge (%d, %d) of weight %r are free: the matching is not maximal (rule 3)"
+                         % (rows[j], cols[j], float(sym.adj_data[j])))
+    own = _greedy_matching_of(sym).astype(np.int64)
+    if np.any(own != m):
+        x = first(own != m)
+
+        def name(u):
+            return "free" if u == int(MATCH_FREE) else "matched to %d" % u
+        raise ValueError("validate_matching: vertex %d is %s, and in the greedy matching under the order (~key(w), lo, hi) it is %s (rule 4)"
+                         % (x, name(m[x]), name(own[x])))
+    return int(np.count_nonzero(~free)) // 2
+
+
 def _pattern_as_scipy(csr, n):
     """the entries of a CSRMatrix as an n x n scipy matrix of f64 ones (the matrix may have fewer rows and columns)"""
     import scipy.sparse as sp
@@ -1746,6 +1837,61 @@ class MinimumSpanningForest(_PatternApp):
         self.weights_ = self.graph_.adj_data[once]
         self.total_weight_ = float(np.cumsum(self.weights_, dtype=np.float64)[-1]) if once.size else 0.0     # (cumsum: one by one, in order)
         return self.in_forest_
+
+
+class Matching(_PatternApp):
+    """Greedy weighted matching: gl_match, the locally dominant matching over the rows with a weight per entry.
+    The matrix is read as an undirected weighted graph and stored in both directions by the host (io.symmetrize_weighted with
+    keep="largest": the diagonal is dropped, every other stored entry is an edge -- a stored 0 included --, an edge stored more
+    than once gets its LARGEST value, -0.0 becomes +0.0, NaN is refused; weighted=False: KCore's reading, zero values are no
+    edges and every weight is 1, which gives the lexicographically greedy maximal matching; drop_nonpositive=True removes the
+    edges of weight <= 0 before planning, so that the half-approximation bound holds on signed data).  That matrix is kept as
+    graph_, with the weights in adj_data; an all-ones copy of it is planned (the row copy would store a zero value as no
+    entry).  Edges are ordered by (~key(w), lo, hi) -- heaviest first, then the smallest (lo, hi) --, a strict total order, so
+    the result is unique: the matching that takes the edges greedily in that order."""
+    _no_shards_ = ("gl_match reads the mate of every column of a row and the rows of both ends of a matched edge, so every rank "
+                   "would need the whole symmetric matrix and every vertex's mate")
+    degrees_ = graph_ = mate_ = in_matching_ = edges_ = weights_ = total_weight_ = num_matched_ = None
+    rounds_ = scans_ = launches_ = weight_buf_ = None
+    weighted_, drop_nonpositive_ = True, False
+
+    def load_and_format_matrix(self, csr_float_npz_path, skip_empty_rows=True, weighted=True, drop_nonpositive=False):
+        self.weighted_, self.drop_nonpositive_ = bool(weighted), bool(drop_nonpositive)
+        _PatternApp.load_and_format_matrix(self, csr_float_npz_path, skip_empty_rows)
+
+    def _prepare(self, csr):
+        self.graph_, self.degrees_ = _matching_graph_of(csr, self.weighted_, self.drop_nonpositive_)
+        self.mate_ = self.weight_buf_ = None
+        g = self.graph_
+        return io.CSRMatrix(g.num_rows, g.num_cols, np.ones(g.nnz, dtype=np.float32), g.adj_indices, g.adj_indptr)
+
+    def send_matrix_host_to_device(self):
+        _PatternApp.send_matrix_host_to_device(self)
+        self.weight_buf_ = self.backend.alloc(max(1, self.graph_.nnz), np.float32)
+        if self.graph_.nnz:
+            self.backend.upload(self.weight_buf_, self.graph_.adj_data)
+
+    def run(self):
+        """-> uint32[n_]: mate[v] = the vertex v is matched to, MATCH_FREE (0xffffffff) for a free vertex.  Leaves mate_,
+        in_matching_ (bool[graph_.nnz]: the entry's edge is matched, both entries of an edge alike), edges_ (int64[m, 2]: (lo,
+        hi) of every matched edge, ascending), weights_ (float32[m], aligned with edges_), total_weight_ (the f64 sum of
+        weights_ in that order, added up on the host), num_matched_ (matched edges), rounds_ (rounds in which a vertex pointed
+        or finished), scans_ (row scans of all rounds) and launches_.  The call waits for the device."""
+        self._require_sent()
+        B, n = self.backend, self.n_
+        out = B.alloc(max(1, n), np.float32)                            # (32-bit words)
+        stats = self.SpMV_.match(self.weight_buf_, out)
+        B.sync()
+        self.mate_ = B.download(out, np.uint32, max(1, n))[:n]
+        self.num_matched_, self.rounds_, self.scans_, self.launches_ = stats
+        rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(self.graph_.adj_indptr.astype(np.int64)))
+        cols = self.graph_.adj_indices.astype(np.int64)
+        self.in_matching_ = self.mate_.astype(np.int64)[rows] == cols
+        once = np.flatnonzero(self.in_matching_ & (cols > rows))
+        self.edges_ = np.stack([rows[once], cols[once]], axis=1)
+        self.weights_ = self.graph_.adj_data[once]
+        self.total_weight_ = float(np.cumsum(self.weights_, dtype=np.float64)[-1]) if once.size else 0.0     # (cumsum: one by one, in order)
+        return self.mate_
 
 
 class GraphColoring(_PatternApp):

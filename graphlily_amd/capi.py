@@ -56,7 +56,8 @@ EXPORTS = [
 EXT_EXPORTS = ["gl_color"]
 # ... and one header per extension since (EXT_EXPORTS is pinned as well by now): header under include/ -> the symbols it declares;
 # tests check their own entry, build() checks every list against the library
-EXT_HEADERS = {"graphlily_hip_ext.h": EXT_EXPORTS, "graphlily_hip_truss.h": ["gl_truss"], "graphlily_hip_msf.h": ["gl_msf"]}
+EXT_HEADERS = {"graphlily_hip_ext.h": EXT_EXPORTS, "graphlily_hip_truss.h": ["gl_truss"], "graphlily_hip_msf.h": ["gl_msf"],
+               "graphlily_hip_match.h": ["gl_match"]}
 
 
 class GraphLilyError(RuntimeError):
@@ -126,6 +127,7 @@ def lib():
         "gl_color": [vp, vp, vp, P(u64)],
         "gl_truss": [vp, vp, vp, P(u64)],
         "gl_msf": [vp, vp, vp, vp, P(u64)],
+        "gl_match": [vp, vp, vp, P(u64)],
         "gl_bc_accumulate": [vp, vp, vp, vp, ctypes.c_double, i32, vp, P(u32)],
         "gl_spmv_run": [vp, vp, vp, vp, i32, f32, i32],
         "gl_prof_begin": [u32, u32], "gl_prof_end": [P(ctypes.c_double), P(u32)], "gl_span_begin": [], "gl_span_end": [P(ctypes.c_double)],
@@ -513,6 +515,21 @@ class SpMVPlan:
         garbage = 0xdeadbeefdeadbeef
         stats = (ctypes.c_uint64 * 4)(*([garbage] * 4))
         check(lib().gl_msf(ctypes.c_void_p(self.handle), _p(weight), _p(in_forest), _p(labels), stats))
+        return tuple(int(x) for x in stats)
+
+    def match(self, weight, mate):
+        """gl_match: the greedy matching of this plan's graph under the f32 weights `weight` (nnz device words, entry j = word j
+        of the row copy; BOTH entries of an edge are read and must hold the same bits) into `mate` (num_cols device words: the
+        partner of every vertex, 0xffffffff for a free one) -> (matched edges, rounds, scans, launches enqueued).  Edges are
+        ordered by (~key(w), lo, hi) -- heaviest first, then the smallest (lo, hi) --, a strict total order, and the result is the
+        matching that takes them greedily in that order: unique, maximal, at least half the maximum weight for weights >= 0.
+        The plan is square, whole, its rows strictly ascending sets, its pattern symmetric (io.symmetrize_weighted prepares it;
+        plan all-ones values).  `mate` is fully written by the call, which SYNCHRONISES (it reads a control record back between
+        batches of launches).  Weights whose mirrored words differ so that the vertices' choices close a cycle raise
+        GL_ERR_INVALID_ARG."""
+        garbage = 0xdeadbeefdeadbeef
+        stats = (ctypes.c_uint64 * 4)(*([garbage] * 4))
+        check(lib().gl_match(ctypes.c_void_p(self.handle), _p(weight), _p(mate), stats))
         return tuple(int(x) for x in stats)
 
     def bc_accumulate(self, plan_out, level, bc, scale=1.0, accumulate=False, sigma=None, stats=True):

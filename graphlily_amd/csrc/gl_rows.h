@@ -1,8 +1,8 @@
 // The plain CSR row copy that a GL_PLAN_BOOLEAN plan keeps (gl_spmv_plan.h: d_csr_indptr / d_csr_indices / csr_nz_base), as the
-// graph kernels that walk it see it -- gl_bfs_parents, gl_cc, gl_tc, gl_kcore, gl_color, gl_truss, gl_msf (which also takes a
-// value per entry of the copy from its caller), gl_bc: what a caller may require of it, the
+// graph kernels that walk it see it -- gl_bfs_parents, gl_cc, gl_tc, gl_kcore, gl_color, gl_truss, gl_msf and gl_match (which also take a
+// value per entry of the copy from their caller), gl_bc: what a caller may require of it, the
 // verdicts about it that the plan caches, the few helpers every such kernel wants, and the walk over a row -- a thread per row,
-// then the wavefront -- that five of them run (rows_walk_*, at the end).  gl_rows.hip holds the check kernels.
+// then the wavefront -- that six of them run (rows_walk_*, at the end).  gl_rows.hip holds the check kernels.
 // gl_rounds.h, on top of this, holds what the kernels that run in rounds over a queue share: the atomics of their memory rule,
 // the queue append, the peel record and the gated host loop.
 #ifndef GL_ROWS_H_
@@ -76,7 +76,7 @@ __device__ __forceinline__ uint32_t rows_lower_bound(P s, uint32_t n, uint32_t w
     return lo;
 }
 
-// THE WALK over the entries [beg, end) of one row per lane, 64 rows per wavefront (gl_bfs_parents, gl_cc, gl_kcore, gl_msf and
+// THE WALK over the entries [beg, end) of one row per lane, 64 rows per wavefront (gl_bfs_parents, gl_cc, gl_kcore, gl_msf, gl_match and
 // gl_color run it; DESIGN.md 4.13.  bc_sweep_kernel of gl_bc keeps a copy of its own, in the same forms: through these templates
 // its accumulate figure on one stand-in was 1 - 2 % above the parent's worse run in two visits, EXPERIMENTS.md Round 21):
 //   rows_walk_thread    a thread per row, four entries per step, for at most cut_steps steps while any lane of the wavefront has

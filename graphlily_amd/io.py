@@ -129,14 +129,17 @@ def symmetrize_simple(csr_matrix):
     return sym, deg.astype(np.uint32)
 
 
-def symmetrize_weighted(csr_matrix, weighted=True):
+def symmetrize_weighted(csr_matrix, weighted=True, keep="smallest"):
     """The matrix preparation of MinimumSpanningForest (an extension) -> (symmetric CSRMatrix, degrees as uint32[n]),
     n = max(num_rows, num_cols): symmetrize_simple's layout with weights.  The diagonal is dropped; every remaining STORED entry
     is an edge {u, v}, a stored 0 included (weight 0 is a legitimate weight).  An edge stored more than once, or in both
-    directions, gets the SMALLEST of its values, and both entries of the result carry it.  -0.0 becomes +0.0; a NaN raises
+    directions, gets the SMALLEST of its values (keep="largest": the LARGEST, the natural reading for a maximum-weight result such
+    as Matching's), and both entries of the result carry it.  -0.0 becomes +0.0; a NaN raises
     ValueError naming the first offending entry.  Row v of the result lists the neighbours of v, columns ascending, with the
     weights in adj_data.  weighted=False is symmetrize_simple's reading: zero values are no edges and every weight is 1.
     Applied after padding: padding vertices have empty rows."""
+    if keep not in ("smallest", "largest"):
+        raise ValueError("symmetrize_weighted: keep is %r, not \"smallest\" or \"largest\"" % (keep,))
     if not weighted:
         return symmetrize_simple(csr_matrix)
     n = max(int(csr_matrix.num_rows), int(csr_matrix.num_cols))
@@ -149,10 +152,10 @@ def symmetrize_weighted(csr_matrix, weighted=True):
     if np.any(bad):
         j = int(np.flatnonzero(bad)[0])
         raise ValueError("symmetrize_weighted: entry %d (%d, %d) is NaN: the order of the edges needs comparable weights" % (j, rows[j], cols[j]))
-    keep = rows != cols
-    rows, cols, w = rows[keep], cols[keep], w[keep] + np.float32(0.0)         # (-0.0 + 0.0 == +0.0)
+    off = rows != cols
+    rows, cols, w = rows[off], cols[off], w[off] + np.float32(0.0)            # (-0.0 + 0.0 == +0.0)
     key = np.minimum(rows, cols) * n + np.maximum(rows, cols)
-    order = np.lexsort((w, key))                                              # by edge, the smallest value of each first
+    order = np.lexsort((w if keep == "smallest" else -w, key))                # by edge, the value to keep of each first
     key, w = key[order], w[order]
     once = np.ones(key.shape[0], dtype=bool)
     once[1:] = key[1:] != key[:-1]

@@ -335,6 +335,19 @@ class SpMVModule(BaseModule):
         self._finish(forest_buf, labels_buf)
         return stats
 
+    def match(self, weight_buf, mate_buf):
+        """Extension (gl_match): the greedy weighted matching of this module's matrix, read as a graph -- rows as strictly
+        ascending sets N(v), the pattern symmetric -- under the f32 weights in `weight_buf` (get_nnz() words aligned with the
+        matrix's entries; both entries of an edge hold the same word), into `mate_buf` (get_num_cols() words: every vertex's
+        partner, 0xffffffff for a free vertex) -> (matched edges, rounds, scans, launches).  The call synchronises.  Raises
+        GraphLilyError (GL_ERR_UNSUPPORTED) when the plan keeps no row copy (only the (||,&&) layout does), is not square, is a
+        row shard, its rows are no such sets or its pattern is not symmetric (io.symmetrize_weighted prepares it)."""
+        if self.plan_ is None:
+            _fatal("SpMVModule.match: send_matrix_host_to_device first")
+        stats = self.plan_.match(weight_buf, mate_buf)
+        self._finish(mate_buf)
+        return stats
+
     def bc_accumulate(self, out_module, level_buf, bc_buf, scale=1.0, accumulate=False, sigma_buf=None, stats=True):
         """Extension (gl_bc_accumulate): adds scale x Brandes' dependency of the search whose levels are in `level_buf`
         (get_num_rows() floats) to `bc_buf` (as many doubles; accumulate=False: overwrites it).  This module's matrix is the

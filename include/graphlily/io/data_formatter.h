@@ -116,11 +116,13 @@ CSRMatrix<data_type> util_symmetrize_simple(CSRMatrix<data_type> const &m, std::
 
 // The matrix preparation of app::MinimumSpanningForest (an extension): util_symmetrize_simple's layout with weights.  The diagonal
 // is dropped; every remaining STORED entry is an edge {u, v}, a stored 0 included.  An edge stored more than once, or in both
-// directions, gets the SMALLEST of its values, and both entries of the result carry it; -0.0 becomes +0.0; a NaN prints and
-// exits.  weighted = false is util_symmetrize_simple's reading (zero values are no edges, every weight 1).  `degrees` receives the
+// directions, gets the SMALLEST of its values (keep_largest: the LARGEST, io.symmetrize_weighted's keep="largest", the natural
+// reading for a maximum-weight result such as app::Matching's), and both entries of the result carry it; -0.0 becomes +0.0; a
+// NaN prints and exits.  weighted = false is util_symmetrize_simple's reading (zero values are no edges, every weight 1).  `degrees` receives the
 // row lengths.  n = max(num_rows, num_cols); apply after padding.
 template <typename data_type>
-CSRMatrix<data_type> util_symmetrize_weighted(CSRMatrix<data_type> const &m, std::vector<uint32_t> &degrees, bool weighted = true) {
+CSRMatrix<data_type> util_symmetrize_weighted(CSRMatrix<data_type> const &m, std::vector<uint32_t> &degrees, bool weighted = true,
+                                              bool keep_largest = false) {
     if (!weighted) return util_symmetrize_simple(m, degrees);
     const uint64_t n = std::max(m.num_rows, m.num_cols);
     std::vector<std::pair<uint64_t, data_type>> edge;          // {lo * n + hi, weight}
@@ -137,6 +139,11 @@ CSRMatrix<data_type> util_symmetrize_weighted(CSRMatrix<data_type> const &m, std
             edge.push_back(std::make_pair(std::min<uint64_t>(u, v) * n + std::max<uint64_t>(u, v), w));
         }
     std::sort(edge.begin(), edge.end());                        // by edge, the smallest value of each first
+    if (keep_largest)                                           // ... the largest of each run moves to the run's front
+        for (size_t i = 0, j; i < edge.size(); i = j) {
+            for (j = i + 1; j < edge.size() && edge[j].first == edge[i].first; j++) {}
+            edge[i].second = edge[j - 1].second;
+        }
     std::vector<std::pair<uint64_t, data_type>> entry;          // {row * n + column, weight}, both directions
     entry.reserve(2 * edge.size());
     for (size_t i = 0; i < edge.size(); i++) {

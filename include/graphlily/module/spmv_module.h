@@ -13,6 +13,7 @@
 #include "graphlily_hip_ext.h"
 #include "graphlily_hip_truss.h"
 #include "graphlily_hip_msf.h"
+#include "graphlily_hip_match.h"
 #include "graphlily/io/data_formatter.h"
 #include "graphlily/io/data_loader.h"
 #include "graphlily/module/base_module.h"
@@ -231,6 +232,17 @@ public:
     void msf(DeviceBuffer weight, DeviceBuffer in_forest, uint32_t *labels = nullptr, uint64_t *stats = nullptr) {
         barrier_();
         GRAPHLILY_CHECK(gl_msf(plan_, (const float *)weight.rptr(), (uint32_t *)in_forest.ptr(), labels, stats));
+        finish_();
+    }
+    // extension (gl_match, graphlily_hip_match.h): the greedy weighted matching of this module's matrix, read as a graph -- rows as
+    // strictly ascending sets N(v), the pattern symmetric (graphlily::io::util_symmetrize_weighted prepares it) -- under the f32
+    // weights in `weight` (get_nnz() device words aligned with the matrix's entries; both entries of an edge hold the same word),
+    // into `mate` (get_num_cols() device words: every vertex's partner, 0xffffffff for a free vertex); stats (optional, 4 host
+    // words) receives {matched edges, rounds, scans, launches}.  Only the (||,&&) layout keeps the rows this pass walks.  The call
+    // synchronises.
+    void match(DeviceBuffer weight, DeviceBuffer mate, uint64_t *stats = nullptr) {
+        barrier_();
+        GRAPHLILY_CHECK(gl_match(plan_, (const float *)weight.rptr(), (uint32_t *)mate.ptr(), stats));
         finish_();
     }
     // extension (gl_bc_accumulate): adds scale x Brandes' dependency of the search whose levels are in `level` (get_num_rows()
