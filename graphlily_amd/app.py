@@ -762,6 +762,121 @@ def validate_matching(csr, mate, weighted=True, drop_nonpositive=False):
     return int(np.count_nonzero(~free)) // 2
 
 
+LPA_NO_LABEL = 0xffffffff      # gl_lpa: the word no initial label may be (the empty key of the label tables)
+
+
+def _lpa_row_modes(sym, labels):
+    """for every vertex of the symmetric simple graph `sym` under `labels` -> (best, cur) as int64[n]: the largest number of
+    neighbours that share one label, and the number of neighbours carrying the vertex's own label (0, 0 for an isolated vertex)"""
+    n = sym.num_rows
+    rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(sym.adj_indptr.astype(np.int64)))
+    cols = sym.adj_indices.astype(np.int64)
+    off = rows != cols
+    rows, cols = rows[off], cols[off]
+    _, ident = np.unique(labels, return_inverse=True)                    # labels as numbers below n
+    ident = ident.astype(np.int64)
+    key, count = np.unique(rows * n + ident[cols], return_counts=True)
+    best = np.zeros(n, dtype=np.int64)
+    np.maximum.at(best, key // n, count)
+    own = np.arange(n, dtype=np.int64) * n + ident
+    at = np.minimum(np.searchsorted(key, own), max(key.shape[0] - 1, 0))
+    cur = np.where(key[at] == own, count[at], 0) if key.shape[0] else np.zeros(n, dtype=np.int64)
+    return best, cur
+
+
+def _lpa_color_loop(sym, colors, initial, max_sweeps):
+    """gl_lpa's colour-class schedule restated on the host -> (labels, sweeps, changes, evaluations, converged): the vertices
+    with a neighbour in (colour, vertex) order, one after the other in place; a vertex is evaluated in sweep 1, and later iff a
+    neighbour changed since its previous evaluation.  One np.unique per evaluation (kept apart from the device's tables and
+    from the suite's dictionary loop: validate_communities checks one with the other)."""
+    n = sym.num_rows
+    indptr = sym.adj_indptr.astype(np.int64)
+    cols = sym.adj_indices.astype(np.int64)
+    label = np.asarray(initial, dtype=np.int64).copy()
+    hood = [cols[indptr[v]:indptr[v + 1]] for v in range(n)]
+    hood = [h[h != v] for v, h in enumerate(hood)]
+    linked = np.array([h.shape[0] > 0 for h in hood], dtype=bool)
+    order = [int(v) for v in np.lexsort((np.arange(n), np.asarray(colors, dtype=np.int64))) if linked[v]]
+    active = linked.copy()
+    sweeps = changes = evaluations = converged = 0
+    while sweeps < max_sweeps and not converged:
+        sweeps += 1
+        changed = 0
+        for v in order:
+            if not active[v]:
+                continue
+            active[v] = False
+            evaluations += 1
+            seen, count = np.unique(label[hood[v]], return_counts=True)
+            top = int(count.max())
+            at = np.searchsorted(seen, label[v])
+            cur = int(count[at]) if at < seen.shape[0] and seen[at] == label[v] else 0
+            if top > cur:
+                label[v] = seen[int(np.argmax(count))]                  # (the first maximum: seen ascends, so the smallest label)
+                active[hood[v]] = True
+                changed += 1
+        changes += changed
+        converged = int(changed == 0)
+    return label.astype(np.uint32), sweeps, changes, evaluations, converged
+
+
+def validate_communities(csr, labels, colors=None, initial=None, max_sweeps=None):
+    """Host-side check (numpy) that `labels` is what label propagation leaves on the undirected simple graph of `csr` -- as
+    LabelPropagation reads it: io.symmetrize_simple -- one word per vertex of that symmetric matrix, as LabelPropagation.run()
+    returns them.  `initial`: the labels the run started from (default: every vertex's own number); `colors`: the colouring it
+    swept by (None: the synchronous schedule, or unknown); `max_sweeps`: the cap it ran under (None: the labels are claimed to
+    be a fixed point).  Raises ValueError naming the first offending vertex and the rule; returns the number of distinct labels.
+      1. every label is one of the initial labels;
+      2. a vertex without a neighbour keeps its initial label;
+      3. if the run converged -- max_sweeps is None, or the host loop of rule 4 converged within it -- the labels are a fixed
+         point: every vertex with a neighbour carries a label that a maximum number of its neighbours carry;
+      4. with `colors`, the labels equal, vertex for vertex, what the host loop over the vertices in (colour, vertex) order
+         leaves after at most max_sweeps sweeps (None: run to the fixed point)."""
+    sym, deg = io.symmetrize_simple(csr)
+    n = sym.num_rows
+    got = np.asarray(labels)
+    if got.ndim != 1 or got.shape[0] != n:
+        raise ValueError("validate_communities: %d labels for the %d vertices of the symmetric matrix" % (got.shape[0] if got.ndim == 1 else -1, n))
+    got = got.astype(np.int64)
+    start = np.arange(n, dtype=np.int64)
+    if initial is not None:
+        given = np.asarray(initial).astype(np.int64)
+        if given.ndim != 1 or given.shape[0] > n:
+            raise ValueError("validate_communities: %d initial labels for %d vertices" % (given.shape[0] if given.ndim == 1 else -1, n))
+        start[:given.shape[0]] = given
+
+    def first(bad):
+        return int(np.flatnonzero(bad)[0])
+
+    alien = ~np.isin(got, start)
+    if np.any(alien):
+        x = first(alien)
+        raise ValueError("validate_communities: vertex %d carries the label %d, which no vertex started with (rule 1)" % (x, got[x]))
+    moved = (deg == 0) & (got != start)
+    if np.any(moved):
+        x = first(moved)
+        raise ValueError("validate_communities: vertex %d has no neighbour and carries %d, not its initial label %d (rule 2)" % (x, got[x], start[x]))
+    converged = max_sweeps is None
+    if colors is not None:
+        col = np.asarray(colors).astype(np.int64)
+        if col.ndim != 1 or col.shape[0] > n:
+            raise ValueError("validate_communities: %d colours for %d vertices" % (col.shape[0] if col.ndim == 1 else -1, n))
+        col = np.concatenate([col, np.zeros(n - col.shape[0], dtype=np.int64)])
+        own, _, _, _, done = _lpa_color_loop(sym, col, start, (1 << 62) if max_sweeps is None else int(max_sweeps))
+        converged = bool(done)
+        if np.any(own.astype(np.int64) != got):
+            x = first(own.astype(np.int64) != got)
+            raise ValueError("validate_communities: vertex %d carries %d, and the loop in (colour, vertex) order leaves it %d (rule 4)"
+                             % (x, got[x], own[x]))
+    if converged:
+        best, cur = _lpa_row_modes(sym, got)
+        if np.any(cur < best):
+            x = first(cur < best)
+            raise ValueError("validate_communities: %d neighbours of vertex %d carry its label %d and %d carry another one: not a fixed "
+                             "point (rule 3)" % (cur[x], x, got[x], best[x]))
+    return int(np.unique(got).shape[0])
+
+
 def _pattern_as_scipy(csr, n):
     """the entries of a CSRMatrix as an n x n scipy matrix of f64 ones (the matrix may have fewer rows and columns)"""
     import scipy.sparse as sp
@@ -1948,6 +2063,101 @@ class GraphColoring(_PatternApp):
         mask = self.colors_ == c
         mask[self.n_real_:] = False
         return mask
+
+
+class LabelPropagation(_PatternApp):
+    """Label propagation communities: gl_lpa, Raghavan, Albert & Kumara's rule swept colour class by colour
+    class (Cordasco & Gargano).  The matrix is read as an undirected simple graph -- duplicates, the diagonal, zero-valued
+    entries and direction are ignored, as in KCore and GraphColoring -- and stored in both directions by the host
+    (io.symmetrize_simple).  Evaluating a vertex gives it the smallest of its neighbours' most frequent labels if strictly more
+    neighbours carry that label than its own; under a proper colouring the sweeps equal the sequential loop in (colour, vertex)
+    order, reach a fixed point, and the result is a pure function of (graph, colouring, initial labels), to the bit."""
+    _no_shards_ = ("gl_lpa reads the label of every column of a row and flags the rows of a changed vertex's neighbours, so every "
+                   "rank would need the whole symmetric matrix and every vertex's label")
+    degrees_ = graph_ = labels_ = colors_ = initial_ = num_colors_ = sweeps_ = changes_ = evaluations_ = launches_ = converged_ = None
+    num_communities_ = community_labels_ = community_sizes_ = None
+
+    def _prepare(self, csr):
+        self.graph_, self.degrees_ = io.symmetrize_simple(csr)
+        self.labels_ = None
+        return self.graph_
+
+    def run(self, max_sweeps=100, initial=None, seed=None, order="largest_first", colors=None, synchronous=False):
+        """-> uint32[n_]: labels[v] = the community label of v (padding vertices are isolated and keep their own numbers).
+        The sweeps go colour class by colour class under `colors` (n_real_ or n_ words, a proper colouring) or, without them,
+        under the colouring SpMV_.color gives on the same plan for io.coloring_priorities(degrees_, order, seed or 0)
+        ("smallest_last" first runs gl_kcore, as GraphColoring does); synchronous=True sweeps all vertices at once from the
+        previous sweep's labels instead, which may oscillate until max_sweeps.  `initial` (n_real_ or n_ words, none
+        0xffffffff) are the labels the vertices start with -- seed labels, or a relabelling that undoes the pull towards small
+        vertex numbers that the rule's tie-break has; without it, `seed` gives io.lpa_initial_labels(n_real_, seed), a random
+        permutation, and seed=None every vertex's own number.  Leaves labels_, colors_ (uint32[n_]; None when synchronous),
+        num_colors_ (classes swept), initial_ (the array the run used; None for own numbers), sweeps_, changes_,
+        evaluations_, launches_ (gl_lpa's alone), converged_, and over the real vertices num_communities_,
+        community_labels_ (ascending) and community_sizes_ (aligned with them).  The call waits for the device."""
+        self._require_sent()
+        B, n = self.backend, self.n_
+        out = B.alloc(3 * max(1, n), np.float32)                     # (32-bit words: the labels, the colours, the priorities / initial labels)
+        label_buf, color_buf, third = B.view(out, 0, n, 4), B.view(out, n, n, 4), B.view(out, 2 * n, n, 4)
+
+        def padded(arr, what, fill):
+            a = np.asarray(arr)
+            if a.ndim != 1 or a.shape[0] not in (self.n_real_, n):
+                raise ValueError("LabelPropagation.run(): %s of shape %s, expected %d or %d words" % (what, a.shape, self.n_real_, n))
+            return np.concatenate([a.astype(np.uint32), fill[a.shape[0]:]])
+
+        own = np.arange(n, dtype=np.uint32)
+        if initial is not None:
+            start = padded(initial, "initial", own)
+        else:
+            start = io.lpa_initial_labels(self.n_real_, seed, n) if seed is not None else None
+        if synchronous:
+            self.colors_, self.num_colors_ = None, 1
+        elif colors is not None:
+            self.colors_ = padded(colors, "colors", np.zeros(n, dtype=np.uint32))
+            self.num_colors_ = int(self.colors_.max()) + 1 if n else 0
+            B.upload(color_buf, self.colors_)
+        else:
+            seed0 = 0 if seed is None else seed
+            if order == "smallest_last":
+                peel = B.alloc(2 * n, np.float32)                    # (32-bit words: the core numbers, then the order)
+                self.SpMV_.kcore(B.view(peel, 0, n, 4), B.view(peel, n, n, 4))
+                B.sync()
+                prio = io.coloring_priorities(self.degrees_, order, seed0, peel_order=B.download(peel, np.uint32, 2 * n)[n:])
+            else:
+                prio = io.coloring_priorities(self.degrees_, order, seed0)
+            if prio is not None:
+                B.upload(third, prio)
+            self.num_colors_ = self.SpMV_.color(color_buf, third if prio is not None else None)[0]
+            B.sync()
+            self.colors_ = B.download(out, np.uint32, 2 * n)[n:]
+        if start is not None:
+            B.upload(third, start)
+        stats = self.SpMV_.lpa(label_buf, None if synchronous else color_buf, third if start is not None else None, max_sweeps)
+        B.sync()
+        self.labels_ = B.download(out, np.uint32, n)
+        self.initial_ = start
+        self.sweeps_, self.changes_, self.evaluations_, self.launches_, self.converged_ = stats
+        self.community_labels_, sizes = np.unique(self.labels_[:self.n_real_], return_counts=True)
+        self.community_sizes_ = sizes.astype(np.int64)
+        self.num_communities_ = int(sizes.shape[0])
+        return self.labels_
+
+    def modularity(self, labels=None):
+        """-> float: Newman's modularity sum_c e_c / m - (d_c / 2 m)^2 of the last run's labels (or of `labels`, n_ words) on
+        graph_, computed on the host in f64: e_c = edges inside community c, d_c = the degrees of its vertices, m = edges
+        (0.0 for a graph without edges)"""
+        lab = self.labels_ if labels is None else np.asarray(labels)
+        if lab is None:
+            raise RuntimeError("LabelPropagation.modularity(): run() first")
+        g = self.graph_
+        if g.nnz == 0:
+            return 0.0
+        _, ident = np.unique(lab, return_inverse=True)
+        rows = np.repeat(np.arange(g.num_rows, dtype=np.int64), np.diff(g.adj_indptr.astype(np.int64)))
+        inside = np.bincount(ident[rows][ident[rows] == ident[g.adj_indices.astype(np.int64)]], minlength=int(ident.max()) + 1)   # (twice e_c)
+        degree = np.bincount(ident, weights=self.degrees_.astype(np.float64), minlength=inside.shape[0])
+        two_m = float(g.nnz)
+        return float(np.sum(inside / two_m - (degree / two_m) ** 2))
 
 
 class BetweennessCentrality(_PatternApp):

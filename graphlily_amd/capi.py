@@ -57,7 +57,7 @@ EXT_EXPORTS = ["gl_color"]
 # ... and one header per extension since (EXT_EXPORTS is pinned as well by now): header under include/ -> the symbols it declares;
 # tests check their own entry, build() checks every list against the library
 EXT_HEADERS = {"graphlily_hip_ext.h": EXT_EXPORTS, "graphlily_hip_truss.h": ["gl_truss"], "graphlily_hip_msf.h": ["gl_msf"],
-               "graphlily_hip_match.h": ["gl_match"]}
+               "graphlily_hip_match.h": ["gl_match"], "graphlily_hip_lpa.h": ["gl_lpa"]}
 
 
 class GraphLilyError(RuntimeError):
@@ -128,6 +128,7 @@ def lib():
         "gl_truss": [vp, vp, vp, P(u64)],
         "gl_msf": [vp, vp, vp, vp, P(u64)],
         "gl_match": [vp, vp, vp, P(u64)],
+        "gl_lpa": [vp, vp, vp, vp, u32, P(u64)],
         "gl_bc_accumulate": [vp, vp, vp, vp, ctypes.c_double, i32, vp, P(u32)],
         "gl_spmv_run": [vp, vp, vp, vp, i32, f32, i32],
         "gl_prof_begin": [u32, u32], "gl_prof_end": [P(ctypes.c_double), P(u32)], "gl_span_begin": [], "gl_span_end": [P(ctypes.c_double)],
@@ -530,6 +531,22 @@ class SpMVPlan:
         garbage = 0xdeadbeefdeadbeef
         stats = (ctypes.c_uint64 * 4)(*([garbage] * 4))
         check(lib().gl_match(ctypes.c_void_p(self.handle), _p(weight), _p(mate), stats))
+        return tuple(int(x) for x in stats)
+
+    def lpa(self, label, color=None, init=None, max_sweeps=100):
+        """gl_lpa: label propagation communities of this plan's graph into `label` (num_rows device words) -> (sweeps, changes,
+        evaluations, launches enqueued, converged).  Every vertex starts with `init` (num_rows device words, any word but
+        0xffffffff; None: its own number); evaluating a vertex gives it the smallest of its neighbours' most frequent labels if
+        that label is carried by strictly more neighbours than its own.  With `color` (num_rows device words, a proper
+        colouring with colours below num_rows, as gl_color gives) a sweep evaluates class 0, then class 1, ... in place, which
+        equals the sequential loop in (colour, vertex) order and reaches a fixed point; with color=None every sweep evaluates
+        all vertices from the previous sweep's labels, which may oscillate until `max_sweeps` ends it.  The plan is square,
+        whole, its rows strictly ascending sets, its pattern symmetric (io.symmetrize_simple prepares it).  `label` is fully
+        written by the call, which SYNCHRONISES (it reads a control record back between batches of launches).  A label
+        0xffffffff in `init`, a colour >= num_rows and a colouring that is not proper raise GL_ERR_INVALID_ARG."""
+        garbage = 0xdeadbeefdeadbeef
+        stats = (ctypes.c_uint64 * 5)(*([garbage] * 5))
+        check(lib().gl_lpa(ctypes.c_void_p(self.handle), _p(color), _p(init), _p(label), ctypes.c_uint32(max_sweeps), stats))
         return tuple(int(x) for x in stats)
 
     def bc_accumulate(self, plan_out, level, bc, scale=1.0, accumulate=False, sigma=None, stats=True):

@@ -1,6 +1,6 @@
 // The plain CSR row copy that a GL_PLAN_BOOLEAN plan keeps (gl_spmv_plan.h: d_csr_indptr / d_csr_indices / csr_nz_base), as the
 // graph kernels that walk it see it -- gl_bfs_parents, gl_cc, gl_tc, gl_kcore, gl_color, gl_truss, gl_msf and gl_match (which also take a
-// value per entry of the copy from their caller), gl_bc: what a caller may require of it, the
+// value per entry of the copy from their caller), gl_lpa, gl_bc: what a caller may require of it, the
 // verdicts about it that the plan caches, the few helpers every such kernel wants, and the walk over a row -- a thread per row,
 // then the wavefront -- that six of them run (rows_walk_*, at the end).  gl_rows.hip holds the check kernels.
 // gl_rounds.h, on top of this, holds what the kernels that run in rounds over a queue share: the atomics of their memory rule,

@@ -267,6 +267,9 @@ struct gl_spmv_plan_s {
     // gl_match (gl_match.hip): the pass's scratch, allocated by the first call -- 256 bytes of control record, then four arrays of
     // num_cols words: the pointers, this round's and the next round's vertex lists, and the list of freshly matched vertices
     unsigned char *d_match_scratch = nullptr;
+    // gl_lpa (gl_lpa.hip): the pass's scratch, allocated by the first call -- 256 bytes of control record, then five arrays of
+    // num_rows words (two flag arrays, the second label buffer, the class list, the colour histogram) and num_rows + 1 class offsets
+    unsigned char *d_lpa_scratch = nullptr;
     // gl_bc_accumulate (gl_bc.hip), as plan_in, set up by the first call: the pass's scratch -- 256 bytes of control words, two
     // arrays of num_rows + 2 level offsets, num_rows words of queue, num_rows doubles each of sigma and coef -- the page-locked
     // room the offsets are read back to, and the verdict on the last plan_out that was not this plan itself: is it the

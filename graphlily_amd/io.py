@@ -216,6 +216,17 @@ def coloring_priorities(degrees, order, seed=0, peel_order=None):
     raise ValueError("coloring_priorities: order %r is none of %s" % (order, ", ".join(COLORING_ORDERS)))
 
 
+def lpa_initial_labels(n, seed, n_total=None):
+    """The seeded initial labels of LabelPropagation (an extension) -> uint32[n_total or n]: a permutation of 0 .. n - 1 over the
+    first n vertices -- label[v] = the rank of coloring_hash(v, seed) among them; the hash is a bijection, so no two tie -- and
+    every later (padding) vertex's own number.  It undoes the pull towards small vertex numbers that the rule's tie-break has.
+    graphlily::io::util_lpa_initial_labels (include/graphlily/io/data_formatter.h) computes the same words."""
+    total = n if n_total is None else int(n_total)
+    out = np.arange(total, dtype=np.uint32)
+    out[np.argsort(coloring_hash(np.arange(n), seed), kind="stable")] = np.arange(n, dtype=np.uint32)
+    return out
+
+
 def simple_pattern(csr_matrix):
     """The matrix preparation of BetweennessCentrality (an extension) -> (csr_in, csr_out or None, symmetric).  The simple
     directed graph of the matrix has an edge u -> v iff u != v and a stored non-zero entry A[v, u] exists: zero values, the

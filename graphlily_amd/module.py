@@ -348,6 +348,21 @@ class SpMVModule(BaseModule):
         self._finish(mate_buf)
         return stats
 
+    def lpa(self, label_buf, color_buf=None, init_buf=None, max_sweeps=100):
+        """Extension (gl_lpa): label propagation communities of this module's matrix, read as a graph -- rows as strictly
+        ascending sets N(v), the pattern symmetric -- into `label_buf` (get_num_rows() words), from the initial labels in
+        `init_buf` (as many words, none 0xffffffff; None: every vertex's own number), swept colour class by colour class under
+        the proper colouring in `color_buf` (as many words; SpMVModule.color gives one), or synchronously with color_buf=None
+        -> (sweeps, changes, evaluations, launches, converged).  The call synchronises.  Raises GraphLilyError
+        (GL_ERR_UNSUPPORTED) when the plan keeps no row copy (only the (||,&&) layout does), is not square, is a row shard, its
+        rows are no such sets or its pattern is not symmetric (io.symmetrize_simple prepares it), and (GL_ERR_INVALID_ARG) for
+        a label 0xffffffff, a colour >= get_num_rows() or a colouring that is not proper."""
+        if self.plan_ is None:
+            _fatal("SpMVModule.lpa: send_matrix_host_to_device first")
+        stats = self.plan_.lpa(label_buf, color_buf, init_buf, max_sweeps)
+        self._finish(label_buf)
+        return stats
+
     def bc_accumulate(self, out_module, level_buf, bc_buf, scale=1.0, accumulate=False, sigma_buf=None, stats=True):
         """Extension (gl_bc_accumulate): adds scale x Brandes' dependency of the search whose levels are in `level_buf`
         (get_num_rows() floats) to `bc_buf` (as many doubles; accumulate=False: overwrites it).  This module's matrix is the

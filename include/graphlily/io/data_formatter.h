@@ -212,6 +212,19 @@ inline std::vector<uint32_t> util_coloring_priorities(std::vector<uint32_t> cons
     return prio;
 }
 
+// The seeded initial labels of app::LabelPropagation (an extension), io.lpa_initial_labels's words: a permutation of 0 .. n - 1
+// over the first n vertices -- label[v] = the rank of util_coloring_hash(v, seed) among them -- and every later (padding) vertex's
+// own number.
+inline std::vector<uint32_t> util_lpa_initial_labels(uint32_t n, uint32_t seed, uint32_t n_total) {
+    std::vector<std::pair<uint32_t, uint32_t>> key(n);
+    for (uint32_t v = 0; v < n; v++) key[v] = std::make_pair(util_coloring_hash(v, seed), v);
+    std::sort(key.begin(), key.end());
+    std::vector<uint32_t> out(std::max(n, n_total));
+    for (uint32_t v = 0; v < out.size(); v++) out[v] = v;
+    for (uint32_t i = 0; i < n; i++) out[key[i].second] = i;
+    return out;
+}
+
 // The matrix preparation of app::BetweennessCentrality (an extension): the simple DIRECTED graph of m -- an edge u -> v iff u != v
 // and a stored non-zero entry A[v,u] exists: zero values, the diagonal and duplicates are dropped, the direction is kept.  Row v of
 // `in` lists the vertices v is pulled from, row u of `out` (the transposed pattern) the out-neighbours of u; both n x n, n =

@@ -14,6 +14,7 @@
 #include "graphlily_hip_truss.h"
 #include "graphlily_hip_msf.h"
 #include "graphlily_hip_match.h"
+#include "graphlily_hip_lpa.h"
 #include "graphlily/io/data_formatter.h"
 #include "graphlily/io/data_loader.h"
 #include "graphlily/module/base_module.h"
@@ -243,6 +244,18 @@ public:
     void match(DeviceBuffer weight, DeviceBuffer mate, uint64_t *stats = nullptr) {
         barrier_();
         GRAPHLILY_CHECK(gl_match(plan_, (const float *)weight.rptr(), (uint32_t *)mate.ptr(), stats));
+        finish_();
+    }
+    // extension (gl_lpa, graphlily_hip_lpa.h): label propagation communities of this module's matrix, read as a graph -- rows as
+    // strictly ascending sets N(v), the pattern symmetric (graphlily::io::util_symmetrize_simple prepares it) -- into `label`
+    // (get_num_rows() device words), swept colour class by colour class under the proper colouring in `color` (as many device
+    // words; color() gives one), or synchronously without one, from the initial labels in `init` (as many device words, none
+    // 0xffffffff) or, without them, every vertex's own number; stats (optional, 5 host words) receives {sweeps, changes, evaluations, launches,
+    // converged}.  Only the (||,&&) layout keeps the rows this pass walks.  The call synchronises.
+    void lpa(DeviceBuffer label, const uint32_t *color = nullptr, const uint32_t *init = nullptr, uint32_t max_sweeps = 100,
+             uint64_t *stats = nullptr) {
+        barrier_();
+        GRAPHLILY_CHECK(gl_lpa(plan_, color, init, (uint32_t *)label.ptr(), max_sweeps, stats));
         finish_();
     }
     // extension (gl_bc_accumulate): adds scale x Brandes' dependency of the search whose levels are in `level` (get_num_rows()
