@@ -1745,6 +1745,46 @@ class _PatternApp(_GraphApp):
         self.SpMV_.send_matrix_host_to_device()
         self.sent_ = True
 
+    def _peel_order(self):
+        """-> (uint32[n_], int): gl_kcore on the same plan: a degeneracy ordering of the vertices -- what the "smallest_last"
+        colouring order is made of -- and the degeneracy.  The call waits for the device."""
+        B, n = self.backend, self.n_
+        peel = B.alloc(2 * n, np.float32)                            # (32-bit words: the core numbers, then the order)
+        degeneracy = self.SpMV_.kcore(B.view(peel, 0, n, 4), B.view(peel, n, n, 4))[0]
+        B.sync()
+        return B.download(peel, np.uint32, 2 * n)[n:], degeneracy
+
+
+class _WeightedPatternApp(_PatternApp):
+    """... and of those whose kernels take a weight per entry: _prepare() leaves the symmetric weighted matrix in graph_, with
+    the weights in adj_data, and returns _ones_of_graph(), because the row copy would store a zero value as no entry; the
+    weights travel in a buffer of their own, aligned with graph_.adj_indices."""
+    degrees_ = graph_ = weight_buf_ = edges_ = weights_ = total_weight_ = None
+
+    def _ones_of_graph(self):
+        self.weight_buf_ = None
+        g = self.graph_
+        return io.CSRMatrix(g.num_rows, g.num_cols, np.ones(g.nnz, dtype=np.float32), g.adj_indices, g.adj_indptr)
+
+    def send_matrix_host_to_device(self):
+        _PatternApp.send_matrix_host_to_device(self)
+        self.weight_buf_ = self.backend.alloc(max(1, self.graph_.nnz), np.float32)
+        if self.graph_.nnz:
+            self.backend.upload(self.weight_buf_, self.graph_.adj_data)
+
+    def _collect_edges(self, chosen):
+        """-> bool[graph_.nnz]: chosen(rows, cols) over the entries of graph_.  Leaves edges_ (int64[m, 2]: (lo, hi) of every
+        chosen edge, once, ascending), weights_ (float32[m], aligned with edges_) and total_weight_ (their f64 sum in that
+        order)."""
+        rows = np.repeat(np.arange(self.n_, dtype=np.int64), np.diff(self.graph_.adj_indptr.astype(np.int64)))
+        cols = self.graph_.adj_indices.astype(np.int64)
+        mask = chosen(rows, cols)
+        once = np.flatnonzero(mask & (cols > rows))
+        self.edges_ = np.stack([rows[once], cols[once]], axis=1)
+        self.weights_ = self.graph_.adj_data[once]
+        self.total_weight_ = float(np.cumsum(self.weights_, dtype=np.float64)[-1]) if once.size else 0.0     # (cumsum: one by one, in order)
+        return mask
+
 
 class ConnectedComponents(_PatternApp):
     """Weakly connected components: gl_cc_labels, lock-free union-find over the rows, then pointer doubling.
@@ -1898,7 +1938,7 @@ class KTruss(_PatternApp):
         return self.truss_ >= k
 
 
-class MinimumSpanningForest(_PatternApp):
+class MinimumSpanningForest(_WeightedPatternApp):
     """Minimum spanning forest: gl_msf, Boruvka's algorithm over the rows with a weight per entry.  The matrix is
     read as an undirected weighted graph and stored in both directions by the host (io.symmetrize_weighted: the diagonal is
     dropped, every other stored entry is an edge -- a stored 0 included --, an edge stored more than once gets its smallest
@@ -1908,8 +1948,7 @@ class MinimumSpanningForest(_PatternApp):
     lo, hi), a strict total order, so the forest is unique: the one Kruskal's algorithm returns taking the edges in that order."""
     _no_shards_ = ("gl_msf reads the component of every column of a row and the rows of both ends of a chosen edge, so every rank "
                    "would need the whole symmetric matrix and the whole forest")
-    degrees_ = graph_ = in_forest_ = edges_ = weights_ = total_weight_ = num_edges_ = num_components_ = labels_ = None
-    rounds_ = launches_ = weight_buf_ = None
+    in_forest_ = num_edges_ = num_components_ = labels_ = rounds_ = launches_ = None
     weighted_ = True
 
     def load_and_format_matrix(self, csr_float_npz_path, skip_empty_rows=True, weighted=True):
@@ -1918,15 +1957,8 @@ class MinimumSpanningForest(_PatternApp):
 
     def _prepare(self, csr):
         self.graph_, self.degrees_ = io.symmetrize_weighted(csr, self.weighted_)
-        self.in_forest_ = self.weight_buf_ = None
-        g = self.graph_
-        return io.CSRMatrix(g.num_rows, g.num_cols, np.ones(g.nnz, dtype=np.float32), g.adj_indices, g.adj_indptr)
-
-    def send_matrix_host_to_device(self):
-        _PatternApp.send_matrix_host_to_device(self)
-        self.weight_buf_ = self.backend.alloc(max(1, self.graph_.nnz), np.float32)
-        if self.graph_.nnz:
-            self.backend.upload(self.weight_buf_, self.graph_.adj_data)
+        self.in_forest_ = None
+        return self._ones_of_graph()
 
     def run(self, labels=False):
         """-> bool[graph_.nnz]: in_forest[j] = the edge of entry j is in the minimum spanning forest.  Leaves in_forest_, edges_
@@ -1946,15 +1978,11 @@ class MinimumSpanningForest(_PatternApp):
         self.labels_ = got[room:] if labels else None
         self.num_edges_, components, self.rounds_, self.launches_ = stats
         self.num_components_ = components - (n - self.n_real_)
-        rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(self.graph_.adj_indptr.astype(np.int64)))
-        once = np.flatnonzero(self.in_forest_ & (self.graph_.adj_indices.astype(np.int64) > rows))
-        self.edges_ = np.stack([rows[once], self.graph_.adj_indices[once].astype(np.int64)], axis=1)
-        self.weights_ = self.graph_.adj_data[once]
-        self.total_weight_ = float(np.cumsum(self.weights_, dtype=np.float64)[-1]) if once.size else 0.0     # (cumsum: one by one, in order)
+        self._collect_edges(lambda rows, cols: self.in_forest_)
         return self.in_forest_
 
 
-class Matching(_PatternApp):
+class Matching(_WeightedPatternApp):
     """Greedy weighted matching: gl_match, the locally dominant matching over the rows with a weight per entry.
     The matrix is read as an undirected weighted graph and stored in both directions by the host (io.symmetrize_weighted with
     keep="largest": the diagonal is dropped, every other stored entry is an edge -- a stored 0 included --, an edge stored more
@@ -1966,8 +1994,7 @@ class Matching(_PatternApp):
     the result is unique: the matching that takes the edges greedily in that order."""
     _no_shards_ = ("gl_match reads the mate of every column of a row and the rows of both ends of a matched edge, so every rank "
                    "would need the whole symmetric matrix and every vertex's mate")
-    degrees_ = graph_ = mate_ = in_matching_ = edges_ = weights_ = total_weight_ = num_matched_ = None
-    rounds_ = scans_ = launches_ = weight_buf_ = None
+    mate_ = in_matching_ = num_matched_ = rounds_ = scans_ = launches_ = None
     weighted_, drop_nonpositive_ = True, False
 
     def load_and_format_matrix(self, csr_float_npz_path, skip_empty_rows=True, weighted=True, drop_nonpositive=False):
@@ -1976,15 +2003,8 @@ class Matching(_PatternApp):
 
     def _prepare(self, csr):
         self.graph_, self.degrees_ = _matching_graph_of(csr, self.weighted_, self.drop_nonpositive_)
-        self.mate_ = self.weight_buf_ = None
-        g = self.graph_
-        return io.CSRMatrix(g.num_rows, g.num_cols, np.ones(g.nnz, dtype=np.float32), g.adj_indices, g.adj_indptr)
-
-    def send_matrix_host_to_device(self):
-        _PatternApp.send_matrix_host_to_device(self)
-        self.weight_buf_ = self.backend.alloc(max(1, self.graph_.nnz), np.float32)
-        if self.graph_.nnz:
-            self.backend.upload(self.weight_buf_, self.graph_.adj_data)
+        self.mate_ = None
+        return self._ones_of_graph()
 
     def run(self):
         """-> uint32[n_]: mate[v] = the vertex v is matched to, MATCH_FREE (0xffffffff) for a free vertex.  Leaves mate_,
@@ -1999,13 +2019,7 @@ class Matching(_PatternApp):
         B.sync()
         self.mate_ = B.download(out, np.uint32, max(1, n))[:n]
         self.num_matched_, self.rounds_, self.scans_, self.launches_ = stats
-        rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(self.graph_.adj_indptr.astype(np.int64)))
-        cols = self.graph_.adj_indices.astype(np.int64)
-        self.in_matching_ = self.mate_.astype(np.int64)[rows] == cols
-        once = np.flatnonzero(self.in_matching_ & (cols > rows))
-        self.edges_ = np.stack([rows[once], cols[once]], axis=1)
-        self.weights_ = self.graph_.adj_data[once]
-        self.total_weight_ = float(np.cumsum(self.weights_, dtype=np.float64)[-1]) if once.size else 0.0     # (cumsum: one by one, in order)
+        self.in_matching_ = self._collect_edges(lambda rows, cols: self.mate_.astype(np.int64)[rows] == cols)
         return self.mate_
 
 
@@ -2038,10 +2052,8 @@ class GraphColoring(_PatternApp):
                 raise ValueError("GraphColoring.run(): priorities of shape %s, expected %d or %d words" % (prio.shape, self.n_real_, n))
             prio = np.concatenate([prio.astype(np.uint32), np.zeros(n - prio.shape[0], dtype=np.uint32)])
         elif order == "smallest_last":
-            peel = B.alloc(2 * n, np.float32)                        # (32-bit words: the core numbers, then the order)
-            self.degeneracy_ = self.SpMV_.kcore(B.view(peel, 0, n, 4), B.view(peel, n, n, 4))[0]
-            B.sync()
-            prio = io.coloring_priorities(self.degrees_, order, seed, peel_order=B.download(peel, np.uint32, 2 * n)[n:])
+            peel_order, self.degeneracy_ = self._peel_order()
+            prio = io.coloring_priorities(self.degrees_, order, seed, peel_order=peel_order)
         else:
             prio = io.coloring_priorities(self.degrees_, order, seed)
         out = B.alloc(2 * n if prio is not None else n, np.float32)  # (32-bit words: the colours, then the priorities)
@@ -2119,10 +2131,7 @@ class LabelPropagation(_PatternApp):
         else:
             seed0 = 0 if seed is None else seed
             if order == "smallest_last":
-                peel = B.alloc(2 * n, np.float32)                    # (32-bit words: the core numbers, then the order)
-                self.SpMV_.kcore(B.view(peel, 0, n, 4), B.view(peel, n, n, 4))
-                B.sync()
-                prio = io.coloring_priorities(self.degrees_, order, seed0, peel_order=B.download(peel, np.uint32, 2 * n)[n:])
+                prio = io.coloring_priorities(self.degrees_, order, seed0, peel_order=self._peel_order()[0])
             else:
                 prio = io.coloring_priorities(self.degrees_, order, seed0)
             if prio is not None:

@@ -8,10 +8,7 @@
 #ifndef GRAPHLILY_HIP_APP_CC_H_
 #define GRAPHLILY_HIP_APP_CC_H_
 
-#include "graphlily/app/module_collection.h"
-#include "graphlily/module/spmv_module.h"
-#include "graphlily/io/data_loader.h"
-#include "graphlily/io/data_formatter.h"
+#include "graphlily/app/pattern_app.h"
 
 #include <algorithm>
 #include <vector>
@@ -19,55 +16,20 @@
 namespace graphlily {
 namespace app {
 
-class ConnectedComponents : public app::ModuleCollection {
+class ConnectedComponents : public app::PatternApp {
 private:
-    graphlily::module::SpMVModule<graphlily::val_t, graphlily::val_t> *SpMV_;
-    uint32_t matrix_num_rows_ = 0, matrix_num_cols_ = 0;
-    uint32_t num_channels_, spmv_out_buf_len_, vec_buf_len_;
-    graphlily::SemiringType semiring_ = graphlily::LogicalSemiring;
-    uint32_t n_real_ = 0;
-    bool sent_ = false;
     uint32_t num_components_ = 0, largest_component_ = 0;
 
 public:
     typedef std::vector<uint32_t, aligned_allocator<uint32_t>> aligned_label_vec_t;
 
     ConnectedComponents(uint32_t num_channels, uint32_t spmv_out_buf_len, uint32_t vec_buf_len)
-        : num_channels_(num_channels), spmv_out_buf_len_(spmv_out_buf_len), vec_buf_len_(vec_buf_len) {
-        SpMV_ = new graphlily::module::SpMVModule<graphlily::val_t, graphlily::val_t>(num_channels_, spmv_out_buf_len_, vec_buf_len_);
-        SpMV_->set_semiring(semiring_);
-        SpMV_->set_mask_type(graphlily::kNoMask);
-        add_module(SpMV_);
-    }
-
-    uint32_t get_nnz() { return SpMV_->get_nnz(); }
-    uint32_t num_vertices() const { return matrix_num_rows_; }      // the padded matrix's
-    uint32_t num_real_vertices() const { return n_real_; }
-
-    void load_and_format_matrix(std::string csr_float_npz_path, bool skip_empty_rows) {
-        CSRMatrix<float> csr_matrix = graphlily::io::load_csr_matrix_from_float_npz(csr_float_npz_path);
-        n_real_ = csr_matrix.num_rows;
-        graphlily::io::util_round_csr_matrix_dim(csr_matrix, num_channels_ * graphlily::pack_size, num_channels_ * graphlily::pack_size);
-        for (auto &x : csr_matrix.adj_data) x = 1;      // every stored entry is an edge, as in BFS
-        SpMV_->load_and_format_matrix(csr_matrix, skip_empty_rows);
-        matrix_num_rows_ = SpMV_->get_num_rows();
-        matrix_num_cols_ = SpMV_->get_num_cols();
-        assert(matrix_num_rows_ == matrix_num_cols_);
-        sent_ = false;
-    }
-
-    void send_matrix_host_to_device() {
-        SpMV_->send_matrix_host_to_device();
-        sent_ = true;
-    }
+        : PatternApp("ConnectedComponents", num_channels, spmv_out_buf_len, vec_buf_len) {}      // (PatternApp's prepare(): every stored entry an edge)
 
     // labels of the padded matrix's vertices (padding vertices are singletons); leaves num_components() -- over the real
     // vertices -- and largest_component()
     aligned_label_vec_t run() {
-        if (!sent_) {
-            printf("ConnectedComponents::run(): send_matrix_host_to_device first\n");
-            exit(EXIT_FAILURE);
-        }
+        require_sent("run()");
         const uint32_t n = matrix_num_rows_;
         DeviceBuffer out(sizeof(uint32_t) * ((size_t)n + 1));      // vertex numbers, then the component count
         SpMV_->cc_labels(out, (uint32_t *)out.ptr() + n);

@@ -11,10 +11,7 @@
 #ifndef GRAPHLILY_HIP_APP_LPA_H_
 #define GRAPHLILY_HIP_APP_LPA_H_
 
-#include "graphlily/app/module_collection.h"
-#include "graphlily/module/spmv_module.h"
-#include "graphlily/io/data_loader.h"
-#include "graphlily/io/data_formatter.h"
+#include "graphlily/app/pattern_app.h"
 
 #include <algorithm>
 #include <string>
@@ -23,52 +20,26 @@
 namespace graphlily {
 namespace app {
 
-class LabelPropagation : public app::ModuleCollection {
+class LabelPropagation : public app::PatternApp {
 private:
-    graphlily::module::SpMVModule<graphlily::val_t, graphlily::val_t> *SpMV_;
-    uint32_t matrix_num_rows_ = 0, matrix_num_cols_ = 0;
-    uint32_t num_channels_, spmv_out_buf_len_, vec_buf_len_;
-    graphlily::SemiringType semiring_ = graphlily::LogicalSemiring;
-    uint32_t n_real_ = 0;
-    bool sent_ = false;
     CSRMatrix<float> graph_;
-    std::vector<uint32_t> degrees_, labels_, colors_, initial_, community_labels_;
+    std::vector<uint32_t> labels_, colors_, initial_, community_labels_;
     std::vector<uint64_t> community_sizes_;
     uint64_t num_colors_ = 0, sweeps_ = 0, changes_ = 0, evaluations_ = 0, launches_ = 0, converged_ = 0;
+
+    // get_nnz() counts the entries of the symmetric matrix: twice the undirected edges
+    CSRMatrix<float> prepare(CSRMatrix<float> &padded) override {
+        graph_ = graphlily::io::util_symmetrize_simple(padded, degrees_);
+        return graph_;
+    }
 
 public:
     typedef std::vector<uint32_t, aligned_allocator<uint32_t>> aligned_label_vec_t;
 
     LabelPropagation(uint32_t num_channels, uint32_t spmv_out_buf_len, uint32_t vec_buf_len)
-        : num_channels_(num_channels), spmv_out_buf_len_(spmv_out_buf_len), vec_buf_len_(vec_buf_len) {
-        SpMV_ = new graphlily::module::SpMVModule<graphlily::val_t, graphlily::val_t>(num_channels_, spmv_out_buf_len_, vec_buf_len_);
-        SpMV_->set_semiring(semiring_);
-        SpMV_->set_mask_type(graphlily::kNoMask);
-        add_module(SpMV_);
-    }
+        : PatternApp("LabelPropagation", num_channels, spmv_out_buf_len, vec_buf_len) {}
 
-    uint32_t get_nnz() { return SpMV_->get_nnz(); }                 // entries of the symmetric matrix: twice the undirected edges
-    uint32_t num_vertices() const { return matrix_num_rows_; }      // the padded matrix's
-    uint32_t num_real_vertices() const { return n_real_; }
-    const std::vector<uint32_t> &degrees() const { return degrees_; }
     const CSRMatrix<float> &graph() const { return graph_; }        // the symmetric matrix
-
-    void load_and_format_matrix(std::string csr_float_npz_path, bool skip_empty_rows) {
-        CSRMatrix<float> csr_matrix = graphlily::io::load_csr_matrix_from_float_npz(csr_float_npz_path);
-        n_real_ = csr_matrix.num_rows;
-        graphlily::io::util_round_csr_matrix_dim(csr_matrix, num_channels_ * graphlily::pack_size, num_channels_ * graphlily::pack_size);
-        graph_ = graphlily::io::util_symmetrize_simple(csr_matrix, degrees_);      // after padding
-        SpMV_->load_and_format_matrix(graph_, skip_empty_rows);
-        matrix_num_rows_ = SpMV_->get_num_rows();
-        matrix_num_cols_ = SpMV_->get_num_cols();
-        assert(matrix_num_rows_ == matrix_num_cols_);
-        sent_ = false;
-    }
-
-    void send_matrix_host_to_device() {
-        SpMV_->send_matrix_host_to_device();
-        sent_ = true;
-    }
 
     // labels of the padded matrix's vertices (padding vertices keep their own numbers), swept under the colouring gl_color gives
     // on the same plan for graphlily::io::util_coloring_priorities(degrees(), order, seed) ("smallest_last" first runs gl_kcore),
@@ -79,10 +50,7 @@ public:
     // modularity().  The call waits for the device.
     aligned_label_vec_t run(uint32_t max_sweeps = 100, std::string order = "largest_first", bool with_seed = false, uint32_t seed = 0,
                             bool synchronous = false, std::vector<uint32_t> const &initial = std::vector<uint32_t>()) {
-        if (!sent_) {
-            printf("LabelPropagation::run(): send_matrix_host_to_device first\n");
-            exit(EXIT_FAILURE);
-        }
+        require_sent("run()");
         const size_t n = matrix_num_rows_, words = n ? n : 1;
         DeviceBuffer out(sizeof(uint32_t) * words), color(sizeof(uint32_t) * words), third(sizeof(uint32_t) * words);   // third: the priorities, then the initial labels
         uint32_t *d_color = (uint32_t *)color.ptr(), *d_third = (uint32_t *)third.ptr();
@@ -102,16 +70,10 @@ public:
         if (!synchronous) {
             const uint32_t seed0 = with_seed ? seed : 0;
             std::vector<uint32_t> prio;
-            if (order == "smallest_last") {
-                DeviceBuffer peel(sizeof(uint32_t) * 2 * words);          // the core numbers, then the order
-                uint32_t kstats[4] = {0, 0, 0, 0};
-                SpMV_->kcore(peel, (uint32_t *)peel.ptr() + n, kstats);
-                std::vector<uint32_t> both(2 * n);
-                peel.download(both.data(), sizeof(uint32_t) * 2 * n);
-                prio = graphlily::io::util_coloring_priorities(degrees_, order, seed0, std::vector<uint32_t>(both.begin() + n, both.end()));
-            } else {
+            if (order == "smallest_last")
+                prio = graphlily::io::util_coloring_priorities(degrees_, order, seed0, peel_order());
+            else
                 prio = graphlily::io::util_coloring_priorities(degrees_, order, seed0);
-            }
             if (!prio.empty()) GRAPHLILY_CHECK(gl_buf_h2d(d_third, prio.data(), sizeof(uint32_t) * n));
             uint64_t cstats[4] = {0, 0, 0, 0};
             SpMV_->color(color, prio.empty() ? nullptr : d_third, cstats);

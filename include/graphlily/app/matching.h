@@ -12,57 +12,23 @@
 #ifndef GRAPHLILY_HIP_APP_MATCHING_H_
 #define GRAPHLILY_HIP_APP_MATCHING_H_
 
-#include "graphlily/app/module_collection.h"
-#include "graphlily/module/spmv_module.h"
-#include "graphlily/io/data_loader.h"
-#include "graphlily/io/data_formatter.h"
+#include "graphlily/app/pattern_app.h"
 
-#include <utility>
 #include <vector>
 
 namespace graphlily {
 namespace app {
 
-class Matching : public app::ModuleCollection {
+class Matching : public app::WeightedPatternApp {
 private:
-    graphlily::module::SpMVModule<graphlily::val_t, graphlily::val_t> *SpMV_;
-    uint32_t matrix_num_rows_ = 0, matrix_num_cols_ = 0;
-    uint32_t num_channels_, spmv_out_buf_len_, vec_buf_len_;
-    graphlily::SemiringType semiring_ = graphlily::LogicalSemiring;
-    uint32_t n_real_ = 0;
-    bool sent_ = false;
-    CSRMatrix<float> graph_;
-    DeviceBuffer weight_;
-    std::vector<uint32_t> degrees_;
-    std::vector<std::pair<uint32_t, uint32_t>> edges_;
-    std::vector<float> weights_;
-    double total_weight_ = 0.0;
+    bool weighted_ = true, drop_nonpositive_ = false;
+    std::vector<uint32_t> mate_;
     uint64_t num_matched_ = 0, rounds_ = 0, scans_ = 0, launches_ = 0;
 
-public:
-    typedef std::vector<uint32_t, aligned_allocator<uint32_t>> aligned_mate_vec_t;
-    static const uint32_t kFree = 0xffffffffu;                       // mate()[v] of a vertex that stays free
-
-    Matching(uint32_t num_channels, uint32_t spmv_out_buf_len, uint32_t vec_buf_len)
-        : num_channels_(num_channels), spmv_out_buf_len_(spmv_out_buf_len), vec_buf_len_(vec_buf_len) {
-        SpMV_ = new graphlily::module::SpMVModule<graphlily::val_t, graphlily::val_t>(num_channels_, spmv_out_buf_len_, vec_buf_len_);
-        SpMV_->set_semiring(semiring_);
-        SpMV_->set_mask_type(graphlily::kNoMask);
-        add_module(SpMV_);
-    }
-
-    uint32_t get_nnz() { return SpMV_->get_nnz(); }                 // entries of the symmetric matrix: twice the undirected edges
-    uint32_t num_vertices() const { return matrix_num_rows_; }      // the padded matrix's
-    uint32_t num_real_vertices() const { return n_real_; }
-    const std::vector<uint32_t> &degrees() const { return degrees_; }
-    const CSRMatrix<float> &graph() const { return graph_; }        // the symmetric matrix, weights in adj_data
-
-    void load_and_format_matrix(std::string csr_float_npz_path, bool skip_empty_rows, bool weighted = true, bool drop_nonpositive = false) {
-        CSRMatrix<float> csr_matrix = graphlily::io::load_csr_matrix_from_float_npz(csr_float_npz_path);
-        n_real_ = csr_matrix.num_rows;
-        graphlily::io::util_round_csr_matrix_dim(csr_matrix, num_channels_ * graphlily::pack_size, num_channels_ * graphlily::pack_size);
-        graph_ = graphlily::io::util_symmetrize_weighted(csr_matrix, degrees_, weighted, true);      // after padding
-        if (drop_nonpositive) {
+    // get_nnz() counts the entries of the symmetric matrix: twice the undirected edges
+    CSRMatrix<float> prepare(CSRMatrix<float> &padded) override {
+        graph_ = graphlily::io::util_symmetrize_weighted(padded, degrees_, weighted_, true);
+        if (drop_nonpositive_) {
             CSRMatrix<float> kept;
             kept.num_rows = graph_.num_rows;
             kept.num_cols = graph_.num_cols;
@@ -78,30 +44,26 @@ public:
             }
             graph_ = kept;
         }
-        CSRMatrix<float> ones = graph_;                                    // a zero value would be stored as no entry: plan ones
-        ones.adj_data.assign(ones.adj_indices.size(), 1.0f);
-        SpMV_->load_and_format_matrix(ones, skip_empty_rows);
-        matrix_num_rows_ = SpMV_->get_num_rows();
-        matrix_num_cols_ = SpMV_->get_num_cols();
-        assert(matrix_num_rows_ == matrix_num_cols_);
-        sent_ = false;
+        return ones_of_graph();
     }
 
-    void send_matrix_host_to_device() {
-        SpMV_->send_matrix_host_to_device();
-        const size_t nnz = graph_.adj_data.size();
-        weight_ = DeviceBuffer(sizeof(float) * (nnz ? nnz : 1));
-        if (nnz) weight_.upload(graph_.adj_data.data(), sizeof(float) * nnz);
-        sent_ = true;
+public:
+    typedef std::vector<uint32_t, aligned_allocator<uint32_t>> aligned_mate_vec_t;
+    static const uint32_t kFree = 0xffffffffu;                       // mate()[v] of a vertex that stays free
+
+    Matching(uint32_t num_channels, uint32_t spmv_out_buf_len, uint32_t vec_buf_len)
+        : WeightedPatternApp("Matching", num_channels, spmv_out_buf_len, vec_buf_len) {}
+
+    void load_and_format_matrix(std::string csr_float_npz_path, bool skip_empty_rows, bool weighted = true, bool drop_nonpositive = false) {
+        weighted_ = weighted;
+        drop_nonpositive_ = drop_nonpositive;
+        WeightedPatternApp::load_and_format_matrix(csr_float_npz_path, skip_empty_rows);
     }
 
     // mate[v] = the vertex v is matched to, kFree for a free vertex; leaves edges(), weights(), total_weight(), num_matched(),
     // rounds(), scans() and launches().  The call waits for the device.
     aligned_mate_vec_t run() {
-        if (!sent_) {
-            printf("Matching::run(): send_matrix_host_to_device first\n");
-            exit(EXIT_FAILURE);
-        }
+        require_sent("run()");
         const size_t n = matrix_num_rows_;
         DeviceBuffer out(sizeof(uint32_t) * (n ? n : 1));
         uint64_t stats[4] = {0, 0, 0, 0};
@@ -114,16 +76,7 @@ public:
         rounds_ = stats[1];
         scans_ = stats[2];
         launches_ = stats[3];
-        edges_.clear();
-        weights_.clear();
-        total_weight_ = 0.0;
-        for (size_t v = 0; v < n; v++)
-            for (uint32_t j = graph_.adj_indptr[v]; j < graph_.adj_indptr[v + 1]; j++)
-                if (graph_.adj_indices[j] > v && mate[v] == graph_.adj_indices[j]) {   // once per edge, in entry order: (lo, hi) ascending
-                    edges_.push_back(std::make_pair((uint32_t)v, graph_.adj_indices[j]));
-                    weights_.push_back(graph_.adj_data[j]);
-                    total_weight_ += (double)graph_.adj_data[j];
-                }
+        collect_edges([&](size_t v, uint32_t j) { return mate[v] == graph_.adj_indices[j]; });
         return mate;
     }
     const std::vector<uint32_t> &mate() const { return mate_; }                   // the last run()'s result
@@ -131,12 +84,6 @@ public:
     uint64_t rounds() const { return rounds_; }                                    // rounds in which a vertex pointed or finished
     uint64_t scans() const { return scans_; }                                      // row scans of all rounds
     uint64_t launches() const { return launches_; }
-    double total_weight() const { return total_weight_; }                          // the f64 sum of weights() in entry order
-    const std::vector<std::pair<uint32_t, uint32_t>> &edges() const { return edges_; }   // (lo, hi), ascending
-    const std::vector<float> &weights() const { return weights_; }
-
-private:
-    std::vector<uint32_t> mate_;
 };
 
 }  // namespace app

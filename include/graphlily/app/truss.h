@@ -10,70 +10,38 @@
 #ifndef GRAPHLILY_HIP_APP_TRUSS_H_
 #define GRAPHLILY_HIP_APP_TRUSS_H_
 
-#include "graphlily/app/module_collection.h"
-#include "graphlily/module/spmv_module.h"
-#include "graphlily/io/data_loader.h"
-#include "graphlily/io/data_formatter.h"
+#include "graphlily/app/pattern_app.h"
 
 #include <vector>
 
 namespace graphlily {
 namespace app {
 
-class KTruss : public app::ModuleCollection {
+class KTruss : public app::PatternApp {
 private:
-    graphlily::module::SpMVModule<graphlily::val_t, graphlily::val_t> *SpMV_;
-    uint32_t matrix_num_rows_ = 0, matrix_num_cols_ = 0;
-    uint32_t num_channels_, spmv_out_buf_len_, vec_buf_len_;
-    graphlily::SemiringType semiring_ = graphlily::LogicalSemiring;
-    uint32_t n_real_ = 0;
-    bool sent_ = false;
     CSRMatrix<float> graph_;
-    std::vector<uint32_t> degrees_, support_, vertex_truss_;
+    std::vector<uint32_t> support_, vertex_truss_;
     std::vector<uint64_t> truss_sizes_;
     uint64_t max_truss_ = 0, levels_ = 0, sub_rounds_ = 0, launches_ = 0, num_edges_ = 0, num_triangles_ = 0;
+
+    // get_nnz() counts the entries of the symmetric matrix: twice the undirected edges
+    CSRMatrix<float> prepare(CSRMatrix<float> &padded) override {
+        graph_ = graphlily::io::util_symmetrize_simple(padded, degrees_);
+        return graph_;
+    }
 
 public:
     typedef std::vector<uint32_t, aligned_allocator<uint32_t>> aligned_truss_vec_t;
 
     KTruss(uint32_t num_channels, uint32_t spmv_out_buf_len, uint32_t vec_buf_len)
-        : num_channels_(num_channels), spmv_out_buf_len_(spmv_out_buf_len), vec_buf_len_(vec_buf_len) {
-        SpMV_ = new graphlily::module::SpMVModule<graphlily::val_t, graphlily::val_t>(num_channels_, spmv_out_buf_len_, vec_buf_len_);
-        SpMV_->set_semiring(semiring_);
-        SpMV_->set_mask_type(graphlily::kNoMask);
-        add_module(SpMV_);
-    }
+        : PatternApp("KTruss", num_channels, spmv_out_buf_len, vec_buf_len) {}
 
-    uint32_t get_nnz() { return SpMV_->get_nnz(); }                 // entries of the symmetric matrix: twice the undirected edges
-    uint32_t num_vertices() const { return matrix_num_rows_; }      // the padded matrix's
-    uint32_t num_real_vertices() const { return n_real_; }
-    const std::vector<uint32_t> &degrees() const { return degrees_; }
     const CSRMatrix<float> &graph() const { return graph_; }        // the symmetric simple matrix the results are aligned with
-
-    void load_and_format_matrix(std::string csr_float_npz_path, bool skip_empty_rows) {
-        CSRMatrix<float> csr_matrix = graphlily::io::load_csr_matrix_from_float_npz(csr_float_npz_path);
-        n_real_ = csr_matrix.num_rows;
-        graphlily::io::util_round_csr_matrix_dim(csr_matrix, num_channels_ * graphlily::pack_size, num_channels_ * graphlily::pack_size);
-        graph_ = graphlily::io::util_symmetrize_simple(csr_matrix, degrees_);      // after padding
-        SpMV_->load_and_format_matrix(graph_, skip_empty_rows);
-        matrix_num_rows_ = SpMV_->get_num_rows();
-        matrix_num_cols_ = SpMV_->get_num_cols();
-        assert(matrix_num_rows_ == matrix_num_cols_);
-        sent_ = false;
-    }
-
-    void send_matrix_host_to_device() {
-        SpMV_->send_matrix_host_to_device();
-        sent_ = true;
-    }
 
     // the truss number of every entry's edge; leaves max_truss(), levels(), sub_rounds(), launches(), num_edges(),
     // num_triangles(), truss_sizes(), vertex_truss() and, with want_support, support().  The call waits for the device.
     aligned_truss_vec_t run(bool want_support = false) {
-        if (!sent_) {
-            printf("KTruss::run(): send_matrix_host_to_device first\n");
-            exit(EXIT_FAILURE);
-        }
+        require_sent("run()");
         const size_t n = matrix_num_rows_, nnz = graph_.adj_indices.size(), words = want_support ? 2 * nnz : nnz;
         DeviceBuffer out(sizeof(uint32_t) * (words ? words : 1));    // the truss numbers, then the supports
         uint64_t stats[6] = {0, 0, 0, 0, 0, 0};

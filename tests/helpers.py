@@ -1,10 +1,26 @@
 """Shared helpers for the parity tests (the oracle is the checker, never the thing under test)."""
 import functools
+import os
+import subprocess
 
 import numpy as np
 
 from graphlily_amd import datasets, io
 from oracle import oracle as O
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LIBDIR = os.path.join(ROOT, "graphlily_amd", "lib")
+
+
+def build_cpp_driver(source, *defines):
+    """tests/cpp/<source> against include/, warnings as errors, linked to the HIP library -> the executable's path:
+    build/<source's stem>, followed by _<DEFINE> for every -D<...>_<DEFINE> given (typed_modules_driver_UFIXED)"""
+    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
+    exe = os.path.join(ROOT, "build", "_".join([source[:-len(".cpp")]] + [d.rsplit("_", 1)[-1] for d in defines]))
+    subprocess.check_call(["g++", "-std=c++11", "-O2", "-Wall", "-Werror"] + list(defines) +
+                          ["-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", source), "-o", exe,
+                           "-L", LIBDIR, "-lgraphlily_hip", "-Wl,-rpath," + LIBDIR])
+    return exe
 
 
 def to_oracle(m):

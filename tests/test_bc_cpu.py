@@ -18,11 +18,10 @@ import pytest
 from graphlily_amd import app, capi, io, module as M
 
 from cpu_backend import CpuBackend
-from helpers import named_matrix
+from helpers import build_cpp_driver, named_matrix
 from test_kcore_cpu import _TwoRanks, _csr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIBDIR = os.path.join(ROOT, "graphlily_amd", "lib")
 BC_DRIVER = os.path.join(ROOT, "build", "bc_driver")
 DECL = ("int gl_bc_accumulate(gl_spmv_plan plan_in, gl_spmv_plan plan_out, const float *d_level, double *d_bc, double scale, int accumulate,\n"
         "                     double *d_sigma /* may be NULL: plan scratch */,\n"
@@ -382,13 +381,6 @@ def test_driver_refuses_row_shards_and_a_run_before_send(golden_dir):
     assert two.directed_ is True and two.out_ is not None
 
 
-def build_cpp_driver():
-    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
-    subprocess.check_call(["g++", "-std=c++11", "-O2", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "bc_driver.cpp"), "-o", BC_DRIVER,
-                           "-L", LIBDIR, "-lgraphlily_hip", "-Wl,-rpath," + LIBDIR])
-
-
 def save_npz(m, path):
     import scipy.sparse as sp
     A = sp.csr_matrix((m.adj_data, m.adj_indices.astype(np.int32), m.adj_indptr.astype(np.int32)), shape=(m.num_rows, m.num_cols), dtype=np.float32)
@@ -396,7 +388,7 @@ def save_npz(m, path):
 
 
 def test_cpp_driver_compiles_and_prepares_the_pattern_alike(tmp_path):
-    build_cpp_driver()
+    build_cpp_driver("bc_driver.cpp")
     raw = prepared("rmat_20K")[0]
     path = str(tmp_path / "rmat_20K_csr_float32.npz")
     save_npz(raw, path)

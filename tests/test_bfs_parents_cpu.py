@@ -10,8 +10,9 @@ import pytest
 
 from graphlily_amd import app, capi, datasets, io
 
+from helpers import build_cpp_driver
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIBDIR = os.path.join(ROOT, "graphlily_amd", "lib")
 PARENTS_DRIVER = os.path.join(ROOT, "build", "bfs_parents_driver")
 NONE = np.uint32(0xFFFFFFFF)
 
@@ -177,10 +178,7 @@ def test_orphans_of_a_level_array_that_is_no_bfs_result(golden_dir):
 
 
 def test_cpp_driver_compiles_and_fails_loudly_without_gpu(tmp_path):
-    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
-    subprocess.check_call(["g++", "-std=c++11", "-O2", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "bfs_parents_driver.cpp"), "-o", PARENTS_DRIVER,
-                           "-L", LIBDIR, "-lgraphlily_hip", "-Wl,-rpath," + LIBDIR])
+    build_cpp_driver("bfs_parents_driver.cpp")
     if capi.device_count() == 0:
         r = subprocess.run([PARENTS_DRIVER, str(tmp_path / "none.npz"), str(tmp_path), "0", "4"], capture_output=True, text=True)
         assert r.returncode != 0

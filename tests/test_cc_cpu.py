@@ -13,10 +13,9 @@ import pytest
 from graphlily_amd import app, capi, datasets, io, module as M
 
 from cpu_backend import CpuBackend
-from helpers import named_matrix
+from helpers import build_cpp_driver, named_matrix
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIBDIR = os.path.join(ROOT, "graphlily_amd", "lib")
 CC_DRIVER = os.path.join(ROOT, "build", "cc_driver")
 SYMBOLS = ("gl_cc_begin", "gl_cc_hook", "gl_cc_finish", "gl_cc_labels")
 
@@ -249,10 +248,7 @@ def test_driver_refuses_row_shards_and_a_run_before_send(golden_dir):
 
 
 def test_cpp_driver_compiles_and_fails_loudly_without_gpu(tmp_path):
-    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
-    subprocess.check_call(["g++", "-std=c++11", "-O2", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "cc_driver.cpp"), "-o", CC_DRIVER,
-                           "-L", LIBDIR, "-lgraphlily_hip", "-Wl,-rpath," + LIBDIR])
+    build_cpp_driver("cc_driver.cpp")
     if capi.device_count() == 0:
         r = subprocess.run([CC_DRIVER, str(tmp_path / "none.npz"), str(tmp_path)], capture_output=True, text=True)
         assert r.returncode != 0

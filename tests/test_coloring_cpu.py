@@ -15,11 +15,10 @@ import pytest
 from graphlily_amd import app, capi, io, module as M
 
 from cpu_backend import CpuBackend
-from helpers import named_matrix
+from helpers import build_cpp_driver, named_matrix
 from test_kcore_cpu import _TwoRanks, _csr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIBDIR = os.path.join(ROOT, "graphlily_amd", "lib")
 COLORING_DRIVER = os.path.join(ROOT, "build", "coloring_driver")
 DECL = ("int gl_color(gl_spmv_plan plan, const uint32_t *d_prio /* may be NULL */, uint32_t *d_color, "
         "uint64_t *h_stats /* may be NULL, 4 words: num_colors, rounds, launches, widest */);")
@@ -343,13 +342,6 @@ def test_driver_refuses_row_shards_and_runs_before_send(golden_dir):
     assert gc.colors_ is None and gc.num_colors_ is None and gc.degeneracy_ is None
 
 
-def build_cpp_driver():
-    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
-    subprocess.check_call(["g++", "-std=c++11", "-O2", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "coloring_driver.cpp"), "-o", COLORING_DRIVER,
-                           "-L", LIBDIR, "-lgraphlily_hip", "-Wl,-rpath," + LIBDIR])
-
-
 def save_npz(path, m):
     import scipy.sparse as sp
     A = sp.csr_matrix((m.adj_data, m.adj_indices.astype(np.int32), m.adj_indptr.astype(np.int32)), shape=(m.num_rows, m.num_cols), dtype=np.float32)
@@ -357,7 +349,7 @@ def save_npz(path, m):
 
 
 def test_cpp_driver_compiles_computes_the_same_priorities_and_fails_loudly_without_gpu(tmp_path):
-    build_cpp_driver()
+    build_cpp_driver("coloring_driver.cpp")
     raw = graph("uniform_10K_10")[0]
     path = str(tmp_path / "uniform_csr_float32.npz")
     save_npz(path, raw)

@@ -5,12 +5,15 @@ a GPU; where /root/reference exists, the reference's own app drivers compile UNM
 headers (oracle/Makefile `ref_apps`).
 GPU: the parity driver runs every module against its compute_reference_results; the prebuilt reference
 drivers (if they travelled with the snapshot) run BFS / PageRank / SSSP end to end on the HIP backend."""
+import glob
 import os
 import subprocess
 import sys
 
 import numpy as np
 import pytest
+
+from helpers import build_cpp_driver
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIBDIR = os.path.join(ROOT, "graphlily_amd", "lib")
@@ -19,37 +22,22 @@ REF_APPS = os.path.join(ROOT, "oracle", "_ref", "ref_apps_on_hip")
 APPS_DRIVER = os.path.join(ROOT, "build", "apps_driver")
 
 
-def _build_apps_driver():
-    """tests/cpp/apps_driver.cpp against include/graphlily/app/{bfs,sssp,pagerank}.h -- this repo's own app drivers (the
-    reference's classes over the device-resident schedules); needs no reference tree."""
-    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
-    subprocess.check_call(["g++", "-std=c++11", "-O2", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "apps_driver.cpp"), "-o", APPS_DRIVER,
-                           "-L", LIBDIR, "-lgraphlily_hip", "-Wl,-rpath," + LIBDIR])
-
-
-def _build_driver():
-    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
-    subprocess.check_call(["g++", "-std=c++11", "-O2", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "modules_driver.cpp"), "-o", DRIVER,
-                           "-L", LIBDIR, "-lgraphlily_hip", "-Wl,-rpath," + LIBDIR])
-
-
-def _build_typed_driver(define):
-    """tests/cpp/typed_modules_driver.cpp with val_t = the reference's default fixed point (-DGRAPHLILY_VAL_UFIXED) or
-    unsigned (-DGRAPHLILY_VAL_UNSIGNED): global.h:62-64 of the reference."""
-    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
-    out = os.path.join(ROOT, "build", "typed_modules_driver_" + define)
-    subprocess.check_call(["g++", "-std=c++11", "-O2", "-Wall", "-Werror", "-DGRAPHLILY_VAL_" + define,
-                           "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "typed_modules_driver.cpp"),
-                           "-o", out, "-L", LIBDIR, "-lgraphlily_hip", "-Wl,-rpath," + LIBDIR])
-    return out
+def test_the_entry_point_lists_every_cpp_driver():
+    """build() and tests/cpp/ agree on the drivers: a new one cannot be added to one place and forgotten in the other.
+    typed_modules_driver.cpp is no entry of the list: it is for the integer value types, so the tests below build it once per
+    -DGRAPHLILY_VAL_* define and build(), which passes no define, leaves it alone."""
+    import __graft_entry__ as entry
+    on_disk = {os.path.basename(p) for p in glob.glob(os.path.join(ROOT, "tests", "cpp", "*_driver.cpp"))}
+    assert len(set(entry.CPP_DRIVERS)) == len(entry.CPP_DRIVERS)
+    assert set(entry.CPP_DRIVERS) == on_disk - {"typed_modules_driver.cpp"}
 
 
 @pytest.mark.parametrize("define", ["UFIXED", "UNSIGNED"])
 def test_module_headers_instantiate_with_the_integer_value_types(define, tmp_path):
+    """tests/cpp/typed_modules_driver.cpp with val_t = the reference's default fixed point (-DGRAPHLILY_VAL_UFIXED) or
+    unsigned (-DGRAPHLILY_VAL_UNSIGNED): global.h:62-64 of the reference."""
     from graphlily_amd import capi
-    exe = _build_typed_driver(define)
+    exe = build_cpp_driver("typed_modules_driver.cpp", "-DGRAPHLILY_VAL_" + define)
     if capi.device_count() == 0:
         r = subprocess.run([exe, str(tmp_path)], capture_output=True, text=True)
         assert r.returncode != 0 and "gl_init" in r.stdout + r.stderr
@@ -66,7 +54,7 @@ def test_reference_app_drivers_compile_with_the_integer_value_types(define, tmp_
 
 def test_module_headers_compile_and_fail_loudly_without_gpu():
     from graphlily_amd import capi
-    _build_driver()
+    build_cpp_driver("modules_driver.cpp")
     if capi.device_count() == 0:
         r = subprocess.run([DRIVER], capture_output=True, text=True)
         assert r.returncode != 0
@@ -75,7 +63,7 @@ def test_module_headers_compile_and_fail_loudly_without_gpu():
 
 def test_app_headers_compile_and_fail_loudly_without_gpu(tmp_path):
     from graphlily_amd import capi
-    _build_apps_driver()
+    build_cpp_driver("apps_driver.cpp")
     if capi.device_count() == 0:
         r = subprocess.run([APPS_DRIVER, str(tmp_path / "none.npz"), str(tmp_path), "4"], capture_output=True, text=True)
         assert r.returncode != 0
@@ -135,7 +123,7 @@ def test_reference_app_drivers_compile_unmodified():
 
 @pytest.mark.gpu
 def test_cpp_module_layer_parity(gpu):
-    _build_driver()
+    build_cpp_driver("modules_driver.cpp")
     r = subprocess.run([DRIVER], capture_output=True, text=True, timeout=90)
     print(r.stdout[-3000:])
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
@@ -153,7 +141,7 @@ def test_cpp_app_drivers_match_the_oracle(gpu, tmp_path, n, nnz, iters):
     from graphlily_amd import datasets
     from oracle import oracle as O
     from helpers import to_oracle
-    _build_apps_driver()
+    build_cpp_driver("apps_driver.cpp")
     m = datasets.rmat(n, nnz, seed=3)
     A = sp.csr_matrix((m.adj_data, m.adj_indices.astype(np.int32), m.adj_indptr.astype(np.int32)), shape=(m.num_rows, m.num_cols),
                       dtype=np.float32)
@@ -196,7 +184,7 @@ def test_cpp_module_layer_integer_value_types(gpu, define, tmp_path):
     graphlily::ufixed_32_8 / value_kind<>::from_float against the oracle's (io/data_loader.h:75-90)."""
     from graphlily_amd import capi
     from oracle import oracle as O
-    exe = _build_typed_driver(define)
+    exe = build_cpp_driver("typed_modules_driver.cpp", "-DGRAPHLILY_VAL_" + define)
     r = subprocess.run([exe, str(tmp_path)], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and "TYPED DRIVER DONE" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
     vt = capi.GL_VAL_UFIXED_32_8 if define == "UFIXED" else capi.GL_VAL_UNSIGNED

@@ -446,7 +446,7 @@ def test_refusals(gpu):
 
 @pytest.mark.parametrize("name", ["uniform_10K_10", "rmat_20K"])
 def test_cpp_driver_equals_the_python_driver(gpu, tmp_path, name):
-    build_cpp_driver()
+    build_cpp_driver("bc_driver.cpp")
     raw, m, cin, cout, directed = prepared(name)
     sources = _fixed_sources(name, raw)[:4]
     path = str(tmp_path / (name + "_csr_float32.npz"))

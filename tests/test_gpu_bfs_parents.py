@@ -11,8 +11,8 @@ from graphlily_amd import app, capi, datasets, io, module as M
 from graphlily_amd.dist import partition_rows_by_nnz
 from oracle import oracle as O
 
-from helpers import named_matrix, to_oracle
-from test_bfs_parents_cpu import LIBDIR, NONE, PARENTS_DRIVER, ROOT, levels_by_definition, parents_by_definition
+from helpers import build_cpp_driver, named_matrix, to_oracle
+from test_bfs_parents_cpu import NONE, PARENTS_DRIVER, levels_by_definition, parents_by_definition
 
 pytestmark = pytest.mark.gpu
 
@@ -231,10 +231,7 @@ def test_full_size_tree_on_the_orkut_stand_in(orkut, gpu):
 
 def test_cpp_driver_equals_the_python_driver(gpu, tmp_path):
     import scipy.sparse as sp
-    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
-    subprocess.check_call(["g++", "-std=c++11", "-O2", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "bfs_parents_driver.cpp"), "-o", PARENTS_DRIVER,
-                           "-L", LIBDIR, "-lgraphlily_hip", "-Wl,-rpath," + LIBDIR])
+    build_cpp_driver("bfs_parents_driver.cpp")
     m = named_matrix("rmat_sym_50K")
     A = sp.csr_matrix((m.adj_data, m.adj_indices.astype(np.int32), m.adj_indptr.astype(np.int32)), shape=(m.num_rows, m.num_cols),
                       dtype=np.float32)

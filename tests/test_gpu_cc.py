@@ -11,8 +11,8 @@ import pytest
 from graphlily_amd import app, capi, datasets, io, module as M
 from graphlily_amd.dist import partition_rows_by_nnz
 
-from helpers import named_matrix
-from test_cc_cpu import CC_DRIVER, LIBDIR, ROOT, components_by_definition, many_components, permute_rows
+from helpers import build_cpp_driver, named_matrix
+from test_cc_cpu import CC_DRIVER, ROOT, components_by_definition, many_components, permute_rows
 
 pytestmark = pytest.mark.gpu
 
@@ -204,10 +204,7 @@ def test_shards_hooked_into_one_forest(gpu, name, world):
 
 def test_cpp_driver_equals_the_python_driver(gpu, tmp_path):
     import scipy.sparse as sp
-    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
-    subprocess.check_call(["g++", "-std=c++11", "-O2", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "cc_driver.cpp"), "-o", CC_DRIVER,
-                           "-L", LIBDIR, "-lgraphlily_hip", "-Wl,-rpath," + LIBDIR])
+    build_cpp_driver("cc_driver.cpp")
     raw, m, want, count = _prepared("rmat_20K")
     A = sp.csr_matrix((raw.adj_data, raw.adj_indices.astype(np.int32), raw.adj_indptr.astype(np.int32)), shape=(raw.num_rows, raw.num_cols),
                       dtype=np.float32)

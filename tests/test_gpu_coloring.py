@@ -123,7 +123,7 @@ def test_smallest_last_needs_at_most_degeneracy_plus_one_colours(gpu, name):
 @pytest.mark.parametrize("name", ["uniform_10K_10", "rmat_20K"])
 @pytest.mark.parametrize("order", ["random", "largest_first"])
 def test_cpp_driver_equals_the_python_driver(gpu, tmp_path, name, order):
-    build_cpp_driver()
+    build_cpp_driver("coloring_driver.cpp")
     raw = graph(name)[0]
     _, want, rounds = reference(name, order)
     path = str(tmp_path / (name + "_csr_float32.npz"))
@@ -142,7 +142,7 @@ def test_cpp_driver_equals_the_python_driver(gpu, tmp_path, name, order):
 
 def test_cpp_driver_smallest_last(gpu, tmp_path):
     """the peeling order is not unique, so the colours are not compared: the driver checks the bound and that the colouring is proper"""
-    build_cpp_driver()
+    build_cpp_driver("coloring_driver.cpp")
     raw, m, _ = graph("rmat_20K")
     path = str(tmp_path / "rmat_20K_csr_float32.npz")
     save_npz(path, raw)

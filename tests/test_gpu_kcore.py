@@ -125,7 +125,7 @@ def test_drivers(gpu, name):
 @pytest.mark.parametrize("name", ["uniform_10K_10", "rmat_20K"])
 def test_cpp_driver_equals_the_python_driver(gpu, tmp_path, name):
     import scipy.sparse as sp
-    build_cpp_driver()
+    build_cpp_driver("kcore_driver.cpp")
     raw, m, sym, want = _reference(name)
     A = sp.csr_matrix((raw.adj_data, raw.adj_indices.astype(np.int32), raw.adj_indptr.astype(np.int32)), shape=(raw.num_rows, raw.num_cols),
                       dtype=np.float32)

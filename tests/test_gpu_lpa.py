@@ -296,7 +296,7 @@ def test_driver_with_seed_colors_initial_and_synchronous(gpu):
 @pytest.mark.parametrize("order,seed,sweeps,sync", [("largest_first", -1, 100, 0), ("natural", 4, 100, 0), ("random", -1, 2, 0), ("largest_first", -1, 5, 1)])
 def test_cpp_driver_equals_the_python_driver(gpu, tmp_path, order, seed, sweeps, sync):
     import scipy.sparse as sp
-    build_cpp_driver()
+    build_cpp_driver("lpa_driver.cpp")
     raw = named_matrix("uniform_10K_10")
     A = sp.csr_matrix((raw.adj_data, raw.adj_indices.astype(np.int32), raw.adj_indptr.astype(np.int32)), shape=(raw.num_rows, raw.num_cols),
                       dtype=np.float32)

@@ -294,7 +294,7 @@ def test_drivers(gpu, weighted, drop):
 @pytest.mark.parametrize("weighted,drop", [(1, 0), (1, 1), (0, 0)])
 def test_cpp_driver_equals_the_python_driver(gpu, tmp_path, weighted, drop):
     import scipy.sparse as sp
-    build_cpp_driver()
+    build_cpp_driver("match_driver.cpp")
     raw = weighted_uniform()
     A = sp.csr_matrix((raw.adj_data, raw.adj_indices.astype(np.int32), raw.adj_indptr.astype(np.int32)), shape=(raw.num_rows, raw.num_cols),
                       dtype=np.float32)                                            # (stored zeros stay stored)

@@ -20,7 +20,8 @@ import pytest
 
 from graphlily_amd import app, capi, module as M
 
-from test_sssp_parents_cpu import GRAPHS, LIBDIR, ROOT, raw_graph
+from helpers import build_cpp_driver
+from test_sssp_parents_cpu import GRAPHS, raw_graph
 from test_pagerank_solve_cpu import (DAMPING, KINDS, PAGERANK_DRIVER, given_personalization, long_run, personalization, prepared_graph,
                                      reference)
 
@@ -293,10 +294,7 @@ def test_reference_order_plans_run_the_same_sequence(gpu):
 def test_cpp_driver_equals_the_python_driver(gpu, tmp_path):
     import scipy.sparse as sp
     if not os.path.exists(PAGERANK_DRIVER):
-        os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
-        subprocess.check_call(["g++", "-std=c++11", "-O2", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                               os.path.join(ROOT, "tests", "cpp", "pagerank_solve_driver.cpp"), "-o", PAGERANK_DRIVER,
-                               "-L", LIBDIR, "-lgraphlily_hip", "-Wl,-rpath," + LIBDIR])
+        build_cpp_driver("pagerank_solve_driver.cpp")
     name = "rmat_sym_4000"
     m = raw_graph(name)
     A = sp.csr_matrix((m.adj_data, m.adj_indices.astype(np.int32), m.adj_indptr.astype(np.int32)), shape=(m.num_rows, m.num_cols),

@@ -2,7 +2,6 @@
 graphlily::app::SSSP::parents): every comparison is np.array_equal -- distances against the oracle's O.sssp on the test's own
 prepared matrix, parents against the numpy statement of the definition (tests/test_sssp_parents_cpu.py) applied to the ORACLE's
 distances, plus app.validate_sssp_tree.  (min,+) is order-independent, the definition is exact: no tolerance, no excluded rows."""
-import os
 import subprocess
 
 import numpy as np
@@ -12,7 +11,8 @@ from graphlily_amd import app, capi, datasets, io, module as M
 from graphlily_amd.dist import partition_rows_by_nnz
 from oracle import oracle as O
 
-from test_sssp_parents_cpu import (GRAPHS, INF, ITERS, LIBDIR, NONE, ROOT, SHORT, SSSP_DRIVER, WEIGHTINGS, distances_by_definition,
+from helpers import build_cpp_driver
+from test_sssp_parents_cpu import (GRAPHS, INF, ITERS, NONE, SHORT, SSSP_DRIVER, WEIGHTINGS, distances_by_definition,
                                    parents_by_definition, prepared_graph, raw_graph, sources, weighted_graph, weights)
 
 pytestmark = pytest.mark.gpu
@@ -246,10 +246,7 @@ def test_row_shards_on_one_gpu(gpu, world):
 
 def test_cpp_driver_equals_the_python_driver(gpu, tmp_path):
     import scipy.sparse as sp
-    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
-    subprocess.check_call(["g++", "-std=c++11", "-O2", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "sssp_parents_driver.cpp"), "-o", SSSP_DRIVER,
-                           "-L", LIBDIR, "-lgraphlily_hip", "-Wl,-rpath," + LIBDIR])
+    build_cpp_driver("sssp_parents_driver.cpp")
     name, kind = "rmat_sym_4000", "int"
     m = weighted_graph(name, kind)
     A = sp.csr_matrix((m.adj_data, m.adj_indices.astype(np.int32), m.adj_indptr.astype(np.int32)), shape=(m.num_rows, m.num_cols),

@@ -12,9 +12,9 @@ import pytest
 
 from graphlily_amd import app, capi, io, module as M
 
-from helpers import named_matrix, set_knob
+from helpers import build_cpp_driver, named_matrix, set_knob
 from test_cc_cpu import many_components, permute_rows
-from test_tc_cpu import (LIBDIR, MANY_CYCLES, ROOT, TC_DRIVER, _csr, _from_scipy, abi_counts, symmetric_simple,
+from test_tc_cpu import (MANY_CYCLES, ROOT, TC_DRIVER, _csr, _from_scipy, abi_counts, symmetric_simple,
                          triangles_by_definition)
 
 pytestmark = pytest.mark.gpu
@@ -269,10 +269,7 @@ def test_refusals(gpu):
 
 def test_cpp_driver_equals_the_python_driver(gpu, tmp_path):
     import scipy.sparse as sp
-    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
-    subprocess.check_call(["g++", "-std=c++11", "-O2", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "tc_driver.cpp"), "-o", TC_DRIVER,
-                           "-L", LIBDIR, "-lgraphlily_hip", "-Wl,-rpath," + LIBDIR])
+    build_cpp_driver("tc_driver.cpp")
     raw, m, want, _ = _prepared("rmat_20K")
     A = sp.csr_matrix((raw.adj_data, raw.adj_indices.astype(np.int32), raw.adj_indptr.astype(np.int32)), shape=(raw.num_rows, raw.num_cols),
                       dtype=np.float32)

@@ -315,7 +315,7 @@ def test_refusals(gpu):
 @pytest.mark.parametrize("name", ["uniform", "rmat"])
 def test_cpp_driver_equals_the_python_driver(gpu, tmp_path, name):
     import scipy.sparse as sp
-    build_cpp_driver()
+    build_cpp_driver("truss_driver.cpp")
     raw, m, sym, want, want_support, levels, sub_rounds = prepared(name)
     A = sp.csr_matrix((raw.adj_data, raw.adj_indices.astype(np.int32), raw.adj_indptr.astype(np.int32)), shape=(raw.num_rows, raw.num_cols),
                       dtype=np.float32)

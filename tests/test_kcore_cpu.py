@@ -13,10 +13,9 @@ import pytest
 from graphlily_amd import app, capi, io, module as M
 
 from cpu_backend import CpuBackend
-from helpers import named_matrix
+from helpers import build_cpp_driver, named_matrix
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIBDIR = os.path.join(ROOT, "graphlily_amd", "lib")
 KCORE_DRIVER = os.path.join(ROOT, "build", "kcore_driver")
 DECL = "int gl_kcore(gl_spmv_plan plan, uint32_t *d_core, uint32_t *d_order /* may be NULL */, uint32_t *h_stats /* may be NULL, 4 words */);"
 # degeneracy and sum of the core numbers of the graphs padded to 128: computed on the CPU by networkx.core_number (3.4.2) and by a
@@ -281,16 +280,9 @@ def test_driver_refuses_row_shards_and_a_run_before_send(golden_dir):
         kc.k_core(1)
 
 
-def build_cpp_driver():
-    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
-    subprocess.check_call(["g++", "-std=c++11", "-O2", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "kcore_driver.cpp"), "-o", KCORE_DRIVER,
-                           "-L", LIBDIR, "-lgraphlily_hip", "-Wl,-rpath," + LIBDIR])
-
-
 def test_cpp_driver_compiles_symmetrizes_alike_and_fails_loudly_without_gpu(tmp_path):
     import scipy.sparse as sp
-    build_cpp_driver()
+    build_cpp_driver("kcore_driver.cpp")
     m = _hand_made()
     A = sp.csr_matrix((m.adj_data, m.adj_indices.astype(np.int32), m.adj_indptr.astype(np.int32)), shape=(m.num_rows, m.num_cols), dtype=np.float32)
     path = str(tmp_path / "hand_made_csr_float32.npz")

@@ -17,11 +17,10 @@ import pytest
 from graphlily_amd import app, capi, io, module as M
 
 from cpu_backend import CpuBackend
-from helpers import named_matrix
+from helpers import build_cpp_driver, named_matrix
 from test_msf_cpu import clique_edges, entry_rows, raw_csr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIBDIR = os.path.join(ROOT, "graphlily_amd", "lib")
 LPA_DRIVER = os.path.join(ROOT, "build", "lpa_driver")
 HEADER = "graphlily_hip_lpa.h"
 DECL = ("int gl_lpa(gl_spmv_plan plan, const uint32_t *d_color /* may be NULL: synchronous */, const uint32_t *d_init /* may be NULL: own "
@@ -460,15 +459,8 @@ def test_driver_prepares_the_graph_and_refuses_what_it_cannot_do(golden_dir):
     assert abs(d.modularity(lab) - (6.0 / 7.0 - 0.5)) < 1e-12 and abs(d.modularity(np.zeros(128, np.int64))) < 1e-12
 
 
-def build_cpp_driver():
-    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
-    subprocess.check_call(["g++", "-std=c++11", "-O2", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "lpa_driver.cpp"), "-o", LPA_DRIVER,
-                           "-L", LIBDIR, "-lgraphlily_hip", "-Wl,-rpath," + LIBDIR])
-
-
 def test_cpp_driver_compiles_and_fails_loudly_without_gpu(tmp_path):
-    build_cpp_driver()
+    build_cpp_driver("lpa_driver.cpp")
     if capi.device_count() == 0:
         r = subprocess.run([LPA_DRIVER, str(tmp_path / "none.npz"), str(tmp_path)], capture_output=True, text=True)
         assert r.returncode != 0

@@ -15,11 +15,11 @@ import pytest
 
 from graphlily_amd import app, capi, io, module as M
 
+from helpers import build_cpp_driver
 from cpu_backend import CpuBackend
 from test_msf_cpu import SPECIAL, clique_edges, components_graph, entry_rows, graph_of, keys_of, random_graph, raw_csr, special_graph
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIBDIR = os.path.join(ROOT, "graphlily_amd", "lib")
 MATCH_DRIVER = os.path.join(ROOT, "build", "match_driver")
 HEADER = "graphlily_hip_match.h"
 DECL = "int gl_match(gl_spmv_plan plan, const float *d_weight, uint32_t *d_mate, uint64_t *h_stats /* may be NULL, 4 words */);"
@@ -406,15 +406,8 @@ def test_validate_matching_accepts_the_truth_and_refuses_one_violation_per_rule(
         app.validate_matching(signed, greedy(pos))
 
 
-def build_cpp_driver():
-    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
-    subprocess.check_call(["g++", "-std=c++11", "-O2", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "match_driver.cpp"), "-o", MATCH_DRIVER,
-                           "-L", LIBDIR, "-lgraphlily_hip", "-Wl,-rpath," + LIBDIR])
-
-
 def test_cpp_driver_compiles_and_fails_loudly_without_gpu(tmp_path):
-    build_cpp_driver()
+    build_cpp_driver("match_driver.cpp")
     if capi.device_count() == 0:
         r = subprocess.run([MATCH_DRIVER, str(tmp_path / "none.npz"), str(tmp_path)], capture_output=True, text=True)
         assert r.returncode != 0

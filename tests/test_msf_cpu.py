@@ -13,10 +13,10 @@ import pytest
 
 from graphlily_amd import app, capi, io, module as M
 
+from helpers import build_cpp_driver
 from cpu_backend import CpuBackend
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIBDIR = os.path.join(ROOT, "graphlily_amd", "lib")
 MSF_DRIVER = os.path.join(ROOT, "build", "msf_driver")
 HEADER = "graphlily_hip_msf.h"
 DECL = ("int gl_msf(gl_spmv_plan plan, const float *d_weight, uint32_t *d_in_forest, uint32_t *d_labels /* may be NULL */, "
@@ -389,15 +389,8 @@ def test_driver_refuses_row_shards_and_a_run_before_send(golden_dir):
     assert msf.graph_.nnz == 4 and sorted(msf.graph_.adj_data.tolist()) == [0.0, 0.0, 3.0, 3.0]
 
 
-def build_cpp_driver():
-    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
-    subprocess.check_call(["g++", "-std=c++11", "-O2", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "msf_driver.cpp"), "-o", MSF_DRIVER,
-                           "-L", LIBDIR, "-lgraphlily_hip", "-Wl,-rpath," + LIBDIR])
-
-
 def test_cpp_driver_compiles_and_fails_loudly_without_gpu(tmp_path):
-    build_cpp_driver()
+    build_cpp_driver("msf_driver.cpp")
     if capi.device_count() == 0:
         r = subprocess.run([MSF_DRIVER, str(tmp_path / "none.npz"), str(tmp_path)], capture_output=True, text=True)
         assert r.returncode != 0

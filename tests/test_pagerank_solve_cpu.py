@@ -19,7 +19,8 @@ import pytest
 from graphlily_amd import app, capi, io, module as M
 from graphlily_amd.dist import EmulatedComm
 
-from test_sssp_parents_cpu import GRAPHS, LIBDIR, ROOT, raw_graph
+from helpers import build_cpp_driver
+from test_sssp_parents_cpu import GRAPHS, ROOT, raw_graph
 
 PAGERANK_DRIVER = os.path.join(ROOT, "build", "pagerank_solve_driver")
 DAMPING = 0.85
@@ -261,10 +262,7 @@ def test_solve_refuses_row_shards():
 
 
 def test_cpp_driver_compiles_and_fails_loudly_without_gpu(tmp_path):
-    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
-    subprocess.check_call(["g++", "-std=c++11", "-O2", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "pagerank_solve_driver.cpp"), "-o", PAGERANK_DRIVER,
-                           "-L", LIBDIR, "-lgraphlily_hip", "-Wl,-rpath," + LIBDIR])
+    build_cpp_driver("pagerank_solve_driver.cpp")
     if capi.device_count() == 0:
         r = subprocess.run([PAGERANK_DRIVER, str(tmp_path / "none.npz"), str(tmp_path), "0.85", "1e-6", "10"],
                            capture_output=True, text=True)

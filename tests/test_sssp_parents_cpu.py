@@ -15,8 +15,9 @@ import pytest
 from graphlily_amd import app, capi, datasets, io, module as M
 from oracle import oracle as O
 
+from helpers import build_cpp_driver
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIBDIR = os.path.join(ROOT, "graphlily_amd", "lib")
 SSSP_DRIVER = os.path.join(ROOT, "build", "sssp_parents_driver")
 NONE = np.uint32(0xFFFFFFFF)
 INF = np.float32(M.FLOAT_INF)
@@ -367,10 +368,7 @@ def test_definition_agrees_with_the_validator_on_random_graphs(name, kind):
 
 
 def test_cpp_driver_compiles_and_fails_loudly_without_gpu(tmp_path):
-    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
-    subprocess.check_call(["g++", "-std=c++11", "-O2", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "sssp_parents_driver.cpp"), "-o", SSSP_DRIVER,
-                           "-L", LIBDIR, "-lgraphlily_hip", "-Wl,-rpath," + LIBDIR])
+    build_cpp_driver("sssp_parents_driver.cpp")
     if capi.device_count() == 0:
         r = subprocess.run([SSSP_DRIVER, str(tmp_path / "none.npz"), str(tmp_path), "0", "4"], capture_output=True, text=True)
         assert r.returncode != 0

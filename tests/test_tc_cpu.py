@@ -12,11 +12,10 @@ import pytest
 from graphlily_amd import app, capi, datasets, io, module as M
 
 from cpu_backend import CpuBackend
-from helpers import named_matrix
+from helpers import build_cpp_driver, named_matrix
 from test_cc_cpu import many_components
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIBDIR = os.path.join(ROOT, "graphlily_amd", "lib")
 TC_DRIVER = os.path.join(ROOT, "build", "tc_driver")
 DECL = "int gl_tc_count(gl_spmv_plan plan, uint64_t *d_total, uint64_t *d_per_vertex /* may be NULL */);"
 
@@ -264,10 +263,7 @@ def test_driver_refuses_row_shards_and_a_run_before_send(golden_dir):
 
 
 def test_cpp_driver_compiles_and_fails_loudly_without_gpu(tmp_path):
-    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
-    subprocess.check_call(["g++", "-std=c++11", "-O2", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "tc_driver.cpp"), "-o", TC_DRIVER,
-                           "-L", LIBDIR, "-lgraphlily_hip", "-Wl,-rpath," + LIBDIR])
+    build_cpp_driver("tc_driver.cpp")
     if capi.device_count() == 0:
         r = subprocess.run([TC_DRIVER, str(tmp_path / "none.npz"), str(tmp_path)], capture_output=True, text=True)
         assert r.returncode != 0

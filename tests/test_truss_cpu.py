@@ -13,11 +13,10 @@ import pytest
 from graphlily_amd import app, capi, io, module as M
 
 from cpu_backend import CpuBackend
-from helpers import named_matrix
+from helpers import build_cpp_driver, named_matrix
 from test_tc_cpu import GRAPHS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIBDIR = os.path.join(ROOT, "graphlily_amd", "lib")
 TRUSS_DRIVER = os.path.join(ROOT, "build", "truss_driver")
 HEADER = "graphlily_hip_truss.h"
 DECL = "int gl_truss(gl_spmv_plan plan, uint32_t *d_truss, uint32_t *d_support /* may be NULL */, uint64_t *h_stats /* may be NULL, 6 words */);"
@@ -303,15 +302,8 @@ def test_driver_refuses_row_shards_and_a_run_before_send(golden_dir):
         kt.k_truss(3)
 
 
-def build_cpp_driver():
-    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
-    subprocess.check_call(["g++", "-std=c++11", "-O2", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "truss_driver.cpp"), "-o", TRUSS_DRIVER,
-                           "-L", LIBDIR, "-lgraphlily_hip", "-Wl,-rpath," + LIBDIR])
-
-
 def test_cpp_driver_compiles_and_fails_loudly_without_gpu(tmp_path):
-    build_cpp_driver()
+    build_cpp_driver("truss_driver.cpp")
     if capi.device_count() == 0:
         r = subprocess.run([TRUSS_DRIVER, str(tmp_path / "none.npz"), str(tmp_path)], capture_output=True, text=True)
         assert r.returncode != 0
