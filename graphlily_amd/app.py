@@ -1019,6 +1019,82 @@ def validate_betweenness(csr, bc, sources=None, normalized=False, directed=None)
     return float(np.max(np.abs(got[live] - want[live]) / want[live])) if np.any(live) else 0.0
 
 
+def _edges_of_pattern(csr, n):
+    """-> (src, dst), int64 each: the edges u -> v of the simple directed graph of `csr` among the first n vertices -- u != v, a
+    stored non-zero entry A[v, u]; duplicates stay (they change no reachability)"""
+    ip = np.asarray(csr.adj_indptr).astype(np.int64)[:csr.num_rows + 1]
+    nnz = int(ip[-1])
+    dst = np.repeat(np.arange(csr.num_rows, dtype=np.int64), np.diff(ip))
+    src = np.asarray(csr.adj_indices[:nnz]).astype(np.int64)
+    keep = (np.asarray(csr.adj_data[:nnz]) != 0) & (src != dst) & (src < n) & (dst < n)
+    return src[keep], dst[keep]
+
+
+def _reach_inside(src, dst, start, n):
+    """-> bool[n]: the vertices reached from the vertices `start` (bool[n]) along the edges src[i] -> dst[i], whole sweeps in numpy"""
+    seen = start.copy()
+    while True:
+        step = np.zeros(n, dtype=bool)
+        step[dst[seen[src]]] = True
+        step &= ~seen
+        if not step.any():
+            return seen
+        seen |= step
+
+
+def validate_strong_components(csr, labels):
+    """Host-side check (numpy) that `labels` are the strongly connected components of the simple directed graph of `csr` -- an
+    edge u -> v iff u != v and a stored non-zero entry A[v, u] exists -- each vertex labelled with the SMALLEST vertex of its
+    component.  Raises ValueError naming the first offender and the rule; returns the number of components among the vertices
+    `labels` covers.  The rules:
+      1. labels[labels[v]] == labels[v] and labels[v] <= v;
+      2. every class is strongly connected: inside the class, every member is reached from its label and reaches it;
+      3. the classes are maximal: the graph between the classes (the condensation) has no cycle.
+    `labels` may be longer than the matrix (the drivers pad it): the extra vertices have empty rows."""
+    nr, nc = int(csr.num_rows), int(csr.num_cols)
+    lab = np.asarray(labels).astype(np.int64)
+    n = lab.shape[0]
+    if lab.ndim != 1 or n < max(nr, nc):
+        raise ValueError("validate_strong_components: %d labels for a %d x %d matrix" % (n, nr, nc))
+
+    def first(bad):
+        return int(np.flatnonzero(bad)[0])
+
+    v = np.arange(n, dtype=np.int64)
+    if np.any((lab < 0) | (lab > v)):
+        k = first((lab < 0) | (lab > v))
+        raise ValueError("validate_strong_components: vertex %d has label %d, which is above it (rule 1)" % (k, lab[k]))
+    if np.any(lab[lab] != lab):
+        k = first(lab[lab] != lab)
+        raise ValueError("validate_strong_components: vertex %d has label %d, whose own label is %d (rule 1)" % (k, lab[k], lab[lab[k]]))
+    src, dst = _edges_of_pattern(csr, n)
+    inside = lab[src] == lab[dst]
+    roots = lab == v
+    forward = _reach_inside(src[inside], dst[inside], roots, n)
+    if not forward.all():
+        k = first(~forward)
+        raise ValueError("validate_strong_components: vertex %d is not reached from its label %d inside its class (rule 2)" % (k, lab[k]))
+    backward = _reach_inside(dst[inside], src[inside], roots, n)
+    if not backward.all():
+        k = first(~backward)
+        raise ValueError("validate_strong_components: vertex %d does not reach its label %d inside its class (rule 2)" % (k, lab[k]))
+    # Kahn's peeling of the condensation, a whole layer of classes at a time: what cannot be peeled lies on a cycle of classes
+    a, b = lab[src[~inside]], lab[dst[~inside]]
+    left = roots.copy()
+    while a.size:
+        fed = np.zeros(n, dtype=bool)
+        fed[b] = True
+        peel = left & ~fed
+        if not peel.any():
+            k = first(left & fed)
+            raise ValueError("validate_strong_components: the class of label %d lies on a cycle of classes or behind one, so the classes "
+                             "on that cycle are no whole components (rule 3)" % k)
+        left &= ~peel
+        keep = ~peel[a]
+        a, b = a[keep], b[keep]
+    return int(np.count_nonzero(roots))
+
+
 class HipBackend:
     """Allocation / transfer hooks of the drivers.  The CPU tests substitute a stand-in with the
     same methods to exercise the distributed control flow over gloo."""
@@ -2167,6 +2243,107 @@ class LabelPropagation(_PatternApp):
         degree = np.bincount(ident, weights=self.degrees_.astype(np.float64), minlength=inside.shape[0])
         two_m = float(g.nnz)
         return float(np.sum(inside / two_m - (degree / two_m) ** 2))
+
+
+class StronglyConnectedComponents(_PatternApp):
+    """Strongly connected components: gl_scc, trimming and colour-and-collect passes over the pattern and its
+    transpose.  The matrix is read as a simple DIRECTED graph (io.simple_pattern: an edge u -> v for a stored non-zero A[v, u], u
+    != v; zero values, the diagonal and duplicates dropped, rows ascending); the transposed pattern lives in a second boolean
+    SpMVModule, out_, which exists only when the pattern is not symmetric.  run() labels every vertex with the smallest vertex
+    of its component, ConnectedComponents' convention: on a symmetric pattern the two agree to the bit."""
+    _no_shards_ = ("gl_scc reads the colour of every column of a row, in the pattern and in its transpose, so every rank would need "
+                   "both whole patterns")
+    ORDERS = ("natural", "random", "largest_first")
+    graph_ = graph_out_ = symmetric_ = degrees_ = labels_ = priorities_ = num_components_ = largest_component_ = None
+    component_labels_ = component_sizes_ = trimmed_ = passes_ = rounds_ = launches_ = is_dag_ = None
+
+    def __init__(self, num_channels=M.num_hbm_channels, spmv_out_buf_len=0, vec_buf_len=0, comm=None, backend=None):
+        _PatternApp.__init__(self, num_channels, spmv_out_buf_len, vec_buf_len, comm, backend)
+        self.buf_lens_ = (spmv_out_buf_len, vec_buf_len)
+        self.out_ = None                 # the transposed pattern's module (a pattern that is not symmetric)
+
+    def _prepare(self, csr):
+        self.graph_, self.graph_out_, self.symmetric_ = io.simple_pattern(csr)      # (after padding: padding vertices have empty rows)
+        n = self.graph_.num_rows
+        self.degrees_ = (np.diff(self.graph_.adj_indptr.astype(np.int64))
+                         + np.bincount(self.graph_.adj_indices, minlength=n)).astype(np.uint32)      # in-degree + out-degree
+        self.labels_ = None
+        return self.graph_
+
+    def load_and_format_matrix(self, csr_float_npz_path, skip_empty_rows=True):
+        _PatternApp.load_and_format_matrix(self, csr_float_npz_path, skip_empty_rows)
+        self.modules_ = [self.SpMV_]
+        self.out_ = None
+        if not self.symmetric_:
+            self.out_ = self.backend.SpMVModule(self.num_channels_, *self.buf_lens_)
+            self.out_.set_semiring(M.LogicalSemiring)
+            self.out_.set_mask_type(M.kNoMask)
+            self.out_.blocking = False
+            self.out_.load_and_format_matrix(self.graph_out_, skip_empty_rows)
+            self.add_module(self.out_)
+
+    def send_matrix_host_to_device(self):
+        _PatternApp.send_matrix_host_to_device(self)
+        if self.out_ is not None:
+            self.out_.send_matrix_host_to_device()
+
+    def run(self, order="largest_first", seed=0, priorities=None):
+        """-> uint32[n_]: labels[v] = the smallest vertex u such that v reaches u and u reaches v (padding vertices are
+        singletons).  The priorities decide which component every pass removes -- its best-keyed live vertex's, larger priority
+        first, ties to the smaller vertex -- and never the labels: io.coloring_priorities(degrees_, order, seed) for "natural",
+        "random" or "largest_first" (degrees_ = in-degree + out-degree: hubs first normally collects the giant component in
+        pass 1), or an explicit `priorities` array of n_real_ or n_ words, which overrides `order`.  Leaves labels_, priorities_
+        (uint32[n_], the array the run used; None for natural), trimmed_, passes_, rounds_, launches_ and, over the n_real_ real
+        vertices, num_components_, largest_component_, component_labels_ (ascending), component_sizes_ (aligned with them) and
+        is_dag_ (every component is a single vertex).  The call waits for the device."""
+        self._require_sent()
+        B, n = self.backend, self.n_
+        if priorities is not None:
+            prio = np.asarray(priorities)
+            if prio.ndim != 1 or prio.shape[0] not in (self.n_real_, n):
+                raise ValueError("StronglyConnectedComponents.run(): priorities of shape %s, expected %d or %d words"
+                                 % (prio.shape, self.n_real_, n))
+            prio = np.concatenate([prio.astype(np.uint32), np.zeros(n - prio.shape[0], dtype=np.uint32)])
+        elif order in self.ORDERS:
+            prio = io.coloring_priorities(self.degrees_, order, seed)
+        else:
+            raise ValueError("StronglyConnectedComponents.run(): order %r is none of %s" % (order, ", ".join(self.ORDERS)))
+        out = B.alloc(2 * n if prio is not None else n, np.float32)  # (32-bit words: the labels, then the priorities)
+        if prio is not None:
+            B.upload(B.view(out, n, n, 4), prio)
+        stats = self.SpMV_.scc(self.out_, B.view(out, 0, n, 4), B.view(out, n, n, 4) if prio is not None else None)
+        B.sync()
+        self.labels_ = B.download(out, np.uint32, n)
+        self.priorities_ = prio
+        components, self.passes_, self.trimmed_, self.rounds_, self.launches_ = stats
+        if self.graph_.nnz:
+            self.trimmed_ -= n - self.n_real_                        # (every padding vertex was trimmed; without entries nothing runs)
+        self.num_components_ = components - (n - self.n_real_)
+        self.component_labels_, sizes = np.unique(self.labels_[:self.n_real_], return_counts=True)
+        self.component_sizes_ = sizes.astype(np.int64)
+        self.largest_component_ = int(sizes.max()) if sizes.size else 0
+        self.is_dag_ = self.largest_component_ <= 1
+        return self.labels_
+
+    def condensation(self):
+        """-> (CSRMatrix, rank_of_label): the graph between the components of the last run, on the host (numpy).  The
+        components of the real vertices are ranked by ascending label, rank_of_label[l] = the rank of the component labelled l
+        (uint32[n_real_], 0xffffffff where l is no label); the matrix is num_components_ x num_components_ and, as everywhere
+        here, an entry A[b, a] = 1 is an edge a -> b: some u in component a has an edge to some v in component b != a.  It is
+        the simple pattern of a DAG: rows ascending, no diagonal, no duplicates."""
+        if self.labels_ is None:
+            raise RuntimeError("StronglyConnectedComponents.condensation(): run() first")
+        nr, k = self.n_real_, int(self.num_components_)
+        rank = np.full(nr, 0xFFFFFFFF, dtype=np.uint32)
+        rank[self.component_labels_.astype(np.int64)] = np.arange(k, dtype=np.uint32)
+        src, dst = _edges_of_pattern(self.graph_, nr)
+        lab = self.labels_.astype(np.int64)
+        a, b = rank[lab[src]].astype(np.int64), rank[lab[dst]].astype(np.int64)
+        key = np.unique(b[a != b] * k + a[a != b])
+        indptr = np.zeros(k + 1, dtype=np.int64)
+        np.cumsum(np.bincount(key // max(k, 1), minlength=k), out=indptr[1:])
+        dag = io.CSRMatrix(k, k, np.ones(key.shape[0], dtype=np.float32), (key % max(k, 1)).astype(np.uint32), indptr.astype(np.uint32))
+        return dag, rank
 
 
 class BetweennessCentrality(_PatternApp):

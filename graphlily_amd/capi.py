@@ -57,7 +57,8 @@ EXT_EXPORTS = ["gl_color"]
 # ... and one header per extension since (EXT_EXPORTS is pinned as well by now): header under include/ -> the symbols it declares;
 # tests check their own entry, build() checks every list against the library
 EXT_HEADERS = {"graphlily_hip_ext.h": EXT_EXPORTS, "graphlily_hip_truss.h": ["gl_truss"], "graphlily_hip_msf.h": ["gl_msf"],
-               "graphlily_hip_match.h": ["gl_match"], "graphlily_hip_lpa.h": ["gl_lpa"]}
+               "graphlily_hip_match.h": ["gl_match"], "graphlily_hip_lpa.h": ["gl_lpa"],
+               "graphlily_hip_scc.h": ["gl_scc"]}
 
 
 class GraphLilyError(RuntimeError):
@@ -129,6 +130,7 @@ def lib():
         "gl_msf": [vp, vp, vp, vp, P(u64)],
         "gl_match": [vp, vp, vp, P(u64)],
         "gl_lpa": [vp, vp, vp, vp, u32, P(u64)],
+        "gl_scc": [vp, vp, vp, vp, P(u64)],
         "gl_bc_accumulate": [vp, vp, vp, vp, ctypes.c_double, i32, vp, P(u32)],
         "gl_spmv_run": [vp, vp, vp, vp, i32, f32, i32],
         "gl_prof_begin": [u32, u32], "gl_prof_end": [P(ctypes.c_double), P(u32)], "gl_span_begin": [], "gl_span_end": [P(ctypes.c_double)],
@@ -547,6 +549,21 @@ class SpMVPlan:
         garbage = 0xdeadbeefdeadbeef
         stats = (ctypes.c_uint64 * 5)(*([garbage] * 5))
         check(lib().gl_lpa(ctypes.c_void_p(self.handle), _p(color), _p(init), _p(label), ctypes.c_uint32(max_sweeps), stats))
+        return tuple(int(x) for x in stats)
+
+    def scc(self, plan_out, label, prio=None):
+        """gl_scc with this plan as plan_in (row v: the predecessors of v) and `plan_out` as the transposed pattern's plan (None,
+        or this plan: the pattern is symmetric): the strongly connected components of the directed graph into `label`
+        (num_rows device words) -- label[v] = the smallest vertex that v reaches and that reaches v, cc_labels' convention --
+        -> (components, passes, trimmed, rounds, launches enqueued).  `prio` (num_rows device words, or None: all equal; larger
+        first, ties to the smaller vertex, gl_color's order) decides which component every pass removes, never the labels;
+        components, passes and trimmed are properties of (graph, prio), rounds depends on the hardware's schedule.  Both plans
+        are square, whole, their rows strictly ascending sets (io.simple_pattern prepares them).  `label` is fully written by
+        the call, which SYNCHRONISES (it reads a control record back between batches of launches)."""
+        out = self if plan_out is None else plan_out
+        garbage = 0xdeadbeefdeadbeef
+        stats = (ctypes.c_uint64 * 5)(*([garbage] * 5))
+        check(lib().gl_scc(ctypes.c_void_p(self.handle), ctypes.c_void_p(out.handle), _p(prio), _p(label), stats))
         return tuple(int(x) for x in stats)
 
     def bc_accumulate(self, plan_out, level, bc, scale=1.0, accumulate=False, sigma=None, stats=True):

@@ -233,28 +233,11 @@ __global__ __launch_bounds__(256) void bc_sweep_kernel(BcSweepArgs a) {
     }
 }
 
-// the refusals, the verdicts and plan_in's scratch, on first use
+// the refusals and the verdicts (gl_rows.h: rows_require_pair, shared with gl_scc), then plan_in's scratch, on first use
 static int bc_prepare(gl_spmv_plan pin, gl_spmv_plan pout, const char *who) {
-    const char *hint = "io.simple_pattern";
-    int rc = rows_require(pin, pout == pin ? kRowsSymmetric : kRowsSets, who, "plan_in", hint);
-    if (rc == GL_OK && pout != pin) rc = rows_require(pout, kRowsSets, who, "plan_out", hint);
+    const int rc = rows_require_pair(pin, pout, who, "io.simple_pattern");
     if (rc != GL_OK) return rc;
-    if (pout->num_rows != pin->num_rows)
-        return set_error(GL_ERR_UNSUPPORTED, "%s: plan_out is not the transpose of plan_in: %u and %u vertices", who, pout->num_rows, pin->num_rows);
-    rc = plan_scratch(pin->d_bc_scratch, bc_scratch_bytes(pin->num_rows), who, "queue, offsets, sigma and coef");
-    if (rc != GL_OK || pout == pin) return rc;
-    if (pin->bc_partner != pout || pin->bc_partner_uid != pout->uid) {
-        // every entry (v, u) of plan_in is an entry (u, v) of plan_out, and there are as many: the rows are sets, so that is a bijection
-        bool ok = pin->nnz == pout->nnz;
-        if (ok && pin->nnz != 0 && (rc = rows_check_transpose(pin, pout, &ok)) != GL_OK) return rc;
-        pin->bc_partner = pout;
-        pin->bc_partner_uid = pout->uid;
-        pin->bc_transpose_ok = ok ? 1 : 0;
-    }
-    if (pin->bc_transpose_ok == 0)
-        return set_error(GL_ERR_UNSUPPORTED, "%s: plan_out is not the transpose of plan_in (%llu and %llu entries; an entry (v, u) of plan_in "
-                         "needs (u, v) in plan_out): io.simple_pattern prepares both", who, (unsigned long long)pout->nnz, (unsigned long long)pin->nnz);
-    return GL_OK;
+    return plan_scratch(pin->d_bc_scratch, bc_scratch_bytes(pin->num_rows), who, "queue, offsets, sigma and coef");
 }
 
 static int bc_accumulate(gl_spmv_plan pin, gl_spmv_plan pout, const float *d_level, double *d_bc, double scale, int accumulate,

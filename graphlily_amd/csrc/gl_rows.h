@@ -1,8 +1,8 @@
 // The plain CSR row copy that a GL_PLAN_BOOLEAN plan keeps (gl_spmv_plan.h: d_csr_indptr / d_csr_indices / csr_nz_base), as the
 // graph kernels that walk it see it -- gl_bfs_parents, gl_cc, gl_tc, gl_kcore, gl_color, gl_truss, gl_msf and gl_match (which also take a
-// value per entry of the copy from their caller), gl_lpa, gl_bc: what a caller may require of it, the
+// value per entry of the copy from their caller), gl_lpa, gl_bc, gl_scc: what a caller may require of it, the
 // verdicts about it that the plan caches, the few helpers every such kernel wants, and the walk over a row -- a thread per row,
-// then the wavefront -- that six of them run (rows_walk_*, at the end).  gl_rows.hip holds the check kernels.
+// then the wavefront -- that seven of them run (rows_walk_*, at the end).  gl_rows.hip holds the check kernels.
 // gl_rounds.h, on top of this, holds what the kernels that run in rounds over a queue share: the atomics of their memory rule,
 // the queue append, the peel record and the gated host loop.
 #ifndef GL_ROWS_H_
@@ -39,6 +39,12 @@ int rows_check_sorted(gl_spmv_plan p);
 // is (u, v) stored in `partner` for every entry (v, u) of p?  Both plans passed kRowsSets and have entries and as many rows.
 // partner == p asks whether the pattern is symmetric (diagonal entries are then not looked up): kRowsSymmetric's verdict.
 int rows_check_transpose(gl_spmv_plan p, gl_spmv_plan partner, bool *ok);
+// The refusals of the calls that take a pattern as TWO plans, plan_in (row v: the vertices v is pulled from) and plan_out (the
+// transposed pattern; plan_out == plan_in declares the pattern symmetric) -- gl_bc_accumulate, gl_scc -- in this order:
+// rows_require(plan_in, kRowsSymmetric if the two are one plan, else kRowsSets), rows_require(plan_out, kRowsSets), as many
+// vertices, and plan_out IS the transpose: as many entries and rows_check_transpose, whose verdict plan_in caches for the last
+// partner (by handle and uid).  All GL_ERR_UNSUPPORTED.
+int rows_require_pair(gl_spmv_plan pin, gl_spmv_plan pout, const char *who, const char *hint);
 
 // the grid of a streaming pass, a thread per vertex
 inline unsigned rows_stream_grid(uint32_t n) { return std::max(1u, std::min<unsigned>(cdiv(n, 256u), (unsigned)ctx().num_cus * 8u)); }
@@ -76,8 +82,8 @@ __device__ __forceinline__ uint32_t rows_lower_bound(P s, uint32_t n, uint32_t w
     return lo;
 }
 
-// THE WALK over the entries [beg, end) of one row per lane, 64 rows per wavefront (gl_bfs_parents, gl_cc, gl_kcore, gl_msf, gl_match and
-// gl_color run it; DESIGN.md 4.13.  bc_sweep_kernel of gl_bc keeps a copy of its own, in the same forms: through these templates
+// THE WALK over the entries [beg, end) of one row per lane, 64 rows per wavefront (gl_bfs_parents, gl_cc, gl_kcore, gl_msf, gl_match,
+// gl_color and gl_scc run it; DESIGN.md 4.13.  bc_sweep_kernel of gl_bc keeps a copy of its own, in the same forms: through these templates
 // its accumulate figure on one stand-in was 1 - 2 % above the parent's worse run in two visits, EXPERIMENTS.md Round 21):
 //   rows_walk_thread    a thread per row, four entries per step, for at most cut_steps steps while any lane of the wavefront has
 //                       entries left: body(c, beg) gets the columns of the entries beg .. beg + 3 and returns true when the row

@@ -174,6 +174,27 @@ int rows_require(gl_spmv_plan p, unsigned need, const char *who, const char *whi
     return GL_OK;
 }
 
+int rows_require_pair(gl_spmv_plan pin, gl_spmv_plan pout, const char *who, const char *hint) {
+    int rc = rows_require(pin, pout == pin ? kRowsSymmetric : kRowsSets, who, "plan_in", hint);
+    if (rc == GL_OK && pout != pin) rc = rows_require(pout, kRowsSets, who, "plan_out", hint);
+    if (rc != GL_OK) return rc;
+    if (pout->num_rows != pin->num_rows)
+        return set_error(GL_ERR_UNSUPPORTED, "%s: plan_out is not the transpose of plan_in: %u and %u vertices", who, pout->num_rows, pin->num_rows);
+    if (pout == pin) return GL_OK;
+    if (pin->bc_partner != pout || pin->bc_partner_uid != pout->uid) {
+        // every entry (v, u) of plan_in is an entry (u, v) of plan_out, and there are as many: the rows are sets, so that is a bijection
+        bool ok = pin->nnz == pout->nnz;
+        if (ok && pin->nnz != 0 && (rc = rows_check_transpose(pin, pout, &ok)) != GL_OK) return rc;
+        pin->bc_partner = pout;
+        pin->bc_partner_uid = pout->uid;
+        pin->bc_transpose_ok = ok ? 1 : 0;
+    }
+    if (pin->bc_transpose_ok == 0)
+        return set_error(GL_ERR_UNSUPPORTED, "%s: plan_out is not the transpose of plan_in (%llu and %llu entries; an entry (v, u) of plan_in "
+                         "needs (u, v) in plan_out): %s prepares both", who, (unsigned long long)pout->nnz, (unsigned long long)pin->nnz, hint);
+    return GL_OK;
+}
+
 }  // namespace gl
 
 int gl_spmv_plan_rows_sorted(gl_spmv_plan plan, int *sorted) {

@@ -270,10 +270,13 @@ struct gl_spmv_plan_s {
     // gl_lpa (gl_lpa.hip): the pass's scratch, allocated by the first call -- 256 bytes of control record, then five arrays of
     // num_rows words (two flag arrays, the second label buffer, the class list, the colour histogram) and num_rows + 1 class offsets
     unsigned char *d_lpa_scratch = nullptr;
+    // gl_scc (gl_scc.hip), as plan_in: the pass's scratch, allocated by the first call -- 256 bytes of control record, num_rows
+    // 64-bit colour words, then four arrays of num_rows words: the marks, the components' minima and the two lists of live vertices
+    unsigned char *d_scc_scratch = nullptr;
     // gl_bc_accumulate (gl_bc.hip), as plan_in, set up by the first call: the pass's scratch -- 256 bytes of control words, two
     // arrays of num_rows + 2 level offsets, num_rows words of queue, num_rows doubles each of sigma and coef -- the page-locked
     // room the offsets are read back to, and the verdict on the last plan_out that was not this plan itself: is it the
-    // transpose?  (the partner is remembered by handle AND uid: a later plan may be allocated where a destroyed one was;
+    // transpose?  (gl_rows.h: rows_require_pair, which gl_scc asks as well; the partner is remembered by handle AND uid: a later plan may be allocated where a destroyed one was;
     // plan_out == plan_in asks for rows_symmetric above)
     uint64_t uid = gl::plan_uid();
     unsigned char *d_bc_scratch = nullptr;

@@ -363,6 +363,20 @@ class SpMVModule(BaseModule):
         self._finish(label_buf)
         return stats
 
+    def scc(self, out_module, label_buf, prio_buf=None):
+        """Extension (gl_scc): the strongly connected components of this module's matrix, read as a directed graph -- row v: the
+        predecessors of v, `out_module` (None: the pattern is symmetric) holds the transposed pattern -- into `label_buf`
+        (get_num_rows() words: the smallest vertex of every vertex's component) -> (components, passes, trimmed, rounds,
+        launches).  `prio_buf` (as many words, larger first, ties by vertex number; None: all equal) decides which component a
+        pass removes, never the labels.  The call synchronises.  Raises GraphLilyError (GL_ERR_UNSUPPORTED) when a plan keeps no
+        row copy (only the (||,&&) layout does), is not square, is a row shard, its rows are no strictly ascending sets, or the
+        two are not each other's transpose (io.simple_pattern prepares them)."""
+        if self.plan_ is None or (out_module is not None and out_module.plan_ is None):
+            _fatal("SpMVModule.scc: send_matrix_host_to_device first")
+        stats = self.plan_.scc(None if out_module is None else out_module.plan_, label_buf, prio_buf)
+        self._finish(label_buf)
+        return stats
+
     def bc_accumulate(self, out_module, level_buf, bc_buf, scale=1.0, accumulate=False, sigma_buf=None, stats=True):
         """Extension (gl_bc_accumulate): adds scale x Brandes' dependency of the search whose levels are in `level_buf`
         (get_num_rows() floats) to `bc_buf` (as many doubles; accumulate=False: overwrites it).  This module's matrix is the

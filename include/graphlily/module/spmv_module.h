@@ -15,6 +15,7 @@
 #include "graphlily_hip_msf.h"
 #include "graphlily_hip_match.h"
 #include "graphlily_hip_lpa.h"
+#include "graphlily_hip_scc.h"
 #include "graphlily/io/data_formatter.h"
 #include "graphlily/io/data_loader.h"
 #include "graphlily/module/base_module.h"
@@ -256,6 +257,17 @@ public:
              uint64_t *stats = nullptr) {
         barrier_();
         GRAPHLILY_CHECK(gl_lpa(plan_, color, init, (uint32_t *)label.ptr(), max_sweeps, stats));
+        finish_();
+    }
+    // extension (gl_scc, graphlily_hip_scc.h): the strongly connected components of this module's matrix, read as a directed graph
+    // -- row v: the predecessors of v; `out` holds the transposed pattern (nullptr: the pattern is symmetric); both in the (||,&&)
+    // layout, rows strictly ascending (graphlily::io::util_simple_pattern prepares them) -- into `label` (get_num_rows() device
+    // words: the smallest vertex of every vertex's component).  `prio` (as many device words, larger first, ties to the smaller
+    // vertex number; nullptr: all equal) decides which component a pass removes, never the labels; stats (optional, 5 host
+    // words) receives {components, passes, trimmed, rounds, launches}.  The call synchronises.
+    void scc(SpMVModule *out, DeviceBuffer label, const uint32_t *prio = nullptr, uint64_t *stats = nullptr) {
+        barrier_();
+        GRAPHLILY_CHECK(gl_scc(plan_, out ? out->plan_ : plan_, prio, (uint32_t *)label.ptr(), stats));
         finish_();
     }
     // extension (gl_bc_accumulate): adds scale x Brandes' dependency of the search whose levels are in `level` (get_num_rows()
