@@ -20,6 +20,7 @@ Differences that do not change results:
 """
 import collections
 import functools
+import math
 import os
 import time
 
@@ -874,6 +875,222 @@ def validate_communities(csr, labels, colors=None, initial=None, max_sweeps=None
             x = first(cur < best)
             raise ValueError("validate_communities: %d neighbours of vertex %d carry its label %d and %d carry another one: not a fixed "
                              "point (rule 3)" % (cur[x], x, got[x], best[x]))
+    return int(np.unique(got).shape[0])
+
+
+def _modularity_of(graph, degrees, labels):
+    """-> float: Newman's modularity sum_c e_c / m - (d_c / 2 m)^2 of `labels` (one per vertex) on the symmetric simple graph
+    `graph` with the degrees `degrees`, on the host in f64: e_c = edges inside community c, d_c = the degrees of its vertices,
+    m = edges (0.0 for a graph without edges).  LabelPropagation.modularity and Louvain.modularity."""
+    g = graph
+    if g.nnz == 0:
+        return 0.0
+    _, ident = np.unique(labels, return_inverse=True)
+    rows = np.repeat(np.arange(g.num_rows, dtype=np.int64), np.diff(g.adj_indptr.astype(np.int64)))
+    inside = np.bincount(ident[rows][ident[rows] == ident[g.adj_indices.astype(np.int64)]], minlength=int(ident.max()) + 1)   # (twice e_c)
+    degree = np.bincount(ident, weights=np.asarray(degrees).astype(np.float64), minlength=inside.shape[0])
+    two_m = float(g.nnz)
+    return float(np.sum(inside / two_m - (degree / two_m) ** 2))
+
+
+def _louvain_entries(sym, weights):
+    """-> (rows, cols, w) as int64 over the off-diagonal entries of `sym`; weights None: all 1"""
+    n = sym.num_rows
+    rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(sym.adj_indptr.astype(np.int64)))
+    cols = sym.adj_indices.astype(np.int64)
+    w = np.ones(cols.shape[0], dtype=np.int64) if weights is None else np.asarray(weights).astype(np.int64)
+    off = rows != cols
+    return rows[off], cols[off], w[off]
+
+
+def _louvain_move_loop(sym, weights, vertex_weights, colors, max_sweeps, min_gain):
+    """gl_louvain_move restated on the host -> (labels, sweeps, moves, evaluations, stop reason, q_first, q_last): class by
+    class, every vertex of a class decides from the labels and tot as they stand when the class begins, in numpy over the
+    class's entries (one np.unique per class: kept apart from the device's tables and from the suite's dictionary loop;
+    validate_louvain checks one with the other).  int64 throughout: two_m < 2^31 keeps every product below 2^62."""
+    n = sym.num_rows
+    rows, cols, w = _louvain_entries(sym, weights)
+    if vertex_weights is None:
+        k = np.zeros(n, dtype=np.int64)
+        np.add.at(k, rows, w)
+    else:
+        k = np.asarray(vertex_weights).astype(np.int64)
+    two_m = int(k.sum())
+    if two_m >= 1 << 31:
+        raise ValueError("_louvain_move_loop: two_m = %d >= 2^31" % two_m)
+    label = np.arange(n, dtype=np.int64)
+    tot = k.copy()
+    inner = int(k.sum()) - int(w.sum())
+
+    def q_of():
+        return two_m * (inner + int(w[label[rows] == label[cols]].sum())) - int((tot * tot).sum())
+
+    q_first = q_last = q_of()
+    if rows.shape[0] == 0:
+        return label.astype(np.uint32), 1, 0, 0, 1, 0, 0
+    col = np.asarray(colors).astype(np.int64)
+    by_class = np.argsort(col[rows], kind="stable")
+    bounds = np.searchsorted(col[rows][by_class], np.arange(int(col.max()) + 2))
+    linked = int(np.unique(rows).shape[0])
+    sweeps = moves = evaluations = reason = 0
+    while True:
+        sweeps += 1
+        moved = 0
+        evaluations += linked
+        for c in range(bounds.shape[0] - 1):
+            e = by_class[bounds[c]:bounds[c + 1]]
+            if e.shape[0] == 0:
+                continue
+            r, lab, ww = rows[e], label[cols[e]], w[e]
+            key, inverse = np.unique(r * n + lab, return_inverse=True)
+            kin = np.zeros(key.shape[0], dtype=np.int64)
+            np.add.at(kin, inverse.reshape(-1), ww)
+            kr, kl = key // n, key % n
+            own = kl == label[kr]
+            vs, at = np.unique(kr, return_inverse=True)                # the class's vertices only: cur of each, then per key
+            at = at.reshape(-1)
+            cur = -k[vs] * (tot[label[vs]] - k[vs])
+            cur[at[own]] += two_m * kin[own]
+            kr, kl, score, cur = kr[~own], kl[~own], (two_m * kin - k[kr] * tot[kl])[~own], cur[at][~own]
+            first = np.lexsort((kl, -score, kr))                       # per vertex: the largest score, then the smallest label
+            kr, kl, score, cur = kr[first], kl[first], score[first], cur[first]
+            head = np.ones(kr.shape[0], dtype=bool)
+            head[1:] = kr[1:] != kr[:-1]
+            go = head & (score > cur)
+            v, to = kr[go], kl[go]
+            np.subtract.at(tot, label[v], k[v])
+            np.add.at(tot, to, k[v])
+            label[v] = to
+            moved += int(v.shape[0])
+        moves += moved
+        q_old, q_last = q_last, q_of()
+        if moved == 0:
+            reason = 1
+            break
+        if q_last - q_old <= min_gain:
+            reason = 2
+            break
+        if sweeps >= max_sweeps:
+            break
+    return label.astype(np.uint32), sweeps, moves, evaluations, reason, q_first, q_last
+
+
+def _greedy_coloring_of(sym, prio):
+    """-> uint32[n]: the first-fit greedy colouring in gl_color's order (larger priority first, ties to the smaller vertex
+    number; prio None: ascending vertex order), the sequential loop"""
+    n = sym.num_rows
+    indptr = sym.adj_indptr.astype(np.int64).tolist()
+    cols = sym.adj_indices.astype(np.int64).tolist()
+    order = range(n) if prio is None else np.lexsort((np.arange(n), -np.asarray(prio).astype(np.int64))).tolist()
+    color = [-1] * n
+    for v in order:
+        used = {color[u] for u in cols[indptr[v]:indptr[v + 1]] if u != v}
+        c = 0
+        while c in used:
+            c += 1
+        color[v] = c
+    return np.asarray(color, dtype=np.uint32)
+
+
+def _smallest_member_labels(community_of, n):
+    """-> uint32[n]: every vertex labelled with the smallest vertex of its community"""
+    community_of = np.asarray(community_of).astype(np.int64)
+    smallest = np.full(int(community_of.max()) + 1 if n else 0, n, dtype=np.int64)
+    np.minimum.at(smallest, community_of, np.arange(n, dtype=np.int64))
+    return smallest[community_of].astype(np.uint32)
+
+
+def _louvain_levels(sym, degrees, move, color, tol, max_sweeps, max_levels):
+    """Louvain's level loop, shared by the driver (move and color run on the device) and the host model (they run on the
+    host) -> a dict of the results.  move(level, graph, weights, k, colors, min_gain) -> (labels, sweeps, moves, evaluations,
+    launches-or-0, reason, q_first, q_last); color(level, graph, degrees) -> (colors, num_colors).  Level 0 is `sym` with every
+    weight 1 and k = degrees; a level is ACCEPTED iff it moved something and its q_last is strictly above the last accepted Q
+    (at the start: the singletons' Q); otherwise it is discarded and the run ends, as it does when a level merges nothing or
+    max_levels is reached."""
+    n = sym.num_rows
+    graph, weights, k = sym, None, np.asarray(degrees).astype(np.uint32)
+    community_of = np.arange(n, dtype=np.int64)
+    out = {"sizes": [], "colors": [], "sweeps": [], "moves": [], "q": [], "dendrogram": [], "colorings": [], "launches": 0, "levels": 0}
+    accepted = None
+    for level in range(max_levels):
+        deg = np.diff(graph.adj_indptr.astype(np.int64)).astype(np.uint32)
+        colors, num_colors = color(level, graph, deg)
+        two_m = int(k.astype(np.int64).sum())
+        min_gain = int(math.floor(tol * float(two_m * two_m)))
+        labels, sweeps, moves, _, launches, _, q_first, q_last = move(level, graph, weights, k, colors, min_gain)
+        out["sizes"].append(int(graph.num_rows))
+        out["colors"].append(int(num_colors))
+        out["colorings"].append(colors)
+        out["sweeps"].append(int(sweeps))
+        out["moves"].append(int(moves))
+        out["q"].append((int(q_first), int(q_last)))
+        out["launches"] += int(launches)
+        if accepted is None:
+            accepted = int(q_first)
+        if moves == 0 or int(q_last) <= accepted:
+            break
+        accepted = int(q_last)
+        smaller, weights, k, part = io.aggregate_communities(graph, weights, k, labels[:graph.num_rows])
+        community_of = part.astype(np.int64)[community_of]
+        out["dendrogram"].append(community_of.astype(np.uint32))
+        out["levels"] += 1
+        if smaller.num_rows == graph.num_rows:
+            break
+        graph = smaller
+    out["labels"] = _smallest_member_labels(community_of, n)
+    return out
+
+
+def _louvain_host(sym, degrees, tol, max_sweeps, max_levels, order, seed, colorings=None):
+    """the level loop with the host move loop and the host greedy colouring (colorings: one array per level overrides it)"""
+    def color(level, graph, deg):
+        if colorings is not None and level < len(colorings):
+            c = np.asarray(colorings[level]).astype(np.uint32)[:graph.num_rows]
+        else:
+            if order == "smallest_last":
+                raise ValueError("_louvain_host: the peeling order of \"smallest_last\" is not unique: pass the colourings the run used")
+            c = _greedy_coloring_of(graph, io.coloring_priorities(deg, order, seed))
+        return c, (int(c.max()) + 1 if c.shape[0] else 0)
+
+    def move(level, graph, weights, k, colors, min_gain):
+        lab, sweeps, moves, evals, reason, q0, q1 = _louvain_move_loop(graph, weights, k, colors, max_sweeps, min_gain)
+        return lab, sweeps, moves, evals, 0, reason, q0, q1
+    return _louvain_levels(sym, degrees, move, color, tol, max_sweeps, max_levels)
+
+
+def validate_louvain(csr, labels, tol=1e-7, max_sweeps=100, max_levels=32, order="largest_first", seed=0, colorings=None):
+    """Host-side check (numpy) that `labels` is what Louvain.run(tol, max_sweeps, max_levels, order, seed) leaves on the
+    undirected simple graph of `csr` -- as Louvain reads it: io.symmetrize_simple -- one word per vertex of that symmetric
+    matrix.  `colorings` (Louvain.level_colorings_: one colouring per level) replaces the host's greedy colourings; the
+    "smallest_last" order needs them, because gl_kcore's peeling order is not unique.  Raises ValueError naming the first
+    offending vertex and the rule; returns the number of communities.
+      1. every vertex carries the smallest vertex number of its community: labels[v] <= v and labels[labels[v]] == labels[v];
+      2. a vertex without a neighbour carries its own number;
+      3. the labels equal, vertex for vertex, what the host model of the level loop leaves (_louvain_host)."""
+    sym, deg = io.symmetrize_simple(csr)
+    n = sym.num_rows
+    got = np.asarray(labels)
+    if got.ndim != 1 or got.shape[0] != n:
+        raise ValueError("validate_louvain: %d labels for the %d vertices of the symmetric matrix" % (got.shape[0] if got.ndim == 1 else -1, n))
+    got = got.astype(np.int64)
+    own = np.arange(n, dtype=np.int64)
+
+    def first(bad):
+        return int(np.flatnonzero(bad)[0])
+
+    bad = (got > own) | (got < 0)
+    bad |= got[np.minimum(np.maximum(got, 0), n - 1)] != got
+    if np.any(bad):
+        x = first(bad)
+        raise ValueError("validate_louvain: vertex %d carries %d, which is not the smallest vertex of a community (rule 1)" % (x, got[x]))
+    alone = (deg == 0) & (got != own)
+    if np.any(alone):
+        x = first(alone)
+        raise ValueError("validate_louvain: vertex %d has no neighbour and carries %d, not its own number (rule 2)" % (x, got[x]))
+    want = _louvain_host(sym, deg, tol, max_sweeps, max_levels, order, seed, colorings)["labels"].astype(np.int64)
+    if np.any(want != got):
+        x = first(want != got)
+        raise ValueError("validate_louvain: vertex %d carries %d, and the host model of the level loop leaves it %d (rule 3)" % (x, got[x], want[x]))
     return int(np.unique(got).shape[0])
 
 
@@ -2234,15 +2451,126 @@ class LabelPropagation(_PatternApp):
         lab = self.labels_ if labels is None else np.asarray(labels)
         if lab is None:
             raise RuntimeError("LabelPropagation.modularity(): run() first")
-        g = self.graph_
-        if g.nnz == 0:
-            return 0.0
-        _, ident = np.unique(lab, return_inverse=True)
-        rows = np.repeat(np.arange(g.num_rows, dtype=np.int64), np.diff(g.adj_indptr.astype(np.int64)))
-        inside = np.bincount(ident[rows][ident[rows] == ident[g.adj_indices.astype(np.int64)]], minlength=int(ident.max()) + 1)   # (twice e_c)
-        degree = np.bincount(ident, weights=self.degrees_.astype(np.float64), minlength=inside.shape[0])
-        two_m = float(g.nnz)
-        return float(np.sum(inside / two_m - (degree / two_m) ** 2))
+        return _modularity_of(self.graph_, self.degrees_, lab)
+
+
+class Louvain(_PatternApp):
+    """Louvain communities: gl_louvain_move, Blondel et al.'s modularity optimisation with the local moving
+    swept colour class by colour class (Lu, Halappanavar & Kalyanaraman).  The matrix is read as an undirected simple graph --
+    duplicates, the diagonal, zero-valued entries and direction are ignored, as in LabelPropagation -- and stored in both
+    directions by the host (io.symmetrize_simple); input edge weights are not read: level 0 has every weight 1 and k = the
+    degrees.  Every level moves vertices on the device until a sweep gains no more than tol, then the host aggregates the
+    communities into the next level's weighted graph (io.aggregate_communities).  Integer arithmetic throughout: the result is
+    a pure function of (graph, colourings, tol, max_sweeps, max_levels), to the bit."""
+    _no_shards_ = ("gl_louvain_move reads the label of every column of a row and the total of every neighbouring community, so "
+                   "every rank would need every label and the whole tot array")
+    degrees_ = graph_ = labels_ = levels_ = level_sizes_ = level_colors_ = level_sweeps_ = level_moves_ = level_q_ = launches_ = None
+    num_communities_ = community_labels_ = community_sizes_ = dendrogram_ = level_colorings_ = timings_ = None
+
+    def _prepare(self, csr):
+        self.graph_, self.degrees_ = io.symmetrize_simple(csr)
+        self.labels_ = None
+        return self.graph_
+
+    def run(self, tol=1e-7, max_sweeps=100, max_levels=32, order="largest_first", seed=0):
+        """-> uint32[n_]: labels[v] = the SMALLEST original vertex of v's community (ConnectedComponents' convention; isolated
+        and padding vertices keep their own numbers).  Level 0 runs on this driver's own module, every later level on a fresh
+        SpMVModule plan of the aggregated pattern; each level is coloured by SpMV.color under io.coloring_priorities(that
+        level's pattern degrees, order, seed) ("smallest_last" first runs gl_kcore on the level's plan) and moved by
+        gl_louvain_move with min_gain = floor(tol * two_m^2).  A level is ACCEPTED iff it moved something and its q_last is
+        strictly above the last accepted Q (at the start: the singletons' Q); otherwise it is discarded and the run ends, as it
+        does when a level merges nothing or max_levels is reached.  Leaves labels_, levels_ (accepted levels), and per level
+        RUN (a discarded last one included) level_sizes_ (vertices), level_colors_ (classes), level_sweeps_, level_moves_,
+        level_q_ (int64[runs, 2]: q_first and q_last, modularity x two_m^2), level_colorings_ (the colourings used);
+        launches_ (gl_louvain_move's alone), dendrogram_ (per accepted level, uint32[n_]: the community of every original
+        vertex), num_communities_, community_labels_ (ascending) and community_sizes_ over the real vertices, and timings_
+        (seconds: color, move, aggregate, plan).  The call waits for the device."""
+        self._require_sent()
+        B = self.backend
+        clock = {"color": 0.0, "move": 0.0, "aggregate": 0.0, "plan": 0.0}
+        live = {}
+
+        def module_of(level, graph):
+            if level == 0:
+                return self.SpMV_, graph.num_rows
+            if live.get("level") != level:
+                t0 = time.perf_counter()
+                padded = graph.copy()
+                self._pad(padded)
+                mod = self.backend.SpMVModule(self.num_channels_, 0, 0)
+                mod.set_semiring(self.semiring_)
+                mod.set_mask_type(M.kNoMask)
+                mod.load_and_format_matrix(padded, True)
+                mod.send_matrix_host_to_device()
+                live.update(level=level, module=mod, rows=padded.num_rows)
+                clock["plan"] += time.perf_counter() - t0
+            return live["module"], live["rows"]
+
+        def color(level, graph, deg):
+            mod, rows = module_of(level, graph)
+            t0 = time.perf_counter()
+            deg = np.concatenate([deg, np.zeros(rows - deg.shape[0], dtype=np.uint32)])
+            buf = B.alloc(2 * max(1, rows), np.float32)                 # (32-bit words: the colours, then the priorities)
+            if order == "smallest_last":
+                peel = B.alloc(2 * max(1, rows), np.float32)
+                mod.kcore(B.view(peel, 0, rows, 4), B.view(peel, rows, rows, 4))
+                B.sync()
+                prio = io.coloring_priorities(deg, order, seed, peel_order=B.download(peel, np.uint32, 2 * rows)[rows:])
+            else:
+                prio = io.coloring_priorities(deg, order, seed)
+            if prio is not None:
+                B.upload(B.view(buf, rows, rows, 4), prio)
+            num_colors = mod.color(B.view(buf, 0, rows, 4), B.view(buf, rows, rows, 4) if prio is not None else None)[0]
+            B.sync()
+            colors = B.download(buf, np.uint32, rows)
+            live["color_buf"] = buf
+            clock["color"] += time.perf_counter() - t0
+            return colors, num_colors
+
+        def move(level, graph, weights, k, colors, min_gain):
+            mod, rows = module_of(level, graph)
+            t0 = time.perf_counter()
+            nnz = graph.nnz
+            buf = B.alloc(2 * max(1, rows) + max(1, nnz), np.float32)   # (32-bit words: the labels, k, the entry weights)
+            label_buf, k_buf, w_buf = B.view(buf, 0, rows, 4), B.view(buf, rows, rows, 4), B.view(buf, 2 * rows, nnz, 4)
+            if level:
+                B.upload(k_buf, np.concatenate([k, np.zeros(rows - k.shape[0], dtype=np.uint32)]))
+                if nnz:
+                    B.upload(w_buf, weights)
+            stats = mod.louvain_move(label_buf, B.view(live["color_buf"], 0, rows, 4), w_buf if level and nnz else None,
+                                     k_buf if level else None, max_sweeps, min_gain)
+            B.sync()
+            labels = B.download(buf, np.uint32, rows)
+            clock["move"] += time.perf_counter() - t0
+            return (labels,) + tuple(stats)
+
+        t_all = time.perf_counter()
+        res = _louvain_levels(self.graph_, self.degrees_, move, color, tol, max_sweeps, max_levels)
+        clock["aggregate"] = time.perf_counter() - t_all - clock["color"] - clock["move"] - clock["plan"]
+        live.clear()
+        self.labels_ = res["labels"]
+        self.levels_ = res["levels"]
+        self.level_sizes_ = np.asarray(res["sizes"], dtype=np.int64)
+        self.level_colors_ = np.asarray(res["colors"], dtype=np.int64)
+        self.level_sweeps_ = np.asarray(res["sweeps"], dtype=np.int64)
+        self.level_moves_ = np.asarray(res["moves"], dtype=np.int64)
+        self.level_q_ = np.asarray(res["q"], dtype=np.int64).reshape(-1, 2)
+        self.level_colorings_ = res["colorings"]
+        self.launches_ = res["launches"]
+        self.dendrogram_ = res["dendrogram"]
+        self.timings_ = clock
+        self.community_labels_, sizes = np.unique(self.labels_[:self.n_real_], return_counts=True)
+        self.community_sizes_ = sizes.astype(np.int64)
+        self.num_communities_ = int(sizes.shape[0])
+        return self.labels_
+
+    def modularity(self, labels=None):
+        """-> float: Newman's modularity of the last run's labels (or of `labels`, n_ words) on graph_, on the host in f64
+        (_modularity_of, LabelPropagation.modularity's formula)"""
+        lab = self.labels_ if labels is None else np.asarray(labels)
+        if lab is None:
+            raise RuntimeError("Louvain.modularity(): run() first")
+        return _modularity_of(self.graph_, self.degrees_, lab)
 
 
 class StronglyConnectedComponents(_PatternApp):

@@ -58,7 +58,7 @@ EXT_EXPORTS = ["gl_color"]
 # tests check their own entry, build() checks every list against the library
 EXT_HEADERS = {"graphlily_hip_ext.h": EXT_EXPORTS, "graphlily_hip_truss.h": ["gl_truss"], "graphlily_hip_msf.h": ["gl_msf"],
                "graphlily_hip_match.h": ["gl_match"], "graphlily_hip_lpa.h": ["gl_lpa"],
-               "graphlily_hip_scc.h": ["gl_scc"]}
+               "graphlily_hip_scc.h": ["gl_scc"], "graphlily_hip_louvain.h": ["gl_louvain_move"]}
 
 
 class GraphLilyError(RuntimeError):
@@ -131,6 +131,7 @@ def lib():
         "gl_match": [vp, vp, vp, P(u64)],
         "gl_lpa": [vp, vp, vp, vp, u32, P(u64)],
         "gl_scc": [vp, vp, vp, vp, P(u64)],
+        "gl_louvain_move": [vp, vp, vp, vp, vp, u32, u64, P(u64)],
         "gl_bc_accumulate": [vp, vp, vp, vp, ctypes.c_double, i32, vp, P(u32)],
         "gl_spmv_run": [vp, vp, vp, vp, i32, f32, i32],
         "gl_prof_begin": [u32, u32], "gl_prof_end": [P(ctypes.c_double), P(u32)], "gl_span_begin": [], "gl_span_end": [P(ctypes.c_double)],
@@ -550,6 +551,28 @@ class SpMVPlan:
         stats = (ctypes.c_uint64 * 5)(*([garbage] * 5))
         check(lib().gl_lpa(ctypes.c_void_p(self.handle), _p(color), _p(init), _p(label), ctypes.c_uint32(max_sweeps), stats))
         return tuple(int(x) for x in stats)
+
+    def louvain_move(self, label, color, weight=None, vertex_weight=None, max_sweeps=100, min_gain=0):
+        """gl_louvain_move: one level of Louvain's local moving on this plan's graph into `label` (num_rows device words) ->
+        (sweeps, moves, evaluations, launches enqueued, stop reason, q_first, q_last), the two Q values as signed integers.
+        `weight` (nnz device words aligned with the row copy, each at least 1; None: every entry 1) are the entry weights -- the
+        same word in (v, u) and (u, v), which is NOT checked --, `vertex_weight` (num_rows device words; None: the sum of the
+        vertex's entry weights) the k[v], which may exceed that sum by the vertex's internal weight; their sum two_m must stay
+        below 2^31.  Every vertex starts in its own community; a sweep goes through the classes of `color` (num_rows device
+        words, a proper colouring with colours below num_rows, as gl_color gives); every vertex of a class decides from the
+        labels and community totals as they stand when the class begins: it moves to the smallest community of the largest
+        score two_m kin(c) - k[v] tot[c] iff that is strictly above two_m kin(own) - k[v] (tot[own] - k[v]).  After each sweep
+        Q = two_m In - sum tot^2 (modularity x two_m^2); the run stops after a sweep without a move (reason 1), one with
+        Q_new - Q_old <= min_gain (2), or sweep max_sweeps (0).  The plan is square, whole, its rows strictly ascending sets, its
+        pattern symmetric (io.symmetrize_simple prepares it).  `label` is fully written by the call, which SYNCHRONISES (it
+        reads a control record back between batches of launches).  A colour >= num_rows, a colouring that is not proper, a
+        zero weight and a vertex weight below its entries' sum raise GL_ERR_INVALID_ARG, two_m >= 2^31 GL_ERR_UNSUPPORTED."""
+        garbage = 0xdeadbeefdeadbeef
+        stats = (ctypes.c_uint64 * 7)(*([garbage] * 7))
+        check(lib().gl_louvain_move(ctypes.c_void_p(self.handle), _p(weight), _p(vertex_weight), _p(color), _p(label),
+                                    ctypes.c_uint32(max_sweeps), ctypes.c_uint64(min_gain), stats))
+        out = [int(x) for x in stats]
+        return tuple(out[:5] + [x - (1 << 64) if x >= (1 << 63) else x for x in out[5:]])
 
     def scc(self, plan_out, label, prio=None):
         """gl_scc with this plan as plan_in (row v: the predecessors of v) and `plan_out` as the transposed pattern's plan (None,

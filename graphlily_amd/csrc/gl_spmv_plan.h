@@ -270,6 +270,10 @@ struct gl_spmv_plan_s {
     // gl_lpa (gl_lpa.hip): the pass's scratch, allocated by the first call -- 256 bytes of control record, then five arrays of
     // num_rows words (two flag arrays, the second label buffer, the class list, the colour histogram) and num_rows + 1 class offsets
     unsigned char *d_lpa_scratch = nullptr;
+    // gl_louvain_move (gl_louvain.hip): the pass's scratch, allocated by the first call -- 256 bytes of control record, then four
+    // arrays of num_rows words (k, tot, the class list, the colour histogram), num_rows + 1 class offsets and 2 num_rows words of
+    // mover list
+    unsigned char *d_louvain_scratch = nullptr;
     // gl_scc (gl_scc.hip), as plan_in: the pass's scratch, allocated by the first call -- 256 bytes of control record, num_rows
     // 64-bit colour words, then four arrays of num_rows words: the marks, the components' minima and the two lists of live vertices
     unsigned char *d_scc_scratch = nullptr;

@@ -363,6 +363,23 @@ class SpMVModule(BaseModule):
         self._finish(label_buf)
         return stats
 
+    def louvain_move(self, label_buf, color_buf, weight_buf=None, vertex_weight_buf=None, max_sweeps=100, min_gain=0):
+        """Extension (gl_louvain_move): one level of Louvain's local moving on this module's matrix, read as a graph -- rows as
+        strictly ascending sets N(v), the pattern symmetric -- into `label_buf` (get_num_rows() words), swept colour class by
+        colour class under the proper colouring in `color_buf` (as many words; SpMVModule.color gives one), under the integer
+        entry weights in `weight_buf` (get_nnz() words aligned with the matrix's entries, each at least 1, both entries of an
+        edge the same; None: all 1) and the vertex weights in `vertex_weight_buf` (get_num_rows() words; None: the sums of the
+        entry weights) -> (sweeps, moves, evaluations, launches, stop reason, q_first, q_last).  The call synchronises.  Raises
+        GraphLilyError (GL_ERR_UNSUPPORTED) when the plan keeps no row copy (only the (||,&&) layout does), is not square, is a
+        row shard, its rows are no such sets, its pattern is not symmetric (io.symmetrize_simple prepares it) or the vertex
+        weights sum to 2^31 or more, and (GL_ERR_INVALID_ARG) for a colour >= get_num_rows(), a colouring that is not proper, a
+        zero weight or a vertex weight below its entries' sum."""
+        if self.plan_ is None:
+            _fatal("SpMVModule.louvain_move: send_matrix_host_to_device first")
+        stats = self.plan_.louvain_move(label_buf, color_buf, weight_buf, vertex_weight_buf, max_sweeps, min_gain)
+        self._finish(label_buf)
+        return stats
+
     def scc(self, out_module, label_buf, prio_buf=None):
         """Extension (gl_scc): the strongly connected components of this module's matrix, read as a directed graph -- row v: the
         predecessors of v, `out_module` (None: the pattern is symmetric) holds the transposed pattern -- into `label_buf`

@@ -225,6 +225,63 @@ inline std::vector<uint32_t> util_lpa_initial_labels(uint32_t n, uint32_t seed, 
     return out;
 }
 
+// The aggregation step of app::Louvain (an extension), io.aggregate_communities's words: `graph` is a symmetric matrix in
+// util_symmetrize_simple's layout (a diagonal entry is ignored), `weights` its integer entry weights (empty: all 1), `k` the vertex
+// weights and `labels` one community label per vertex.  The communities are numbered 0 .. count - 1 in ascending order of their
+// labels; community_of[v] is the number of v's.  The result has an entry (a, b), a != b, iff an entry joins a member of a to a
+// member of b; out_weights holds the SUM of those entries' weights, out_k[a] the sum of k[v] over the members of a (the weight
+// inside a community goes there only: the result has no diagonal).
+template <typename data_type>
+CSRMatrix<data_type> util_aggregate_communities(CSRMatrix<data_type> const &graph, std::vector<uint32_t> const &weights,
+                                                std::vector<uint32_t> const &k, std::vector<uint32_t> const &labels,
+                                                std::vector<uint32_t> &out_weights, std::vector<uint32_t> &out_k,
+                                                std::vector<uint32_t> &community_of) {
+    const size_t n = graph.num_rows;
+    std::vector<uint32_t> sorted(labels.begin(), labels.begin() + n);
+    std::sort(sorted.begin(), sorted.end());
+    sorted.erase(std::unique(sorted.begin(), sorted.end()), sorted.end());
+    const uint64_t count = sorted.size();
+    community_of.assign(n, 0);
+    std::vector<uint64_t> tot(count, 0);
+    for (size_t v = 0; v < n; v++) {
+        community_of[v] = (uint32_t)(std::lower_bound(sorted.begin(), sorted.end(), labels[v]) - sorted.begin());
+        tot[community_of[v]] += k[v];
+    }
+    std::vector<std::pair<uint64_t, uint64_t>> entry;     // (a * count + b, weight)
+    for (size_t v = 0; v < n; v++)
+        for (uint32_t j = graph.adj_indptr[v]; j < graph.adj_indptr[v + 1]; j++) {
+            const uint32_t u = graph.adj_indices[j];
+            if (u == v || community_of[u] == community_of[v]) continue;
+            entry.push_back(std::make_pair(community_of[v] * count + community_of[u], (uint64_t)(weights.empty() ? 1u : weights[j])));
+        }
+    std::sort(entry.begin(), entry.end());
+    CSRMatrix<data_type> out;
+    out.num_rows = out.num_cols = (uint32_t)count;
+    out.adj_indptr.assign(count + 1, 0);
+    out_weights.clear();
+    out_k.assign(count, 0);
+    std::vector<uint64_t> sums;
+    for (size_t i = 0; i < entry.size(); i++) {
+        if (i == 0 || entry[i].first != entry[i - 1].first) {
+            out.adj_indices.push_back((uint32_t)(entry[i].first % count));
+            out.adj_indptr[entry[i].first / count + 1]++;
+            sums.push_back(0);
+        }
+        sums.back() += entry[i].second;
+    }
+    for (uint64_t a = 0; a < count; a++) out.adj_indptr[a + 1] += out.adj_indptr[a];
+    for (uint64_t a = 0; a < count; a++) {
+        if (tot[a] > 0xffffffffull) { printf("util_aggregate_communities: a summed weight does not fit 32 bits\n"); exit(EXIT_FAILURE); }
+        out_k[a] = (uint32_t)tot[a];
+    }
+    for (uint64_t x : sums) {
+        if (x > 0xffffffffull) { printf("util_aggregate_communities: a summed weight does not fit 32 bits\n"); exit(EXIT_FAILURE); }
+        out_weights.push_back((uint32_t)x);
+    }
+    out.adj_data.assign(out.adj_indices.size(), data_type(1));
+    return out;
+}
+
 // The matrix preparation of app::BetweennessCentrality (an extension): the simple DIRECTED graph of m -- an edge u -> v iff u != v
 // and a stored non-zero entry A[v,u] exists: zero values, the diagonal and duplicates are dropped, the direction is kept.  Row v of
 // `in` lists the vertices v is pulled from, row u of `out` (the transposed pattern) the out-neighbours of u; both n x n, n =

@@ -15,6 +15,7 @@
 #include "graphlily_hip_msf.h"
 #include "graphlily_hip_match.h"
 #include "graphlily_hip_lpa.h"
+#include "graphlily_hip_louvain.h"
 #include "graphlily_hip_scc.h"
 #include "graphlily/io/data_formatter.h"
 #include "graphlily/io/data_loader.h"
@@ -257,6 +258,20 @@ public:
              uint64_t *stats = nullptr) {
         barrier_();
         GRAPHLILY_CHECK(gl_lpa(plan_, color, init, (uint32_t *)label.ptr(), max_sweeps, stats));
+        finish_();
+    }
+    // extension (gl_louvain_move, graphlily_hip_louvain.h): one level of Louvain's local moving on this module's matrix, read as a
+    // graph -- rows as strictly ascending sets N(v), the pattern symmetric (graphlily::io::util_symmetrize_simple prepares it) --
+    // into `label` (get_num_rows() device words), swept colour class by colour class under the proper colouring in `color` (as
+    // many device words; color() gives one), under the integer entry weights in `weight` (get_nnz() device words aligned with the
+    // matrix's entries, each at least 1, both entries of an edge the same; nullptr: all 1) and the vertex weights in
+    // `vertex_weight` (get_num_rows() device words; nullptr: the sums of the entry weights); stats (optional, 7 host words)
+    // receives {sweeps, moves, evaluations, launches, stop reason, q_first, q_last}, the two Q values as int64_t bits.  Only the
+    // (||,&&) layout keeps the rows this pass walks.  The call synchronises.
+    void louvain_move(DeviceBuffer label, const uint32_t *color, const uint32_t *weight = nullptr, const uint32_t *vertex_weight = nullptr,
+                      uint32_t max_sweeps = 100, uint64_t min_gain = 0, uint64_t *stats = nullptr) {
+        barrier_();
+        GRAPHLILY_CHECK(gl_louvain_move(plan_, weight, vertex_weight, color, (uint32_t *)label.ptr(), max_sweeps, min_gain, stats));
         finish_();
     }
     // extension (gl_scc, graphlily_hip_scc.h): the strongly connected components of this module's matrix, read as a directed graph

@@ -1,0 +1,631 @@
+"""CPU suite of Louvain communities (gl_louvain_move, SpMVPlan.louvain_move, SpMVModule.louvain_move, app.Louvain,
+app.validate_louvain, io.aggregate_communities): the export and its bindings exist; the host truth kept here -- move_loop(), a
+dictionary loop written from the rule's text in include/graphlily_hip_louvain.h, and louvain(), the level loop over it with a
+dictionary aggregation -- gives the closed forms of cliques, planted blocks, stars and K(6,7), agrees with networkx's modularity,
+reaches at least label propagation's modularity and 0.95 of networkx's Louvain on eight graphs, and agrees with app's numpy
+restatement (app._louvain_move_loop, app._louvain_host) on every input tests/test_gpu_louvain.py uses; io.aggregate_communities
+keeps two_m and Q; the named inputs reach every branch of the rule (the coverage proof); the validator accepts the truth and
+refuses one violation per rule.  tests/test_gpu_louvain.py compares the kernels with move_loop() and louvain() bit for bit."""
+import collections
+import functools
+import math
+import os
+import re
+
+import networkx as nx
+import numpy as np
+import pytest
+
+from graphlily_amd import app, capi, datasets, io, module as M
+
+from helpers import build_cpp_driver
+from test_msf_cpu import entry_rows, raw_csr
+from test_lpa_cpu import cliques_graph, greedy_colors, hubs_graph, largest_first, planted_graph, propagate, simple_graph
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LOUVAIN_DRIVER = os.path.join(ROOT, "build", "louvain_driver")
+HEADER = "graphlily_hip_louvain.h"
+DECL = ("int gl_louvain_move(gl_spmv_plan plan, const uint32_t *d_weight /* may be NULL: every entry 1 */, const uint32_t *d_vertex_weight "
+        "/* may be NULL: the sum of the entry weights */, const uint32_t *d_color, uint32_t *d_label, uint32_t max_sweeps, uint64_t min_gain, "
+        "uint64_t *h_stats /* may be NULL, 7 words: sweeps, moves, evaluations, launches, stop reason, q_first, q_last */);")
+
+
+# ------------------------------------------------------------------ the host truth, from the rule's text
+def _weighted_hoods(sym, weights):
+    indptr = sym.adj_indptr.astype(np.int64).tolist()
+    cols = sym.adj_indices.astype(np.int64).tolist()
+    w = [1] * len(cols) if weights is None else [int(x) for x in weights]
+    return [[(u, w[j]) for j, u in zip(range(indptr[v], indptr[v + 1]), cols[indptr[v]:indptr[v + 1]]) if u != v] for v in range(sym.num_rows)]
+
+
+def q_of(hood, k, label):
+    """Q = two_m * In - sum_c tot[c]^2 in Python integers"""
+    two_m = sum(k)
+    inner = sum(k[v] - sum(w for _, w in h) for v, h in enumerate(hood))
+    inner += sum(w for v, h in enumerate(hood) for u, w in h if label[u] == label[v])
+    tot = {}
+    for v, l in enumerate(label):
+        tot[l] = tot.get(l, 0) + k[v]
+    return two_m * inner - sum(t * t for t in tot.values())
+
+
+def move_loop(sym, weights, vertex_weights, colors, max_sweeps, min_gain, trace=None):
+    """-> (uint32[n] labels, sweeps, moves, evaluations, stop reason, q_first, q_last).  trace(v, own, cur, scores, moved, sweep)
+    is called for every evaluation, scores = {c: score(c)} over the neighbouring c != own."""
+    n = sym.num_rows
+    hood = _weighted_hoods(sym, weights)
+    k = [sum(w for _, w in h) for h in hood] if vertex_weights is None else [int(x) for x in vertex_weights]
+    two_m = sum(k)
+    assert two_m < 1 << 31 and all(k[v] >= sum(w for _, w in h) for v, h in enumerate(hood))
+    label = list(range(n))
+    if not any(hood):
+        return np.arange(n, dtype=np.uint32), 1, 0, 0, 1, 0, 0
+    tot = list(k)
+    col = [int(c) for c in colors]
+    classes = [[v for v in range(n) if col[v] == c and hood[v]] for c in range(max(col) + 1)]
+    q_first = q_last = q_of(hood, k, label)
+    sweeps = moves = evaluations = reason = 0
+    while True:
+        sweeps += 1
+        moved = 0
+        for members in classes:
+            decided = []                                  # the class decides from the snapshot; its moves are applied behind it
+            for v in members:
+                evaluations += 1
+                own = label[v]
+                kin = {}
+                for u, w in hood[v]:
+                    kin[label[u]] = kin.get(label[u], 0) + w
+                cur = two_m * kin.get(own, 0) - k[v] * (tot[own] - k[v])
+                scores = {c: two_m * x - k[v] * tot[c] for c, x in kin.items() if c != own}
+                go = bool(scores) and max(scores.values()) > cur
+                if trace:
+                    trace(v, own, cur, scores, go, sweeps)
+                if go:
+                    best = max(scores.values())
+                    decided.append((v, min(c for c, s in scores.items() if s == best)))
+            for v, c in decided:
+                tot[label[v]] -= k[v]
+                tot[c] += k[v]
+                label[v] = c
+            moved += len(decided)
+        moves += moved
+        q_old, q_last = q_last, q_of(hood, k, label)
+        if moved == 0:
+            reason = 1
+            break
+        if q_last - q_old <= min_gain:
+            reason = 2
+            break
+        if sweeps >= max_sweeps:
+            break
+    return np.asarray(label, dtype=np.uint32), sweeps, moves, evaluations, reason, q_first, q_last
+
+
+def aggregate(sym, weights, k, label):
+    """the dictionary aggregation -> (graph, weights, tot, community_of): communities numbered in ascending order of label"""
+    hood = _weighted_hoods(sym, weights)
+    number = {l: i for i, l in enumerate(sorted(set(int(x) for x in label)))}
+    part = [number[int(l)] for l in label]
+    tot = [0] * len(number)
+    edges = {}
+    for v, h in enumerate(hood):
+        tot[part[v]] += int(k[v])
+        for u, w in h:
+            if part[u] != part[v]:
+                edges[(part[v], part[u])] = edges.get((part[v], part[u]), 0) + w
+    keys = sorted(edges)
+    g = raw_csr(len(number), [a for a, _ in keys], [b for _, b in keys], np.ones(len(keys)))
+    return g, np.asarray([edges[e] for e in keys], dtype=np.uint32), np.asarray(tot, dtype=np.uint32), np.asarray(part, dtype=np.uint32)
+
+
+def pattern_degrees(g):
+    return np.diff(g.adj_indptr.astype(np.int64)).astype(np.uint32)
+
+
+def louvain(sym, tol=1e-7, max_sweeps=100, max_levels=32, order="largest_first", seed=0, colorings=None, trace=None):
+    """the level loop -> dict(labels, levels, sizes, colors, sweeps, moves, q, dendrogram, colorings, discarded)"""
+    n = sym.num_rows
+    graph, weights, k = sym, None, pattern_degrees(sym)
+    part = list(range(n))
+    out = dict(levels=0, sizes=[], colors=[], sweeps=[], moves=[], q=[], dendrogram=[], colorings=[], discarded=False)
+    accepted = None
+    for level in range(max_levels):
+        if colorings is not None:
+            colors = np.asarray(colorings[level])[:graph.num_rows]
+        else:
+            colors = greedy_colors(graph, io.coloring_priorities(pattern_degrees(graph), order, seed))
+        two_m = int(k.astype(np.int64).sum())
+        label, sweeps, moves, _, _, q_first, q_last = move_loop(graph, weights, k, colors, max_sweeps, math.floor(tol * float(two_m * two_m)),
+                                                                 trace=(lambda *a: trace(level, *a)) if trace else None)
+        out["sizes"].append(graph.num_rows)
+        out["colors"].append(int(colors.max()) + 1 if colors.shape[0] else 0)
+        out["colorings"].append(colors)
+        out["sweeps"].append(sweeps)
+        out["moves"].append(moves)
+        out["q"].append((q_first, q_last))
+        accepted = q_first if accepted is None else accepted
+        if moves == 0 or q_last <= accepted:
+            out["discarded"] = moves != 0
+            break
+        accepted = q_last
+        smaller, weights, k, number = aggregate(graph, weights, k, label)
+        part = [int(number[c]) for c in part]
+        out["dendrogram"].append(np.asarray(part, dtype=np.uint32))
+        out["levels"] += 1
+        if smaller.num_rows == graph.num_rows:
+            break
+        graph = smaller
+    smallest = {}
+    for v, c in enumerate(part):
+        smallest.setdefault(c, v)
+    out["labels"] = np.asarray([smallest[c] for c in part], dtype=np.uint32)
+    return out
+
+
+def modularity_of(sym, labels):
+    d = app.Louvain.__new__(app.Louvain)
+    d.graph_, d.degrees_, d.labels_ = sym, pattern_degrees(sym), np.asarray(labels)
+    return d.modularity()
+
+
+# ------------------------------------------------------------------ the graphs of tests/test_gpu_louvain.py
+def from_networkx(G, pad=128):
+    """-> the symmetric simple graph of G over its nodes in sorted order, padded to a multiple of `pad` vertices"""
+    nodes = sorted(G.nodes())
+    index = {v: i for i, v in enumerate(nodes)}
+    e = [(index[a], index[b]) for a, b in G.edges() if a != b]
+    n = -(-max(1, len(nodes)) // pad) * pad
+    return simple_graph(n, [a for a, _ in e], [b for _, b in e])
+
+
+def path_of(m):
+    return simple_graph(128, np.arange(m - 1), np.arange(1, m))
+
+
+def star_of(leaves, hub=5):
+    """hub `hub`, leaves hub + 1 .. hub + leaves; the hub is colour 0"""
+    n = -(-(hub + leaves + 1) // 128) * 128
+    colors = np.ones(n, dtype=np.uint32)
+    colors[hub] = 0
+    colors[hub + leaves + 1:] = 0
+    return simple_graph(n, np.full(leaves, hub), np.arange(hub + 1, hub + 1 + leaves)), colors
+
+
+def gnp_small(seed, lo=8, hi=40, p_lo=0.1, p_hi=0.5):
+    """the seeded small G(n, p) of the two searches below: n in lo .. hi - 1 and p in p_lo .. p_hi drawn from the seed"""
+    rng = np.random.default_rng(seed)
+    n = int(rng.integers(lo, hi))
+    return from_networkx(nx.gnp_random_graph(n, float(rng.uniform(p_lo, p_hi)), seed=seed))
+
+
+def small_rmat():
+    raw = datasets.rmat(2048, 16000, seed=21, symmetric=False)
+    return io.symmetrize_simple(raw)[0]
+
+
+def random_weights(sym, seed, top=1000, inner=50):
+    """-> (uint32 entry weights 1 .. top, the same word in both entries of an edge; uint32 k = their sums + 0 .. inner)"""
+    rng = np.random.default_rng(seed)
+    rows, cols = entry_rows(sym), sym.adj_indices.astype(np.int64)
+    n = sym.num_rows
+    key = np.minimum(rows, cols) * n + np.maximum(rows, cols)
+    edge, which = np.unique(key, return_inverse=True)
+    w = rng.integers(1, top + 1, size=edge.shape[0])[which.reshape(-1)].astype(np.uint32)
+    k = np.zeros(n, dtype=np.int64)
+    np.add.at(k, rows, w.astype(np.int64))
+    k += rng.integers(0, inner + 1, size=n) * (k > 0)
+    return w, k.astype(np.uint32)
+
+
+BRANCH_LEAVES = 6
+
+
+def branches_case(k20=1, k22=1, k_leaf=1):
+    """one small weighted graph per branch of the rule, all in one input.  Class 0: the centres 10, 20, 30, 40 and the leaves 23 ..
+    of 21; class 1: everybody else.
+      centre 10, leaves 11, 12, equal weights and equal k: sweep 1, a TIE broken towards the smaller label 11
+      centre 20 between 21 and 22: sweep 1 takes it to 21 together with 21's BRANCH_LEAVES heavy leaves, so that in sweep 2 its cur
+                is far below zero; 22 is heavy too, so its only other score is NEGATIVE, and still above cur: it moves to 22
+      centre 30, leaf 31, with k[30] * k[31] == two_m: sweep 1, score == cur == 0 exactly: it STAYS
+      centre 40, leaves 41 (weight 7) and 42 (weight 3): weights above 1 decide
+    k20, k22 and k_leaf are the INTERNAL weights of 20, 22 and each leaf of 21; 30 gets 1 and 31 whatever makes the equality hold."""
+    n = 128
+    leaves = list(range(23, 23 + BRANCH_LEAVES))
+    a = [10, 10, 20, 20, 30, 40, 40] + [21] * BRANCH_LEAVES
+    b = [11, 12, 21, 22, 31, 41, 42] + leaves
+    w = [1, 1, 1, 1, 1, 7, 3] + [1] * BRANCH_LEAVES
+    sym = simple_graph(n, a, b)
+    rows, cols = entry_rows(sym), sym.adj_indices.astype(np.int64)
+    weight = {(min(x, y), max(x, y)): z for x, y, z in zip(a, b, w)}
+    weights = np.asarray([weight[(min(r, c), max(r, c))] for r, c in zip(rows.tolist(), cols.tolist())], dtype=np.uint32)
+    k = np.zeros(n, dtype=np.int64)
+    np.add.at(k, rows, weights.astype(np.int64))
+    k[20] += k20
+    k[22] += k22
+    k[leaves] += k_leaf
+    k[30] += 1                                                            # k[30] = 2: k[31] = 1 + x with two_m' + x == 2 (1 + x)
+    k[31] += int(k.sum()) - 2
+    assert int(k[30]) * int(k[31]) == int(k.sum())
+    colors = np.ones(n, dtype=np.uint32)
+    colors[[10, 20, 30, 40] + leaves] = 0
+    colors[[v for v in range(n) if sym.adj_indptr[v] == sym.adj_indptr[v + 1]]] = 0
+    return sym, weights, k.astype(np.uint32), colors
+
+
+def _branch_20(case):
+    """-> what centre 20 saw in sweep 2: (cur, scores, moved)"""
+    seen = {}
+
+    def trace(v, own, cur, scores, moved, sweep):
+        if v == 20 and sweep == 2:
+            seen[20] = (cur, dict(scores), moved)
+    move_loop(case[0], case[1], case[2], case[3], 2, 0, trace)
+    return seen.get(20)
+
+
+@functools.lru_cache(maxsize=None)
+def _branches_tuned():
+    """branches_case with the first internal weights, in a fixed search order, under which centre 20's sweep 2 is the negative
+    move its docstring describes; the coverage test asserts every branch again on the result"""
+    for k_leaf in (5, 10, 20, 40):
+        for k22 in (5, 10, 20, 40, 80):
+            for k20 in (1, 2, 4, 8):
+                case = branches_case(k20, k22, k_leaf)
+                got = _branch_20(case)
+                if got and got[2] and list(got[1]) == [22] and got[0] < got[1][22] < 0:
+                    return case
+    raise AssertionError("no internal weights make centre 20's best score negative above cur")
+
+
+@functools.lru_cache(maxsize=None)
+def louvain_case(name):
+    """-> (graph, weights or None, vertex weights or None, colours, max_sweeps, min_gain, want = move_loop's tuple): computed once,
+    shared, never written"""
+    weights = vweights = None
+    max_sweeps, min_gain = 100, 0
+    if name.startswith("path_"):
+        sym = path_of(int(name[5:]))
+        colors = greedy_colors(sym)
+    elif name.startswith("cliques_"):
+        sym = cliques_graph(int(name[8:]))
+        colors = greedy_colors(sym)
+    elif name.startswith("row_") or name == "star_3000":
+        sym, colors = star_of(int(name.split("_")[1]))
+    elif name == "hubs":
+        sym = hubs_graph()
+        colors = largest_first(sym)
+    elif name == "branches":
+        sym, weights, vweights, colors = _branches_tuned()
+    elif name.startswith("planted"):
+        sym = planted_graph()
+        colors = largest_first(sym)
+        if name != "planted":
+            weights, vweights = random_weights(sym, 31)
+        if name == "planted_short":
+            max_sweeps = louvain_case("planted_weighted")[6][1] - 1
+        if name == "planted_gain":
+            full = louvain_case("planted_weighted")[6]
+            min_gain = full[6] - full[5]                  # more than any single sweep gains: sweep 1 ends the run
+    elif name == "q_falls":
+        sym = gnp_small(Q_FALLS_SEED)
+        colors = largest_first(sym)
+    elif name in ("rmat", "rmat_weighted"):
+        sym = small_rmat()
+        colors = largest_first(sym)
+        if name == "rmat_weighted":
+            weights, vweights = random_weights(sym, 32)
+    else:
+        raise KeyError(name)
+    want = move_loop(sym, weights, vweights, colors, max_sweeps, min_gain)
+    want[0].setflags(write=False)
+    for arr in (colors, weights, vweights):
+        if arr is not None:
+            arr.setflags(write=False)
+    return sym, weights, vweights, colors, max_sweeps, min_gain, want
+
+
+MOVE_CASES = ["path_2", "path_50", "cliques_3", "cliques_17", "cliques_65", "cliques_130", "row_255", "row_256", "row_257", "star_3000", "hubs",
+              "branches", "planted", "planted_weighted", "planted_short", "planted_gain", "rmat", "rmat_weighted", "q_falls"]
+
+
+@functools.lru_cache(maxsize=None)
+def driver_graph(name):
+    """-> (raw matrix for the driver, its symmetric padded graph): "planted" is label propagation's planted graph, "rmat" the small
+    R-MAT, "discarded" the first of 400 seeded small G(n, p) whose second level moves vertices and loses; all are symmetric and padded
+    already, so the driver plans them as they are"""
+    if name == "planted":
+        sym = planted_graph()
+    elif name == "rmat":
+        sym = small_rmat()
+    elif name == "discarded":
+        sym = gnp_small(107, 8, 60, 0.08, 0.6)
+    else:
+        raise KeyError(name)
+    return sym, sym
+
+
+@functools.lru_cache(maxsize=None)
+def driver_case(name, order="largest_first", seed=0):
+    raw, sym = driver_graph(name)
+    return louvain(sym, order=order, seed=seed)
+
+
+# ------------------------------------------------------------------ the eight graphs of the quality table
+def _karate():
+    """the karate club without networkx's edge weights: input weights are out of scope, so the model and networkx read one graph"""
+    K, G = nx.karate_club_graph(), nx.Graph()
+    G.add_nodes_from(sorted(K.nodes()))
+    G.add_edges_from(K.edges())
+    return G
+
+
+def quality_graphs():
+    return [("ring_of_cliques_8_4", nx.ring_of_cliques(8, 4)), ("barbell_5_0", nx.barbell_graph(5, 0)),
+            ("planted_8_40", nx.planted_partition_graph(8, 40, 0.3, 0.01, seed=1)), ("karate", _karate()),
+            ("planted_16_32", nx.planted_partition_graph(16, 32, 0.25, 0.03, seed=2)), ("barabasi_albert_2000_4", nx.barabasi_albert_graph(2000, 4, seed=3)),
+            ("grid_20_20", nx.convert_node_labels_to_integers(nx.grid_2d_graph(20, 20))), ("gnp_500", nx.gnp_random_graph(500, 0.02, seed=5))]
+
+
+@functools.lru_cache(maxsize=None)
+def quality_rows():
+    """-> [(name, model modularity, label propagation's modularity, networkx's lowest over seeds 0 - 2)]"""
+    rows = []
+    for name, G in quality_graphs():
+        sym = from_networkx(G)
+        res = louvain(sym)
+        lpa = propagate(sym, largest_first(sym), None, 100)[0]
+        low = min(nx.algorithms.community.modularity(G, nx.algorithms.community.louvain_communities(G, seed=s)) for s in range(3))
+        rows.append((name, modularity_of(sym, res["labels"]), modularity_of(sym, lpa), low))
+    return rows
+
+
+# ------------------------------------------------------------------ the tests
+def _declared(header):
+    text = open(os.path.join(ROOT, "include", header)).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    return text, sorted(set(re.findall(r"\b(gl_[a-z0-9_]+)\s*\(", text)))
+
+
+def test_library_exports_and_binds_the_entry_point():
+    """this extension's own header against its own entry of capi.EXT_HEADERS and the library; nothing about other entries"""
+    L = capi.lib()
+    assert hasattr(L, "gl_louvain_move"), "libgraphlily_hip.so does not export gl_louvain_move"
+    assert len(L.gl_louvain_move.argtypes) == 8
+    text, names = _declared(HEADER)
+    assert DECL in open(os.path.join(ROOT, "include", HEADER)).read() and '#include "graphlily_hip.h"' in text and 'extern "C"' in text
+    assert sorted(capi.EXT_HEADERS[HEADER]) == names == ["gl_louvain_move"]
+    assert all(hasattr(L, s) for s in capi.EXT_HEADERS[HEADER])
+    assert "gl_louvain_move" not in capi.EXPORTS and "gl_louvain_move" not in capi.EXT_EXPORTS
+    assert callable(capi.SpMVPlan.louvain_move) and callable(M.SpMVModule.louvain_move)
+    assert callable(app.Louvain.run) and callable(app.Louvain.modularity) and callable(app.validate_louvain) and callable(io.aggregate_communities)
+    spmv_h = open(os.path.join(ROOT, "include", "graphlily", "module", "spmv_module.h")).read()
+    assert "void louvain_move(DeviceBuffer label, const uint32_t *color, const uint32_t *weight = nullptr" in spmv_h
+    assert '#include "%s"' % HEADER in spmv_h
+    louvain_h = open(os.path.join(ROOT, "include", "graphlily", "app", "louvain.h")).read()
+    for piece in ("class Louvain", "run(", "labels()", "levels()", "level_sizes()", "level_colors()", "level_sweeps()", "level_moves()", "level_q()",
+                  "num_communities()", "community_sizes()", "modularity()", "util_symmetrize_simple", "util_aggregate_communities"):
+        assert piece in louvain_h, piece
+    make = open(os.path.join(ROOT, "graphlily_amd", "csrc", "Makefile")).read()
+    assert "gl_louvain.hip" in make and HEADER in make and "gl_classes.h" in make
+    entry = open(os.path.join(ROOT, "__graft_entry__.py")).read()
+    assert "EXT_HEADERS" in entry and "louvain_driver.cpp" in entry
+    # the colour bucketing, the hash and the wavefront helpers live in one header that both files include
+    shared = open(os.path.join(ROOT, "graphlily_amd", "csrc", "gl_classes.h")).read()
+    for unit in ("gl_lpa.hip", "gl_louvain.hip"):
+        text = open(os.path.join(ROOT, "graphlily_amd", "csrc", unit)).read()
+        assert '#include "gl_classes.h"' in text
+        for helper in ("lpa_check_kernel", "lpa_scan_kernel", "lpa_scatter_kernel", "lpa_mix", "lpa_wave_sync"):
+            assert re.search(r"void\s+%s\(|uint32_t\s+%s\(" % (helper, helper), shared) and not re.search(r"(void|uint32_t)\s+%s\(" % helper, text)
+
+
+def test_entry_point_fails_loudly_without_a_gpu():
+    if capi.device_count() == 0:
+        assert capi.lib().gl_louvain_move(None, None, None, None, None, 1, 0, None) == capi.GL_ERR_NOT_INITIALIZED
+
+
+def test_cpp_driver_compiles_against_the_headers():
+    assert os.path.exists(build_cpp_driver("louvain_driver.cpp"))
+
+
+def _communities(labels, upto):
+    groups = {}
+    for v, l in enumerate(np.asarray(labels)[:upto].tolist()):
+        groups.setdefault(l, []).append(v)
+    return sorted(groups.values())
+
+
+def test_closed_forms_of_the_host_truth():
+    res = louvain(from_networkx(nx.ring_of_cliques(8, 4)))
+    assert _communities(res["labels"], 32) == [list(range(4 * i, 4 * i + 4)) for i in range(8)]
+    res = louvain(from_networkx(nx.barbell_graph(5, 0)))
+    assert _communities(res["labels"], 10) == [[0, 1, 2, 3, 4], [5, 6, 7, 8, 9]]
+    G = nx.planted_partition_graph(8, 40, 0.3, 0.01, seed=1)
+    res = louvain(from_networkx(G))
+    assert _communities(res["labels"], 320) == [list(range(40 * i, 40 * i + 40)) for i in range(8)]
+    for G, used in ((nx.star_graph(9), 10), (nx.complete_bipartite_graph(6, 7), 13)):       # one community, Q = 0
+        sym = from_networkx(G)
+        res = louvain(sym)
+        assert _communities(res["labels"], used) == [list(range(used))] and modularity_of(sym, res["labels"]) == 0.0
+        assert np.array_equal(res["labels"][used:], np.arange(used, sym.num_rows))
+    empty = raw_csr(128, [], [], [])
+    res = louvain(io.symmetrize_simple(empty)[0])
+    assert np.array_equal(res["labels"], np.arange(128)) and res["levels"] == 0 and res["sweeps"] == [1] and res["q"] == [(0, 0)]
+    lonely = simple_graph(128, [3, 3, 4], [4, 5, 5])                       # a triangle among isolated vertices
+    res = louvain(lonely)
+    assert res["labels"].tolist() == [0, 1, 2, 3, 3, 3] + list(range(6, 128))
+    for k in (3, 17, 65, 130):                                            # disjoint cliques: one community each
+        sym, _, _, colors, _, _, want = louvain_case("cliques_%d" % k)
+        assert [len(set(want[0][5 + i * (k + 2):5 + i * (k + 2) + k].tolist())) for i in range(3)] == [1, 1, 1]
+    for leaves in (255, 256, 257, 3000):                                  # a star: everybody joins the hub's first choice
+        sym, _, _, colors, _, _, want = louvain_case("row_%d" % leaves if leaves < 3000 else "star_3000")
+        assert colors[5] == 0 and len(set(want[0][5:6 + leaves].tolist())) == 1 and want[4] == 1
+
+
+def test_modularity_is_networkx_modularity():
+    for name, G in quality_graphs():
+        sym = from_networkx(G)
+        res = louvain(sym)
+        groups = [set(g) for g in _communities(res["labels"], G.number_of_nodes())]
+        assert abs(modularity_of(sym, res["labels"]) - nx.algorithms.community.modularity(G, groups)) < 1e-12, name
+        accepted = res["q"][res["levels"] - 1][1] if res["levels"] else res["q"][0][0]
+        assert abs(accepted / (2 * G.number_of_edges()) ** 2 - modularity_of(sym, res["labels"])) < 1e-12, name
+
+
+def test_quality_against_label_propagation_and_networkx():
+    """the model's modularity is at least label propagation's host-model modularity on the same graph and at least 0.95 times
+    the lowest of networkx's Louvain over seeds 0 - 2; the ratios are printed (EXPERIMENTS.md Round 25 records them)"""
+    for name, model, lpa, low in quality_rows():
+        print("%-24s model %.4f  lpa %.4f  networkx-low %.4f  ratio %.4f" % (name, model, lpa, low, model / low))
+    for name, model, lpa, low in quality_rows():
+        assert model >= lpa, (name, model, lpa)
+        assert model >= 0.95 * low, (name, model, low)
+
+
+@pytest.mark.parametrize("name", ["planted_weighted", "rmat_weighted", "branches", "planted"])
+def test_aggregation_preserves_two_m_and_q(name):
+    sym, weights, vweights, colors, _, _, want = louvain_case(name)
+    hood = _weighted_hoods(sym, weights)
+    k = [sum(w for _, w in h) for h in hood] if vweights is None else vweights.tolist()
+    g, w, tot, part = io.aggregate_communities(sym, weights, vweights, want[0])
+    mine = aggregate(sym, weights, k, want[0])
+    assert np.array_equal(g.adj_indptr, mine[0].adj_indptr) and np.array_equal(g.adj_indices, mine[0].adj_indices)
+    assert np.array_equal(w, mine[1]) and np.array_equal(tot, mine[2]) and np.array_equal(part, mine[3])
+    assert w.dtype == tot.dtype == part.dtype == np.uint32 and not np.any(entry_rows(g) == g.adj_indices)
+    assert np.array_equal(np.unique(want[0])[part], want[0])              # numbered in ascending order of label
+    assert int(tot.astype(np.int64).sum()) == sum(k)
+    assert q_of(_weighted_hoods(g, w), tot.tolist(), list(range(g.num_rows))) == want[6] == q_of(hood, k, want[0].tolist())
+    assert app._louvain_move_loop(g, w, tot, greedy_colors(g), 1, 0)[5] == want[6]
+
+
+@pytest.mark.parametrize("name", MOVE_CASES)
+def test_app_restatement_equals_the_host_truth(name):
+    sym, weights, vweights, colors, max_sweeps, min_gain, want = louvain_case(name)
+    got = app._louvain_move_loop(sym, weights, vweights, colors, max_sweeps, min_gain)
+    assert np.array_equal(got[0], want[0]) and tuple(got[1:]) == tuple(want[1:]), (got[1:], want[1:])
+
+
+@pytest.mark.parametrize("name,order", [("planted", "largest_first"), ("planted", "natural"), ("planted", "random"), ("rmat", "largest_first")])
+def test_app_level_loop_equals_the_host_truth(name, order):
+    raw, sym = driver_graph(name)
+    want = driver_case(name, order)
+    got = app._louvain_host(sym, pattern_degrees(sym), 1e-7, 100, 32, order, 0)
+    assert np.array_equal(got["labels"], want["labels"]) and got["levels"] == want["levels"]
+    for key in ("sizes", "colors", "sweeps", "moves", "q"):
+        assert [tuple(x) if isinstance(x, tuple) else x for x in got[key]] == want[key], key
+    assert all(np.array_equal(a, b) for a, b in zip(got["dendrogram"], want["dendrogram"])) and len(got["dendrogram"]) == want["levels"]
+    assert app.validate_louvain(raw, want["labels"], order=order) == np.unique(want["labels"]).shape[0]
+
+
+def test_coverage_proof_of_the_named_inputs():
+    """the inputs tests/test_gpu_louvain.py names reach: a move whose best score is negative, a tie broken towards the smaller
+    label, a stay on best == cur, weights above 1 and non-zero internal weight, a level that is discarded"""
+    seen = {}
+
+    def trace(v, own, cur, scores, moved, sweep):
+        if (sweep == 1 and v in (10, 30, 40)) or (sweep == 2 and v == 20):
+            seen[v] = (own, cur, dict(scores), moved)
+    sym, weights, vweights, colors, _, _, want = louvain_case("branches")
+    move_loop(sym, weights, vweights, colors, 2, 0, trace)
+    own, cur, scores, moved = seen[10]
+    assert scores[11] == scores[12] > cur and moved                       # the tie, towards the smaller label
+    own, cur, scores, moved = seen[20]
+    assert own == 21 and list(scores) == [22] and cur < scores[22] < 0 and moved     # the best score is negative, and cur lower still
+    own, cur, scores, moved = seen[30]
+    assert list(scores) == [31] and scores[31] == cur == 0 and not moved  # best == cur: it stays
+    own, cur, scores, moved = seen[40]
+    assert scores[41] > scores[42] and moved
+    one, two = move_loop(sym, weights, vweights, colors, 1, 0)[0], move_loop(sym, weights, vweights, colors, 2, 0)[0]
+    assert (one[10], one[20], one[30], one[40]) == (11, 21, 30, 41) and (two[20], two[30]) == (22, 30)
+    assert int(weights.max()) > 1 and np.any(vweights.astype(np.int64) > np.bincount(entry_rows(sym), weights=weights, minlength=sym.num_rows))
+    counts = collections.Counter()                                         # ... and at scale: ties among many classes
+    sym = louvain_case("planted")[0]
+
+    def tally_unit(v, own, cur, scores, moved, sweep):
+        if scores:
+            best = max(scores.values())
+            counts["tie"] += moved and sum(1 for s in scores.values() if s == best) > 1
+            counts["equal_stay"] += best == cur
+    move_loop(sym, None, None, louvain_case("planted")[3], 100, 0, tally_unit)
+    assert counts["tie"] > 0, counts
+    assert DISCARDED_CASE is not None
+    name, order = DISCARDED_CASE
+    res = driver_case(name, order)
+    assert res["discarded"] and len(res["sizes"]) == res["levels"] + 1 and res["moves"][-1] > 0 and res["q"][-1][1] <= res["q"][-2][1]
+
+
+DISCARDED_CASE = ("discarded", "largest_first")      # the driver input whose last level moves vertices and is discarded
+
+
+def test_a_sweep_in_which_q_falls():
+    """scores use the class-start snapshot, so a sweep may lose: the first of up to 200 seeded G(n, p) graphs with such a sweep
+    is pinned (Q_FALLS_SEED; None: none was found, EXPERIMENTS.md Round 25 says so)"""
+    def falls(seed):
+        sym = gnp_small(seed)
+        if sym.nnz == 0:
+            return False
+        hood, k = _weighted_hoods(sym, None), pattern_degrees(sym).tolist()
+        colors = largest_first(sym)
+        before = q_of(hood, k, list(range(sym.num_rows)))
+        for sweeps in range(1, 30):
+            label, ran, _, _, reason, _, q = move_loop(sym, None, None, colors, sweeps, -(1 << 62))
+            if q < before:
+                return True
+            if reason == 1 or ran < sweeps:
+                return False
+            before = q
+        return False
+    if Q_FALLS_SEED is None:
+        assert not any(falls(seed) for seed in range(200))
+    else:
+        assert falls(Q_FALLS_SEED) and not any(falls(seed) for seed in range(Q_FALLS_SEED))
+        sym, _, _, colors, _, _, want = louvain_case("q_falls")            # the run ends on the losing sweep: reason 2
+        assert want[4] == 2 and want[1] > 1 and move_loop(sym, None, None, colors, want[1] - 1, 0)[6] > want[6]
+
+
+Q_FALLS_SEED = 51
+
+
+def test_validator_accepts_the_truth_and_refuses_one_violation_per_rule():
+    raw, sym = driver_graph("planted")
+    want = driver_case("planted")["labels"]
+    assert app.validate_louvain(raw, want) == np.unique(want).shape[0]
+    bad = want.copy()
+    member = int(np.flatnonzero(want == want[0])[1])
+    bad[want == want[0]] = member                                         # a community labelled with a member that is not its smallest
+    with pytest.raises(ValueError, match="rule 1"):
+        app.validate_louvain(raw, bad)
+    bad = want.copy()
+    bad[1279] = 1278
+    with pytest.raises(ValueError, match="rule 1|rule 2"):
+        app.validate_louvain(raw, bad)
+    bad = want.copy()
+    bad[1279] = 0                                                         # an isolated (padding) vertex joins a community
+    with pytest.raises(ValueError, match="rule 2"):
+        app.validate_louvain(raw, bad)
+    with pytest.raises(ValueError, match="rule 3"):
+        app.validate_louvain(raw, np.arange(1280, dtype=np.uint32))        # proper labels, but not the level loop's
+    with pytest.raises(ValueError, match="labels for the"):
+        app.validate_louvain(raw, want[:5])
+
+
+def test_driver_refuses_what_it_cannot_do():
+    d = app.Louvain.__new__(app.Louvain)
+    d.sent_ = False
+    with pytest.raises(RuntimeError, match="send_matrix_host_to_device first"):
+        d.run()
+    d.labels_ = None
+    with pytest.raises(RuntimeError, match="run\\(\\) first"):
+        d.modularity()
+    assert "tot" in app.Louvain._no_shards_
+
+
+def test_label_propagation_modularity_is_unchanged():
+    """LabelPropagation.modularity and Louvain.modularity call one helper; its value is networkx's"""
+    G = _karate()
+    sym = from_networkx(G)
+    lab = propagate(sym, largest_first(sym), None, 100)[0]
+    d = app.LabelPropagation.__new__(app.LabelPropagation)
+    d.graph_, d.degrees_, d.labels_ = sym, pattern_degrees(sym), lab
+    groups = [set(g) for g in _communities(lab, 34)]
+    assert abs(d.modularity() - nx.algorithms.community.modularity(G, groups)) < 1e-12 and d.modularity() == modularity_of(sym, lab)
