@@ -88,7 +88,6 @@ struct RelaxSource {
         if (inout[m.index] > m.val) inout[m.index] = m.val;
     }
     __device__ void emitted(const gl_idx_val &) const {}
-    __device__ void begin_chunk(uint32_t) const {}
 };
 
 // ---- the apply kernels for the integer value types (gl_common.h): SAT = ap_ufixed<32,8,AP_RND,AP_SAT>, else unsigned
@@ -119,7 +118,6 @@ struct RelaxSourceBits {   // RelaxSource with the unsigned ordering of the bits
         if (inout[m.index] > __float_as_uint(m.val)) inout[m.index] = __float_as_uint(m.val);
     }
     __device__ void emitted(const gl_idx_val &) const {}
-    __device__ void begin_chunk(uint32_t) const {}
 };
 
 // graphlily/global.h:153-164
@@ -144,31 +142,6 @@ __global__ __launch_bounds__(256) void bfs_bits_begin_kernel(uint32_t *__restric
     for (uint32_t w = tid; w < nvec * words; w += stride) bits[w] = (w == words + (src >> 5)) ? (1u << (src & 31u)) : 0u;
     for (uint32_t w = tid; w < ctl_words; w += stride)     // (grid-stride: more slots than a small graph's launch has threads)
         if (w != 2u) ctl[w] = w == 0u ? first_pull_slot : (w == 4u ? 0xffffffffu : (w == 15u ? ctl_words : 0u));
-}
-
-// the set bits of a frontier bit vector as list candidates (gl_bfs_pull_step_back): entry {row, 1}
-struct BitsSource {
-    const uint32_t *bits;
-    uint32_t n;
-    __device__ uint32_t size() const { return n; }
-    __device__ bool get(uint32_t i, gl_idx_val &out) const {
-        out.index = i;
-        out.val = 1.0f;
-        return (bits[i >> 5] >> (i & 31u)) & 1u;
-    }
-    __device__ void consumed(uint32_t) const {}
-    __device__ void emitted(const gl_idx_val &) const {}
-    __device__ void begin_chunk(uint32_t) const {}
-};
-
-int bits_to_sparse_gated(const uint32_t *d_bits, uint32_t n, gl_idx_val *d_out, uint32_t *d_counts, const uint32_t *gate_word,
-                         uint32_t gate_value, hipStream_t s) {
-    BitsSource src{d_bits, n};
-    Gate gate;
-    gate.word = gate_word;
-    gate.value = gate_value;
-    gate.op = GL_GATE_EQ;
-    return run_compaction(src, n, d_counts, d_out, 0.0f, s, nullptr, gate);
 }
 
 }  // namespace gl

@@ -14,13 +14,9 @@
 
 #include "graphlily_hip.h"
 
-// launch predicates and step flags of the kernels' internal interfaces (what is left of the gated schedules of rounds 2-3:
-// the compaction and the boolean pull step still take a predicate, nobody outside the library passes one)
-#define GL_GATE_EQ 0
-#define GL_GATE_GT 1
-#define GL_GATE_LE 2
+// bit 2 of `may_continue` of gl_bfs_bits_push_step / gl_bfs_bits_pull_step (bits 0..1: BfsBitsCtl::may_continue below): the
+// step runs on a row shard, whose counts are partial -- it runs or not by the control words, keeps no totals and decides nothing
 #define GL_BFS_DEFERRED 4
-#define GL_STEP_PULL_FLAGS 8
 
 namespace gl {
 

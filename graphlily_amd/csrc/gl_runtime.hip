@@ -241,8 +241,7 @@ __global__ __launch_bounds__(256) void copy_out_kernel(uint4 *__restrict__ dst, 
     for (size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; i < n16; i += (size_t)gridDim.x * 256u) dst[i] = src[i];
 }
 
-__global__ void fill_u32_gated_kernel(uint32_t *__restrict__ dst, uint32_t v, size_t n, const uint32_t *__restrict__ gate, uint32_t gate_value) {
-    if (gate && *gate != gate_value) return;
+__global__ void fill_u32_kernel(uint32_t *__restrict__ dst, uint32_t v, size_t n) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (; i < n; i += stride) dst[i] = v;
@@ -1313,14 +1312,12 @@ int gl_host_free(void *h_ptr) {
 }
 
 int gl_buf_fill_u32(uint32_t *d_dst, uint32_t value, size_t count) {
-    const uint32_t *d_gate = nullptr;
-    const uint32_t gate_value = 0u;
     GL_REQUIRE_INIT();
     if (count == 0) return GL_OK;
     GL_ARG(d_dst != nullptr);
     unsigned blocks = gl::cdiv(count, 256);
     if (blocks > 2048) blocks = 2048;
-    gl::fill_u32_gated_kernel<<<blocks, 256, 0, gl::ctx().stream>>>(d_dst, value, count, d_gate, gate_value);
+    gl::fill_u32_kernel<<<blocks, 256, 0, gl::ctx().stream>>>(d_dst, value, count);
     GL_LAUNCH_CHECK();
     return GL_OK;
 }

@@ -1039,7 +1039,8 @@ int gl_bfs_bits_pull_step(gl_spmv_plan p, gl_spmspv_plan csc, const uint32_t *d_
     if (!whole && !deferred)
         return gl::set_error(GL_ERR_UNSUPPORTED, "gl_bfs_bits_pull_step: a row shard's frontier counts are partial -- pass GL_BFS_DEFERRED "
                              "in may_continue and take the slot's decisions with gl_bfs_bits_decide after the all-gather");
-    gl::BfsBitsCtl c;
+    gl::BfsPullSchedule sched;
+    gl::BfsBitsCtl &c = sched.ctl;
     c.ctl = d_ctl;
     c.slot = slot;
     c.n = p->num_rows ? p->num_rows : 1u;
@@ -1052,9 +1053,11 @@ int gl_bfs_bits_pull_step(gl_spmv_plan p, gl_spmspv_plan csc, const uint32_t *d_
     // the new frontier's column lengths decide the direction of the NEXT slot's push: of no use to a schedule that never pushes
     const bool only_pulls = threshold < 0.0f;   // BFS.pull: gl_bfs_bits_begin(first_pull_slot = 0)
     const bool may_push = (may_continue & 2) != 0 && !only_pulls && !deferred;
-    return gl::bool_plan_bfs_step(p, d_bits_in, d_bits_out, d_distance, level, gl::ctx().stream, nullptr, 0u, GL_GATE_EQ, nullptr, 0u, 0.0f, 0,
-                                  &c, may_push ? gl::spmspv_plan_indptr(csc) : nullptr, gl::spmspv_plan_num_cols(csc),
-                                  gl::spmspv_plan_bfs_acc(csc), deferred);
+    sched.indptr = may_push ? gl::spmspv_plan_indptr(csc) : nullptr;
+    sched.ncols = gl::spmspv_plan_num_cols(csc);
+    sched.push_acc = gl::spmspv_plan_bfs_acc(csc);
+    sched.deferred = deferred;
+    return gl::bool_plan_bfs_step(p, d_bits_in, d_bits_out, d_distance, level, gl::ctx().stream, &sched);
 }
 
 int gl_spmv_run(gl_spmv_plan p, const float *d_x, const float *d_mask, float *d_y, int op, float zero,

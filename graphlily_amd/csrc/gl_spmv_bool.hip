@@ -24,6 +24,8 @@
 #include "gl_spmv_plan.h"
 #include "gl_bfs_shard.h"
 
+#include <type_traits>
+
 namespace gl {
 
 struct BoolArgs {
@@ -43,16 +45,6 @@ struct BoolArgs {
     float *dist;
     float level;
     uint32_t tickets;          // 1: ring slots are refilled from an LDS ticket per span; 0: static split (A/B builds)
-    const uint32_t *gate = nullptr;   // non-null: the launch is a no-op unless gate[0] (gate_op) gate_value (gl_bfs_pull_step_gated)
-    uint32_t gate_value = 0;
-    int gate_op = GL_GATE_EQ;
-    // pull -> push decision of a device-resident BFS schedule (gl_bfs_pull_step_back): the fused epilogue counts the rows
-    // it puts into the next frontier (ctl[5]); the workgroup that finishes last (ticket ctl[6]) compares the count with
-    // back_threshold * n and, if the frontier has become that small and iterations remain, re-opens the push gate
-    // (ctl[0] = 0xffffffff) and marks the slot (ctl[4]) so that the list-building pass behind this launch runs
-    uint32_t *back_ctl = nullptr;
-    uint32_t back_slot = 0, back_may_continue = 0, back_n = 1;
-    float back_threshold = 0.0f;
     // bit-frontier BFS schedule (gl_bfs_bits_pull_step, BfsBitsCtl in gl_common.h): the launch runs when its slot pulls
     // OR when the slot's push goes row-wise -- the same pass either way; the fused epilogue also sums the column lengths
     // of the rows it adds (the next push's work) and the workgroup that finishes last takes the step's decisions
@@ -200,10 +192,6 @@ __device__ __forceinline__ void spmv_bool_body(const BoolArgs &a, uint32_t *lds_
             if (threadIdx.x == 0) a.v2.decide(fresh, work, work_rows);
         }
         return;
-    }
-    if (a.gate) {   // (a plain load: the word is written by kernels earlier in the stream)
-        const uint32_t w = *a.gate;
-        if (!(a.gate_op == GL_GATE_EQ ? w == a.gate_value : a.gate_op == GL_GATE_GT ? w > a.gate_value : w <= a.gate_value)) return;
     }
     if (a.v2.ctl && unit == 0 && threadIdx.x == 0) a.v2.record_mode(2u);   // this slot streams the matrix row-wise
     const uint4 d = a.units[2u * unit], dh = a.units[2u * unit + 1u];
@@ -509,27 +497,6 @@ __device__ __forceinline__ void spmv_bool_body(const BoolArgs &a, uint32_t *lds_
                     a.v2.decide(total, wk, wr);
                 }
             }
-        } else if (a.back_ctl) {
-            __shared__ uint32_t fresh_s;   // one global atomic per workgroup, not per wavefront
-            if (threadIdx.x == 0) fresh_s = 0u;
-            __syncthreads();
-            if (lane == 0 && nfresh) atomicAdd(&fresh_s, nfresh);
-            __syncthreads();
-            if (threadIdx.x == 0) {
-                if (fresh_s) atomicAdd(&a.back_ctl[5], fresh_s);
-                __threadfence();
-            }
-            if (threadIdx.x == 0 && atomicAdd(&a.back_ctl[6], 1u) == gridDim.x - 1u) {   // the last workgroup decides
-                __threadfence();
-                const uint32_t total = __hip_atomic_load(&a.back_ctl[5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                a.back_ctl[5] = 0u;
-                a.back_ctl[6] = 0u;
-                if (a.back_may_continue != 0u && (float)total / (float)a.back_n < a.back_threshold) {
-                    a.back_ctl[0] = 0xffffffffu;     // pushing again from the next slot on
-                    a.back_ctl[4] = a.back_slot;     // ... and this slot's new frontier is wanted as a list
-                    a.back_ctl[7] = __float_as_uint(a.back_threshold);   // Direction::decide: stay while below this
-                }
-            }
         }
     } else if (direct) {
         for (uint32_t i = threadIdx.x; i < nrows; i += kThreads) {
@@ -620,69 +587,78 @@ static int launch_bool_keep(gl_spmv_plan p, const BoolArgs &a, hipStream_t s) {
     return GL_OK;
 }
 
-template <int MASK, int FUSED>
-static int launch_bool_variant(gl_spmv_plan p, const BoolArgs &a, hipStream_t s) {
+// KEEP bit 0 of a plan's launches: plans whose stream fits the Infinity Cache keep it there between runs
+static bool bool_plan_keeps(gl_spmv_plan p) {
     static const size_t keep_bytes = (size_t)224 << 20;
     static const size_t keep_min = (size_t)64 << 20;
-    // (the CSR copy for the bottom-up BFS step is not streamed by this kernel)
+    // (the CSR copy for the bottom-up BFS step is not streamed by these kernels)
     const size_t rows_bytes = p->d_csr_indptr ? ((size_t)(p->row_end - p->row_begin) + 1u) * 4u + (size_t)p->nnz * 4u : 0u;
     const size_t streamed = p->device_bytes - std::min<size_t>(rows_bytes, p->device_bytes);
-    const bool keep = p->bool_keep >= 0 ? p->bool_keep != 0 : (streamed <= keep_bytes && streamed >= keep_min);
-    if (p->bool_compressed == 2) return keep ? launch_bool_keep<MASK, FUSED, 7>(p, a, s) : launch_bool_keep<MASK, FUSED, 6>(p, a, s);
-    if (p->bool_compressed) return keep ? launch_bool_keep<MASK, FUSED, 3>(p, a, s) : launch_bool_keep<MASK, FUSED, 2>(p, a, s);
-    return keep ? launch_bool_keep<MASK, FUSED, 1>(p, a, s) : launch_bool_keep<MASK, FUSED, 0>(p, a, s);
+    return p->bool_keep >= 0 ? p->bool_keep != 0 : (streamed <= keep_bytes && streamed >= keep_min);
 }
 
-template <int MASK>
-static int launch_bool(gl_spmv_plan p, const BoolArgs &a, hipStream_t s) {
-    return launch_bool_variant<MASK, 0>(p, a, s);
+// f(std::integral_constant<int, KEEP>()) for the plan's stream coding (bool_compressed 0 / 1 / 2 = KEEP 0 / 2 / 6) and cache hint
+template <typename F>
+static int with_bool_keep(gl_spmv_plan p, F f) {
+    switch ((p->bool_compressed == 2 ? 6 : p->bool_compressed ? 2 : 0) | (bool_plan_keeps(p) ? 1 : 0)) {
+        case 0: return f(std::integral_constant<int, 0>());
+        case 1: return f(std::integral_constant<int, 1>());
+        case 2: return f(std::integral_constant<int, 2>());
+        case 3: return f(std::integral_constant<int, 3>());
+        case 6: return f(std::integral_constant<int, 6>());
+        default: return f(std::integral_constant<int, 7>());
+    }
 }
 
-// One BFS pull iteration on the bit layout (see the FUSED epilogue).  Unsplit plans whose shard starts on a
-// multiple of 64 rows only; bits_out must not alias bits_in.
-int bool_plan_bfs_step(gl_spmv_plan p, const uint32_t *bits_in, uint32_t *bits_out, float *d_distance, float level, hipStream_t s,
-                       const uint32_t *gate, uint32_t gate_value, int gate_op, uint32_t *back_ctl, uint32_t back_slot,
-                       float back_threshold, int back_may_continue, const BfsBitsCtl *v2, const uint32_t *v2_indptr, uint32_t v2_ncols,
-                       uint32_t *v2_push_acc, bool v2_deferred) {
-    if (p->row_end == p->row_begin) return GL_OK;
-    // split plans: only inside the bit-frontier schedule (the claiming epilogue needs an all-zero output vector)
-    const bool claim = p->segments > 1 && v2 != nullptr;
-    if ((p->segments > 1 && !claim) || (p->row_begin & 63u))
-        return set_error(GL_ERR_UNSUPPORTED, "gl_bfs_pull_step: needs an unsplit boolean plan whose shard starts on a multiple of 64 rows");
-    if (!p->nunits) return GL_OK;   // no stored entry in this shard: nothing is reached here
+template <int MASK, int FUSED>
+static int launch_bool_variant(gl_spmv_plan p, const BoolArgs &a, hipStream_t s) {
+    return with_bool_keep(p, [&](auto keep) { return launch_bool_keep<MASK, FUSED, decltype(keep)::value>(p, a, s); });
+}
+
+// the arguments every launch takes from the plan, reading x from `xbits`; the rest neutral: no mask, no output, no fused step
+static BoolArgs bool_plan_args(gl_spmv_plan p, const uint32_t *xbits) {
     BoolArgs a;
     a.entries = p->d_entries;
     a.bases = p->d_bases;
     a.units = p->d_units;
     a.hub_rows = p->d_hub_rows;
     a.spans = p->d_spans;
-    a.xbits = bits_in;
+    a.xbits = xbits;
     a.mask = nullptr;
     a.y = nullptr;
     a.zero = 0.0f;
     a.run_flag = nullptr;
+    a.bits_out = nullptr;
+    a.dist = nullptr;
+    a.level = 0.0f;
+    a.tickets = bool_tickets();
+    return a;
+}
+
+// One BFS pull iteration on the bit layout (see the FUSED epilogue).  Unsplit plans whose shard starts on a
+// multiple of 64 rows only; bits_out must not alias bits_in.
+int bool_plan_bfs_step(gl_spmv_plan p, const uint32_t *bits_in, uint32_t *bits_out, float *d_distance, float level, hipStream_t s,
+                       const BfsPullSchedule *sched) {
+    if (p->row_end == p->row_begin) return GL_OK;
+    // split plans: only inside the bit-frontier schedule (the claiming epilogue needs an all-zero output vector)
+    const bool claim = p->segments > 1 && sched != nullptr;
+    if ((p->segments > 1 && !claim) || (p->row_begin & 63u))
+        return set_error(GL_ERR_UNSUPPORTED, "gl_bfs_pull_step: needs an unsplit boolean plan whose shard starts on a multiple of 64 rows");
+    if (!p->nunits) return GL_OK;   // no stored entry in this shard: nothing is reached here
+    BoolArgs a = bool_plan_args(p, bits_in);
     a.bits_out = bits_out;
     a.dist = d_distance;
     a.level = level;
-    a.gate = gate;
-    a.gate_value = gate_value;
-    a.gate_op = gate_op;
-    a.back_ctl = back_ctl;
-    a.back_slot = back_slot;
-    a.back_threshold = back_threshold;
-    a.back_may_continue = back_may_continue ? 1u : 0u;
-    a.back_n = p->num_rows ? p->num_rows : 1u;
-    if (v2) {
-        a.v2 = *v2;
-        a.v2_indptr = v2_indptr;
-        a.v2_ncols = v2_ncols;
-        a.v2_push_acc = v2_push_acc;
-        a.v2_rowptr = v2_deferred ? nullptr : p->d_csr_indptr;
-        a.v2_deferred = v2_deferred;
+    if (sched) {
+        a.v2 = sched->ctl;
+        a.v2_indptr = sched->indptr;
+        a.v2_ncols = sched->ncols;
+        a.v2_push_acc = sched->push_acc;
+        a.v2_rowptr = sched->deferred ? nullptr : p->d_csr_indptr;
+        a.v2_deferred = sched->deferred;
     }
-    a.tickets = bool_tickets();
     if (claim) {
-        if (!v2_deferred)
+        if (!sched->deferred)
             return set_error(GL_ERR_UNSUPPORTED, "gl_bfs_bits_pull_step: a split plan keeps no totals -- run it with GL_BFS_DEFERRED");
         return launch_bool_variant<GL_NOMASK, 2>(p, a, s);
     }
@@ -707,42 +683,20 @@ static int launch_shard_step(uint32_t grid, const BoolArgs &a, const BfsPushArgs
 int bool_plan_bfs_shard_step(gl_spmv_plan p, BfsPushArgs pa, BfsShardArgs sa, hipStream_t s) {
     if ((p->row_begin & 63u) || (p->row_end != p->num_rows && (p->row_end & 63u)))
         return set_error(GL_ERR_UNSUPPORTED, "gl_bfs_bits_shard_step: the shard must be cut on multiples of 64 rows");
-    BoolArgs a;
-    a.entries = p->d_entries;
-    a.bases = p->d_bases;
-    a.units = p->d_units;
-    a.hub_rows = p->d_hub_rows;
-    a.spans = p->d_spans;
-    a.xbits = pa.bits_in;
-    a.mask = nullptr;
-    a.y = nullptr;
-    a.zero = 0.0f;
-    a.run_flag = nullptr;
+    BoolArgs a = bool_plan_args(p, pa.bits_in);
     a.bits_out = pa.bits_out;
     a.dist = pa.dist;
     a.level = pa.level;
-    a.tickets = bool_tickets();
     a.tally_mine = sa.tally_mine;
     a.t_col_len = pa.col_len;
     a.v2_rowptr = p->d_csr_indptr;
     a.v2_row_base = p->row_begin;
     sa.pull_units = p->nunits;
     const uint32_t grid = sa.finish ? 1u : std::max<uint32_t>(std::max<uint32_t>(sa.pull_units, sa.push_blocks), 1u);
-    static const size_t keep_bytes = (size_t)224 << 20;
-    static const size_t keep_min = (size_t)64 << 20;
-    const size_t rows_bytes = p->d_csr_indptr ? ((size_t)(p->row_end - p->row_begin) + 1u) * 4u + (size_t)p->nnz * 4u : 0u;
-    const size_t streamed = p->device_bytes - std::min<size_t>(rows_bytes, p->device_bytes);
-    const bool keep = p->bool_keep >= 0 ? p->bool_keep != 0 : (streamed <= keep_bytes && streamed >= keep_min);
-    if (p->bool_compressed == 2) {
-        if (p->segments > 1) return keep ? launch_shard_step<2, 7>(grid, a, pa, sa, s) : launch_shard_step<2, 6>(grid, a, pa, sa, s);
-        return keep ? launch_shard_step<1, 7>(grid, a, pa, sa, s) : launch_shard_step<1, 6>(grid, a, pa, sa, s);
-    }
-    if (p->bool_compressed) {
-        if (p->segments > 1) return keep ? launch_shard_step<2, 3>(grid, a, pa, sa, s) : launch_shard_step<2, 2>(grid, a, pa, sa, s);
-        return keep ? launch_shard_step<1, 3>(grid, a, pa, sa, s) : launch_shard_step<1, 2>(grid, a, pa, sa, s);
-    }
-    if (p->segments > 1) return keep ? launch_shard_step<2, 1>(grid, a, pa, sa, s) : launch_shard_step<2, 0>(grid, a, pa, sa, s);
-    return keep ? launch_shard_step<1, 1>(grid, a, pa, sa, s) : launch_shard_step<1, 0>(grid, a, pa, sa, s);
+    return with_bool_keep(p, [&](auto keep) {
+        constexpr int KEEP = decltype(keep)::value;
+        return p->segments > 1 ? launch_shard_step<2, KEEP>(grid, a, pa, sa, s) : launch_shard_step<1, KEEP>(grid, a, pa, sa, s);
+    });
 }
 
 // d_x != nullptr: pack it into the plan's bit vector first; else run on `bits` as the caller prepared them
@@ -763,25 +717,14 @@ int bool_plan_run(gl_spmv_plan p, const float *d_x, const uint32_t *bits, const 
         GL_LAUNCH_CHECK();
         bits = p->d_xbits;
     }
-    BoolArgs a;
-    a.entries = p->d_entries;
-    a.bases = p->d_bases;
-    a.units = p->d_units;
-    a.hub_rows = p->d_hub_rows;
-    a.spans = p->d_spans;
-    a.xbits = bits;
+    BoolArgs a = bool_plan_args(p, bits);
     a.mask = d_mask;
     a.y = d_y;
     a.zero = zero;
-    a.run_flag = nullptr;
-    a.bits_out = nullptr;
-    a.dist = nullptr;
-    a.level = 0.0f;
-    a.tickets = bool_tickets();
     switch (mask_type) {
-        case GL_NOMASK: return launch_bool<GL_NOMASK>(p, a, s);
-        case GL_MASK_WRITETOZERO: return launch_bool<GL_MASK_WRITETOZERO>(p, a, s);
-        case GL_MASK_WRITETOONE: return launch_bool<GL_MASK_WRITETOONE>(p, a, s);
+        case GL_NOMASK: return launch_bool_variant<GL_NOMASK, 0>(p, a, s);
+        case GL_MASK_WRITETOZERO: return launch_bool_variant<GL_MASK_WRITETOZERO, 0>(p, a, s);
+        case GL_MASK_WRITETOONE: return launch_bool_variant<GL_MASK_WRITETOONE, 0>(p, a, s);
         default: return set_error(GL_ERR_INVALID_ARG, "gl_spmv_run: invalid mask type %d", mask_type);
     }
 }
@@ -820,24 +763,12 @@ size_t bool_plan_xbits_bytes(gl_spmv_plan p) { return (size_t)p->nphases * kBool
 
 // gl_spmspv_run's row-wise path: x bits are already in place, no mask, zero = 0, output rows y[row_begin..row_end);
 // the kernels do nothing unless run_flag[0] != 0.  Split plans rely on y being all zero on entry.
-int bool_plan_run_bits(gl_spmv_plan p, float *d_y, const uint32_t *run_flag, hipStream_t s, const uint32_t *xbits) {
+int bool_plan_run_bits(gl_spmv_plan p, float *d_y, const uint32_t *run_flag, hipStream_t s) {
     if (p->row_end == p->row_begin || !p->nunits) return GL_OK;
-    BoolArgs a;
-    a.entries = p->d_entries;
-    a.bases = p->d_bases;
-    a.units = p->d_units;
-    a.hub_rows = p->d_hub_rows;
-    a.spans = p->d_spans;
-    a.xbits = xbits ? xbits : p->d_xbits;
-    a.mask = nullptr;
+    BoolArgs a = bool_plan_args(p, p->d_xbits);
     a.y = d_y;
-    a.zero = 0.0f;
     a.run_flag = run_flag;
-    a.bits_out = nullptr;
-    a.dist = nullptr;
-    a.level = 0.0f;
-    a.tickets = bool_tickets();
-    return launch_bool<GL_NOMASK>(p, a, s);
+    return launch_bool_variant<GL_NOMASK, 0>(p, a, s);
 }
 
 // ------------------------------------------------------------------------------------- planner

@@ -382,18 +382,23 @@ int pack_bits(const float *d_x, uint32_t n, uint32_t *d_bits, hipStream_t s);
 int unpack_bits(const uint32_t *d_bits, uint32_t n, float *d_x, hipStream_t s);
 int bfs_bits_begin_from(uint32_t *d_ctl, uint32_t ctl_words, const float *d_x, uint32_t n, uint32_t *d_bits, uint32_t words, hipStream_t s,
                         const float *d_distance, gl_spmv_plan rows);
+// what gl_bfs_bits_pull_step adds to the plain gl_bfs_pull_step: the slot's control record and, from the CSC plan of the same
+// matrix, its column pointers (null: the new frontier's column lengths are not wanted), its column count and the
+// accumulator lines of the slot's push step; deferred: GL_BFS_DEFERRED
+struct BfsPullSchedule {
+    BfsBitsCtl ctl;
+    const uint32_t *indptr;
+    uint32_t ncols;
+    uint32_t *push_acc;
+    bool deferred;
+};
 int bool_plan_bfs_step(gl_spmv_plan p, const uint32_t *bits_in, uint32_t *bits_out, float *d_distance, float level, hipStream_t s,
-                       const uint32_t *gate = nullptr, uint32_t gate_value = 0, int gate_op = GL_GATE_EQ, uint32_t *back_ctl = nullptr,
-                       uint32_t back_slot = 0, float back_threshold = 0.0f, int back_may_continue = 0, const BfsBitsCtl *v2 = nullptr,
-                       const uint32_t *v2_indptr = nullptr, uint32_t v2_ncols = 0, uint32_t *v2_push_acc = nullptr, bool v2_deferred = false);
-int bool_plan_run_bits(gl_spmv_plan p, float *d_y, const uint32_t *run_flag, hipStream_t s, const uint32_t *xbits = nullptr);
+                       const BfsPullSchedule *sched = nullptr);
+int bool_plan_run_bits(gl_spmv_plan p, float *d_y, const uint32_t *run_flag, hipStream_t s);
 // gl_bfs_shard.h: one slot of the bit-frontier BFS schedule on a row shard in one launch
 struct BfsPushArgs;
 struct BfsShardArgs;
 int bool_plan_bfs_shard_step(gl_spmv_plan p, BfsPushArgs pa, BfsShardArgs sa, hipStream_t s);
-// gl_apply.hip: the set bits of d_bits[0..n) as a sparse list {row, 1} with head {count, 0}; no-op unless *gate_word == gate_value
-int bits_to_sparse_gated(const uint32_t *d_bits, uint32_t n, gl_idx_val *d_out, uint32_t *d_counts, const uint32_t *gate_word,
-                         uint32_t gate_value, hipStream_t s);
 uint32_t *bool_plan_xbits(gl_spmv_plan p);
 size_t bool_plan_xbits_bytes(gl_spmv_plan p);
 int spmv_run_general(gl_spmv_plan p, const float *d_x, const float *d_mask, float *d_y, int op, float zero, int mask_type,

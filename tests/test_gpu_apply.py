@@ -93,6 +93,43 @@ def test_assign_vector_sparse_new_frontier(gpu, inout_size, inf):
         mod.run(1.0)
 
 
+@pytest.mark.parametrize("cnt", [131072, 131073, 140000])
+def test_assign_vector_sparse_new_frontier_long_lists(gpu, cnt):
+    """The compaction on both sides of its 128-block limit (1024 candidates per block): 131 072 candidates are the longest
+    list whose counts the counting launch scans itself, 131 073 and 140 000 (129 and 137 blocks) have every writing block
+    add up the counts in front of it.  Twice on one module: the second run finds the ticket word and the counts as the
+    first one left them."""
+    mask = _strided_mask(2 * cnt, 0.5, 6)
+    assert int(mask["index"][0]) == cnt
+    inout = np.random.default_rng(7).integers(0, 10, size=2 * cnt).astype(np.float32)
+    ref = inout.copy()
+    ref_nf = O.assign_sparse_new_frontier(mask, ref)
+    assert 0.3 * cnt < int(ref_nf["index"][0]) < 0.7 * cnt     # about half of the candidates relax
+    mod = M.AssignVectorSparseModule(True)
+    mod.set_up_runtime()
+    mod.send_mask_host_to_device(mask)
+    for _ in range(2):
+        mod.send_inout_host_to_device(inout)
+        mod.run()
+        assert np.array_equal(mod.send_inout_device_to_host(), ref)
+        nf = mod.send_new_frontier_device_to_host()
+        n = int(nf["index"][0])
+        assert n == int(ref_nf["index"][0]) and nf["val"][0] == 0.0
+        assert np.array_equal(nf[:n + 1], ref_nf)
+
+
+@pytest.mark.parametrize("count", [0, 1, 255, 256, 257, 2048 * 256 + 3])
+def test_fill_u32(gpu, count):
+    """gl_buf_fill_u32 between two sentinel words: one thread per word up to 2048 blocks of 256, a grid-stride loop past that."""
+    sentinel, value = 0xdeadbeef, 0x01234567
+    whole = capi.DeviceBuffer.from_host(np.full(count + 2, sentinel, np.uint32))
+    capi.fill_u32(capi.DeviceBuffer(4 * count, ptr=whole.ptr + 4, keepalive=whole), value, count)
+    capi.sync()
+    got = whole.read(np.uint32, count + 2)
+    assert got[0] == sentinel and got[-1] == sentinel
+    assert np.all(got[1:-1] == value)
+
+
 def test_copy_buffer_bind_buffer(gpu):
     # TEST(CopyBufferBindBuffer, Basic) :209-261
     length = 128

@@ -211,6 +211,46 @@ def test_fused_bfs_pull_step_equals_the_three_calls(gpu, monkeypatch):
     assert not bits[(n + 31) // 32:].any() or np.all(bits[(n + 31) // 32:] == 0xFFFFFFFF)   # words past the rows untouched
 
 
+@pytest.mark.parametrize("segments", [1, 3], ids=["unsplit", "split"])
+def test_scheduled_pull_step_deferred(gpu, segments, monkeypatch):
+    """gl_bfs_bits_pull_step with bit 2 of may_continue (a row shard's step: no totals, no decision) in a slot that pulls, on an
+    unsplit plan (the fused epilogue) and on one cut into column segments (the claiming epilogue, which needs the next
+    frontier all zero on entry): distances and next frontier are the oracle's masked SpMV + assign, the control words are
+    left as they were but for the slot's mode record."""
+    from graphlily_amd import capi
+    set_knob(monkeypatch, "spmv_segments", segments)
+    m = datasets.rmat(30000, 500000, 17, True)
+    io.util_round_csr_matrix_dim(m, 128, 128)
+    m.adj_data = np.ones(m.nnz, np.float32)
+    n = m.num_rows
+    plan = capi.SpMVPlan(n, n, m.adj_indptr, m.adj_indices, m.adj_data, flags=capi.GL_PLAN_BOOLEAN)
+    assert (plan.info()["segments"] > 1) == (segments > 1)
+    csc = io.csr2csc(m)
+    csc_plan = capi.SpMSpVPlan(n, n, csc.adj_indptr, csc.adj_indices, csc.adj_data)
+    rng = np.random.default_rng(2)
+    x = (rng.random(n) < 0.02).astype(np.float32)
+    dist = np.where(rng.random(n) < 0.3, np.float32(2.0), np.float32(0.0)).astype(np.float32)
+    words = plan.bits_words()
+    ctl_words = 24
+    ctl = np.zeros(ctl_words, np.uint32)          # as gl_bfs_bits_begin(first_pull_slot = 0) leaves them: every slot pulls
+    ctl[4], ctl[15] = 0xffffffff, ctl_words
+    d_ctl, dx, dd = capi.DeviceBuffer.from_host(ctl), capi.DeviceBuffer.from_host(x), capi.DeviceBuffer.from_host(dist)
+    b_in, b_out = capi.DeviceBuffer.from_host(np.zeros(words, np.uint32)), capi.DeviceBuffer.from_host(np.zeros(words, np.uint32))
+    capi.pack_bits(dx, n, b_in)
+    capi.bfs_bits_pull_step(plan, csc_plan, b_in, b_out, dd, 5.0, d_ctl, 1, -1.0, 4 | 2, 0.0)
+    capi.sync()
+    y = O.spmv(to_oracle(m), x, 1, 0.0, dist, O.WRITETOZERO)
+    assert y.any() and not y.all()
+    want_dist = dist.copy()
+    want_dist[y != 0] = 5.0
+    assert np.array_equal(dd.read(np.float32, n), want_dist)
+    bits = b_out.read(np.uint32, words)
+    got_front = ((bits[np.arange(n) >> 5] >> (np.arange(n) & 31).astype(np.uint32)) & 1).astype(np.float32)
+    assert np.array_equal(got_front, y) and not bits[(n + 31) // 32:].any()
+    ctl[16 + (ctl_words - 16) // 2 + 1] = 2       # the record of how slot 1 was evaluated: streamed row-wise
+    assert np.array_equal(d_ctl.read(np.uint32, ctl_words), ctl)
+
+
 @pytest.mark.parametrize("name", ["rmat_sym_50K", "uniform_10K_10"])
 def test_bfs_pull_push_device_loop_equals_host_loop(gpu, name, monkeypatch):
     """pull_push with the direction decided on the device (no read-back per iteration; the schedule is

@@ -163,8 +163,8 @@ def test_plan_run_under_every_form_equals_the_oracle(gpu, kind, shape, keep, mon
 
 # ------------------------------------------------------------------ BFS on the square graph
 @functools.lru_cache(maxsize=None)
-def _bfs_reference():
-    g = square().m
+def _bfs_reference(kind):
+    g = square(kind).m
     om = to_oracle(g.copy())
     O.util_round_csr_matrix_dim(om, 128, 128)
     om.adj_data = np.ones(om.nnz, np.float32)
@@ -173,9 +173,9 @@ def _bfs_reference():
     return ref
 
 
-def _square_facts(monkeypatch, blocks, segments=1, r0=0, r1=None):
+def _square_facts(monkeypatch, blocks, segments=1, r0=0, r1=None, kind="wide"):
     """Preconditions on the square graph's plan (or a row shard's), as the BFS driver formats it."""
-    g = square().m
+    g = square(kind).m
     _knobs(monkeypatch, blocks, segments, 0)
     p = capi.SpMVPlan(g.num_rows, g.num_cols, g.adj_indptr, g.adj_indices, np.ones(g.nnz, np.float32), r0, g.num_rows if r1 is None else r1,
                       flags=capi.GL_PLAN_BOOLEAN | capi.GL_PLAN_NO_MULADD)
@@ -204,7 +204,7 @@ def _bfs(g, comm=None):
 def test_bfs_on_the_wide_square_graph(gpu, knob, keep, monkeypatch):
     """app.BFS pull / push / pull_push on the square `wide` graph (the fused pull epilogue, FUSED == 1): the oracle's levels under
     every knob; with bool_keep=1 the pull once more (KEEP 1 / 7)."""
-    ref = _bfs_reference()
+    ref = _bfs_reference("wide")
     f, info = _square_facts(monkeypatch, SQUARE_BLOCKS)
     assert_wide_preconditions(f, "square")
     assert f["interior_padding"] and info["segments"] == 1
@@ -232,7 +232,7 @@ def test_shard_steps_on_the_wide_square_graph(gpu, world, segments, monkeypatch)
     """Every rank of a row-sharded BFS on the 10-bit stream (bool_compress=3): the one-launch shard step (launch_shard_step<1, 6>)
     and, on shard plans cut into column segments, the claiming epilogue of the bit-frontier schedule (FUSED == 2).  One rank at a
     time on one GPU, the exchange emulated from a whole-matrix run; every rank's levels equal the oracle's."""
-    ref = _bfs_reference()
+    ref = _bfs_reference("wide")
     g = square().m
     per = SQUARE_BLOCKS // world
     _knobs(monkeypatch, SQUARE_BLOCKS, 1, 3)
@@ -254,6 +254,32 @@ def test_shard_steps_on_the_wide_square_graph(gpu, world, segments, monkeypatch)
             assert (r0, r1) == (b.r0_, b.r1_)
             assert np.array_equal(got, ref[r0:r1]), "rank %d/%d %s: %d rows differ" % (k, world, mode, int((got != ref[r0:r1]).sum()))
         del b
+
+
+@pytest.mark.parametrize("segments", [1, 3], ids=["unsplit", "split"])
+@pytest.mark.parametrize("keep", [0, 1], ids=["keep0", "keep1"])
+@pytest.mark.parametrize("kind,knob,form", [("wide", 0, 0), ("narrow", 1, 1), ("wide", 3, 2)], ids=["raw", "8bit", "10bit"])
+def test_shard_step_under_every_coding_and_cache_hint(gpu, kind, knob, form, keep, segments, monkeypatch):
+    """The one-launch shard step's streaming pull under each stream coding, both cache-hint twins and both epilogues
+    (launch_shard_step<1 / 2, KEEP 0 .. 7>: the sharded tests above and in test_gpu_bfs_sharded.py leave bool_keep to the plan's
+    size, which is never the keeping twin's, and the 8-bit coding to the graph): rank 1 of 4 pulls in every slot."""
+    world, k = 4, 1
+    ref = _bfs_reference(kind)
+    g = square(kind).m
+    per = SQUARE_BLOCKS // world
+    _knobs(monkeypatch, SQUARE_BLOCKS, 1, knob)
+    whole = _bfs(g)       # (the exchange is emulated from this run's bit vectors)
+    assert np.array_equal(whole.pull(0, BFS_ITERS), ref)
+    f, info = _square_facts(monkeypatch, per, segments, k * g.num_rows // world, (k + 1) * g.num_rows // world, kind)
+    assert expected_form(f["bad"], f["wide"], knob) == form and (info["segments"] > 1) == (segments > 1), (f, info)
+    _knobs(monkeypatch, per, segments, knob, keep)
+    b = _rank(g, k, world, whole)
+    assert (b.SpMV_.plan_.info()["segments"] > 1) == (segments > 1)
+    _assert_stream_form(b.SpMV_.plan_, form)
+    got = b.pull(0, BFS_ITERS)
+    r0, r1 = b.result_range_
+    assert (r0, r1) == (b.r0_, b.r1_) == (k * g.num_rows // world, (k + 1) * g.num_rows // world)
+    assert np.array_equal(got, ref[r0:r1]), "%d rows differ" % int((got != ref[r0:r1]).sum())
 
 
 def test_spmspv_row_wise_leg_on_the_10_bit_stream(gpu, monkeypatch):
