@@ -629,3 +629,18 @@ def test_label_propagation_modularity_is_unchanged():
     d.graph_, d.degrees_, d.labels_ = sym, pattern_degrees(sym), lab
     groups = [set(g) for g in _communities(lab, 34)]
     assert abs(d.modularity() - nx.algorithms.community.modularity(G, groups)) < 1e-12 and d.modularity() == modularity_of(sym, lab)
+
+
+def test_walk_stars_the_last_entry_of_every_hub_row_decides():
+    """the inputs of tests/test_gpu_walk.py::test_louvain_move: with the chosen weight every hub with two leaves or more joins its
+    highest leaf in sweep 1; without the hub's last entry and its mirror it joins its first leaf -- a walk that does not sum
+    that entry cannot give the expected labels"""
+    from test_gpu_walk import DEGREES, _stars, louvain_stars, star_hubs
+    hubs = star_hubs(2)
+    last = _stars()[4][np.asarray(DEGREES)[np.asarray(DEGREES) > 0] >= 2]
+    for packed in (False, True):
+        sym, weights, colors, heavy, first, full = louvain_stars(packed)
+        assert heavy == 2 and int(weights.max()) == 2 and np.count_nonzero(weights == 2) == 2 * 17
+        assert np.array_equal(first[0][hubs], last) and np.array_equal(full[0][hubs], last) and first[1] == 1 and full[4] == 1
+        less = louvain_stars(packed, "last")
+        assert int(less[1].max()) == 1 and np.array_equal(less[4][0][hubs], hubs + 1) and np.array_equal(less[5][0][hubs], hubs + 1)

@@ -465,3 +465,20 @@ def test_cpp_driver_compiles_and_fails_loudly_without_gpu(tmp_path):
         r = subprocess.run([LPA_DRIVER, str(tmp_path / "none.npz"), str(tmp_path)], capture_output=True, text=True)
         assert r.returncode != 0
         assert "gl_init" in r.stdout + r.stderr       # print-and-exit convention of the reference
+
+
+def test_walk_stars_the_last_entry_of_every_hub_row_decides():
+    """the inputs of tests/test_gpu_walk.py::test_lpa: without the hub's last entry and its mirror every hub with two leaves or
+    more ends on another label, under both colourings -- a walk that does not count that entry cannot give the expected labels"""
+    from test_gpu_walk import N, _stars, _star_members, lpa_stars, star_hubs
+    members, highest = _star_members()
+    hubs = star_hubs(2)
+    for packed in (False, True):
+        sym, colors, init, (lab, sweeps, changes, evals, converged) = lpa_stars(packed)
+        assert same_label_edges(sym, colors) == 0 and is_fixed_point(sym, lab)      # a proper colouring
+        assert np.array_equal(lab[members], highest) and np.array_equal(np.delete(lab, members), np.delete(np.arange(N), members))
+        assert (sweeps, converged) == (2, 1)
+        once = propagate(sym, colors, init, 1)[0]
+        assert np.array_equal(once, lab)                                 # (sweep 1 decides everything)
+        less = lpa_stars(packed, "last")[3][0]
+        assert np.all(less[hubs] != lab[hubs]) and np.all(less[hubs] == hubs + 2)      # one of each: the smallest label

@@ -412,3 +412,19 @@ def test_cpp_driver_compiles_and_fails_loudly_without_gpu(tmp_path):
         r = subprocess.run([MATCH_DRIVER, str(tmp_path / "none.npz"), str(tmp_path)], capture_output=True, text=True)
         assert r.returncode != 0
         assert "gl_init" in r.stdout + r.stderr       # print-and-exit convention of the reference
+
+
+def test_walk_stars_one_entry_of_every_hub_row_decides():
+    """the inputs of tests/test_gpu_walk.py::test_match: with the hub's last entry (ascending weights) or its first (descending)
+    and the mirror removed, every hub with two leaves or more is matched to somebody else -- a walk that skips that entry cannot
+    give the expected mates; and the closed forms of the whole graph"""
+    from test_gpu_walk import DEGREES, N, _stars, match_stars, star_hubs
+    hubs, last = star_hubs(1), _stars()[4]
+    two = np.asarray(DEGREES)[np.asarray(DEGREES) > 0] >= 2
+    for ascending, drop in ((True, "last"), (False, "first")):
+        sym, want, rounds, scans = match_stars(ascending)
+        partner = last if ascending else hubs + 1
+        assert np.array_equal(want, mate_of_pairs(N, hubs, partner)) and (rounds, scans) == (2, 2536 + 2519 - 17)
+        less = match_stars(ascending, drop)
+        assert less[0].nnz == sym.nnz - 2 * 17 and np.all(less[1][hubs[two]] != partner[two]) and np.all(less[1][hubs[two]] != FREE)
+        assert np.all(less[1][partner] == FREE) and less[3] < scans

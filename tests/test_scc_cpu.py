@@ -437,3 +437,30 @@ def test_cpp_driver_compiles_and_fails_loudly_without_gpu(tmp_path):
         r = subprocess.run([SCC_DRIVER, str(tmp_path / "none.npz"), str(tmp_path)], capture_output=True, text=True)
         assert r.returncode != 0
         assert "gl_init" in r.stdout + r.stderr       # print-and-exit convention of the reference
+
+
+def test_walk_stars_the_last_entry_of_every_hub_row_decides():
+    """the inputs of tests/test_gpu_walk.py::test_scc_*: without the last entry of the hub's long row (and its mirror in the other
+    plan) the hub and its highest leaf are no component any more, in every variant -- a walk that skips that entry cannot give the
+    expected labels; the loops change nothing the model sees; and the closed forms of the whole graph"""
+    from test_gpu_walk import DEGREES, N as n, _stars, scc_stars, star_hubs
+    hubs, last = star_hubs(1), _stars()[4]
+    want = np.arange(n)
+    want[last] = hubs
+    for kind in ("in", "out"):
+        for prio in (False, True):
+            cin, cout, p, (lab, comps, passes, trimmed, _) = scc_stars(kind, False, prio)
+            assert np.array_equal(lab, want) and (comps, passes, trimmed) == (n - 17, 1, 2519 - 17 + 24)
+            assert np.array_equal(lab, scipy_labels(n, *app._edges_of_pattern(cin, n))[0])
+            looped = scc_stars(kind, True, prio)
+            assert looped[3][1:] == (comps, passes, trimmed, scc_stars(kind, False, prio)[3][4]) and np.array_equal(looped[3][0], lab)
+            assert looped[0].nnz == cin.nnz + 2519 == looped[1].nnz
+            long_rows = np.diff((looped[0] if kind == "in" else looped[1]).adj_indptr.astype(np.int64))[_stars()[3]]
+            assert np.array_equal(long_rows, DEGREES)                      # (the loops are in the leaves' rows only)
+            less = scc_stars(kind, False, prio, "last")[3]
+            assert np.array_equal(less[0], np.arange(n)) and less[1:4] == (n, 0, n)
+    cin, cout, p, (lab, comps, passes, trimmed, _) = scc_stars("sym", False, True)
+    hub_of = _stars()[2]
+    assert cout is None and np.array_equal(lab, np.where(hub_of >= 0, hub_of, np.arange(n))) and (comps, passes, trimmed) == (18 + 23, 1, 24)
+    less = scc_stars("sym", False, True, "last")[3][0]
+    assert np.all(less[last] == last) and np.all(lab[last] == hubs)
