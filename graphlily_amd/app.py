@@ -1378,6 +1378,124 @@ class HipBackend:
         capi.sync()
 
 
+def _mirror_entries(indptr, indices, n):
+    """-> (rows, cols, mirror), int64 each: for every entry j = (v, u) of a symmetric matrix with ascending rows the number of the
+    entry (u, v)"""
+    ip = np.asarray(indptr).astype(np.int64)
+    rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(ip[:n + 1]))
+    cols = np.asarray(indices[:ip[n]]).astype(np.int64)
+    return rows, cols, np.searchsorted(rows * n + cols, cols * n + rows)
+
+
+def _blocks_of(indptr, indices, n):
+    """The biconnected components of a symmetric simple graph with ascending rows, by Hopcroft and Tarjan's depth-first search
+    with a stack of edges (iterative, plain python; kept apart from the device's Tarjan-Vishkin: validate_biconnected checks one
+    with the other) -> int64[nnz]: for every entry the smallest entry number of its block, -1 for an entry (v, v)."""
+    ip = [int(x) for x in np.asarray(indptr).astype(np.int64)[:n + 1]]
+    rows, cols, mirror = _mirror_entries(indptr, indices, n)
+    cols_l, mirror_l = cols.tolist(), mirror.tolist()
+    label = np.full(cols.shape[0], -1, dtype=np.int64)
+    disc, low, via, nxt = [-1] * n, [0] * n, [-1] * n, ip[:n]
+    clock, edges = 0, []
+    for s in range(n):
+        if disc[s] != -1 or ip[s] == ip[s + 1]:
+            continue
+        disc[s] = low[s] = clock
+        clock += 1
+        path = [s]
+        while path:
+            v = path[-1]
+            if nxt[v] < ip[v + 1]:
+                j = nxt[v]
+                nxt[v] += 1
+                u = cols_l[j]
+                if u == v or (via[v] >= 0 and j == mirror_l[via[v]]):
+                    continue
+                if disc[u] == -1:
+                    via[u] = j
+                    disc[u] = low[u] = clock
+                    clock += 1
+                    edges.append(j)
+                    path.append(u)
+                elif disc[u] < disc[v]:
+                    edges.append(j)
+                    low[v] = min(low[v], disc[u])
+            else:
+                path.pop()
+                if path:
+                    p = path[-1]
+                    low[p] = min(low[p], low[v])
+                    if low[v] >= disc[p]:
+                        cut = len(edges) - 1
+                        while edges[cut] != via[v]:
+                            cut -= 1
+                        members = np.array(edges[cut:], dtype=np.int64)
+                        del edges[cut:]
+                        both = np.concatenate([members, mirror[members]])
+                        label[both] = both.min()
+    return label
+
+
+def validate_biconnected(csr, block, vertex_blocks=None, edge_component=None):
+    """Host-side check that `block` are the biconnected components of the undirected simple graph of `csr` -- an edge {u, v} iff u
+    != v and a stored non-zero entry A[v, u] or A[u, v] exists -- one label per entry of io.symmetrize_simple(csr)[0], as
+    BiconnectedComponents.run() returns them: the smallest entry number of the entry's block.  Raises ValueError naming the first
+    offender and the rule; returns the number of blocks.  The rules:
+      1. the two entries of an edge agree;
+      2. a label is the smallest entry of its class: block[block[j]] == block[j] <= j;
+      3. the classes equal those of a host Hopcroft-Tarjan search (_blocks_of);
+      4. vertex_blocks[v] (optional) is the number of distinct labels in row v;
+      5. edge_component (optional) passes validate_components on the graph without its bridges, the blocks of a single edge.
+    `vertex_blocks` and `edge_component` may be longer than the matrix (the drivers pad it): the extra vertices are isolated."""
+    sym, _ = io.symmetrize_simple(csr)
+    b = np.asarray(block)
+    if b.ndim != 1 or b.shape[0] != sym.nnz:
+        raise ValueError("validate_biconnected: %d labels for the %d entries of the symmetric matrix" % (b.shape[0] if b.ndim == 1 else -1, sym.nnz))
+    b = b.astype(np.int64)
+    n, nnz = sym.num_rows, sym.nnz
+    rows, cols, mirror = _mirror_entries(sym.adj_indptr, sym.adj_indices, n)
+
+    def first(bad):
+        return int(np.flatnonzero(bad)[0])
+
+    if np.any(b != b[mirror]):
+        j = first(b != b[mirror])
+        raise ValueError("validate_biconnected: entry %d (%d, %d) is given block %d, its mirror entry %d block %d (rule 1)"
+                         % (j, rows[j], cols[j], b[j], mirror[j], b[mirror[j]]))
+    j_all = np.arange(nnz, dtype=np.int64)
+    if np.any((b < 0) | (b > j_all)):
+        j = first((b < 0) | (b > j_all))
+        raise ValueError("validate_biconnected: entry %d has label %d, which is no entry at or below it (rule 2)" % (j, b[j]))
+    if np.any(b[b] != b):
+        j = first(b[b] != b)
+        raise ValueError("validate_biconnected: entry %d has label %d, whose own label is %d (rule 2)" % (j, b[j], b[b[j]]))
+    want = _blocks_of(sym.adj_indptr, sym.adj_indices, n)
+    if np.any(want != b):
+        j = first(want != b)
+        raise ValueError("validate_biconnected: entry %d (%d, %d) is given block %d, a depth-first search finds its block's smallest entry to be %d "
+                         "(rule 3)" % (j, rows[j], cols[j], b[j], want[j]))
+    sizes = np.bincount(b, minlength=max(nnz, 1))
+    if vertex_blocks is not None:
+        vb = np.asarray(vertex_blocks).astype(np.int64)
+        if vb.ndim != 1 or vb.shape[0] < n:
+            raise ValueError("validate_biconnected: %d vertex_blocks for %d vertices" % (vb.shape[0] if vb.ndim == 1 else -1, n))
+        pairs = np.unique(rows * max(nnz, 1) + b)
+        distinct = np.bincount(pairs // max(nnz, 1), minlength=vb.shape[0])
+        if np.any(distinct != vb):
+            v = first(distinct != vb)
+            raise ValueError("validate_biconnected: vertex %d lies in %d blocks, vertex_blocks says %d (rule 4)" % (v, distinct[v], vb[v]))
+    if edge_component is not None:
+        keep = sizes[b] != 2
+        indptr = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(np.bincount(rows[keep], minlength=n), out=indptr[1:])
+        rest = io.CSRMatrix(n, n, np.ones(int(keep.sum()), dtype=np.float32), cols[keep].astype(np.uint32), indptr.astype(np.uint32))
+        try:
+            validate_components(rest, edge_component)
+        except ValueError as e:
+            raise ValueError("validate_biconnected: edge_component, on the graph without its bridges: %s (rule 5)" % e)
+    return int(np.count_nonzero(sizes))
+
+
 class ModuleCollection:
     def __init__(self):
         self.modules_ = []
@@ -2672,6 +2790,82 @@ class StronglyConnectedComponents(_PatternApp):
         np.cumsum(np.bincount(key // max(k, 1), minlength=k), out=indptr[1:])
         dag = io.CSRMatrix(k, k, np.ones(key.shape[0], dtype=np.float32), (key % max(k, 1)).astype(np.uint32), indptr.astype(np.uint32))
         return dag, rank
+
+
+class BiconnectedComponents(_PatternApp):
+    """Biconnected components: gl_bicc, Tarjan and Vishkin's algorithm over a deterministic BFS forest.  The
+    matrix is read as an undirected simple graph -- duplicates, the diagonal, zero-valued entries and direction are ignored, as in
+    KTruss -- and stored in both directions by the host (io.symmetrize_simple); that matrix is kept as graph_, and the block labels
+    have one word per ENTRY of it, aligned with graph_.adj_indices: both entries of an edge carry the same value."""
+    _no_shards_ = ("gl_bicc reads the level, the parent and the preorder number of every column of a row, so every rank would need "
+                   "the whole symmetric matrix")
+    degrees_ = graph_ = block_ = vertex_blocks_ = articulation_ = bridge_ = edge_component_ = None
+    num_blocks_ = num_articulation_ = num_bridges_ = num_trees_ = depth_ = launches_ = None
+    block_labels_ = block_sizes_ = largest_block_ = None
+
+    def _prepare(self, csr):
+        csr, self.degrees_ = io.symmetrize_simple(csr)
+        self.graph_ = csr
+        self.block_ = None
+        return csr
+
+    def run(self, edge_components=False):
+        """-> uint32[graph_.nnz]: block[j] = the smallest entry number of the block (biconnected component) that holds the edge of
+        entry j.  Leaves block_, vertex_blocks_ (uint32[n_]: the blocks a vertex belongs to; padding vertices are isolated: 0),
+        articulation_ (bool[n_]: two blocks or more), bridge_ (bool per entry: its block has two entries), edge_component_
+        (uint32[n_], the smallest vertex of every vertex's 2-edge-connected component, or None without edge_components=True),
+        num_blocks_, num_articulation_, num_bridges_, num_trees_ (over the real vertices), depth_ (the largest level of the BFS
+        forest), launches_, block_labels_ (ascending), block_sizes_ (edges per block, aligned with them) and largest_block_.  The
+        device's bridge and articulation counts must equal the ones derived from block_ and vertex_blocks_.  The call waits
+        for the device."""
+        self._require_sent()
+        B, n, nnz = self.backend, self.n_, self.graph_.nnz
+        room = max(1, nnz)
+        out = B.alloc(room + (2 * n if edge_components else n), np.float32)    # (32-bit words: block, vertex_blocks, edge_component)
+        stats = self.SpMV_.bicc(B.view(out, 0, room, 4), B.view(out, room, n, 4), B.view(out, room + n, n, 4) if edge_components else None)
+        B.sync()
+        got = B.download(out, np.uint32, room + (2 * n if edge_components else n))
+        self.block_ = got[:nnz]
+        self.vertex_blocks_ = got[room:room + n]
+        self.edge_component_ = got[room + n:] if edge_components else None
+        self.num_blocks_, self.num_articulation_, self.num_bridges_, self.depth_, self.launches_, trees = stats
+        self.num_trees_ = trees - (n - self.n_real_)
+        self.articulation_ = self.vertex_blocks_ >= 2
+        self.block_labels_, entries = np.unique(self.block_, return_counts=True)
+        self.block_sizes_ = (entries // 2).astype(np.int64)
+        self.largest_block_ = int(self.block_sizes_.max()) if entries.size else 0
+        per_label = np.zeros(room, dtype=np.int64)
+        per_label[self.block_labels_.astype(np.int64)] = entries
+        self.bridge_ = per_label[self.block_.astype(np.int64)] == 2
+        assert self.num_blocks_ == self.block_labels_.shape[0], (self.num_blocks_, self.block_labels_.shape[0])
+        assert self.num_bridges_ == int(np.count_nonzero(entries == 2)), (self.num_bridges_, int(np.count_nonzero(entries == 2)))
+        assert self.num_articulation_ == int(np.count_nonzero(self.articulation_)), (self.num_articulation_, int(np.count_nonzero(self.articulation_)))
+        return self.block_
+
+    def block_cut_tree(self):
+        """-> (CSRMatrix, block_rank, cut_rank): the forest between the blocks and the articulation points of the last run, on the
+        host (numpy) -- the counterpart of StronglyConnectedComponents.condensation().  The blocks are ranked by ascending label,
+        block_rank[l] = the rank of the block labelled l (uint32[graph_.nnz], 0xffffffff where l is no label): nodes 0 ..
+        num_blocks_ - 1; the articulation points follow in ascending vertex order, cut_rank[v] = the node of vertex v
+        (uint32[n_], 0xffffffff where v is none).  The matrix is symmetric and bipartite: an entry between a block and an
+        articulation point that belongs to it; rows ascending.  It is a forest: one tree per component with an edge."""
+        if self.block_ is None:
+            raise RuntimeError("BiconnectedComponents.block_cut_tree(): run() first")
+        n, nnz, k = self.n_, self.graph_.nnz, int(self.num_blocks_)
+        block_rank = np.full(nnz, 0xFFFFFFFF, dtype=np.uint32)
+        block_rank[self.block_labels_.astype(np.int64)] = np.arange(k, dtype=np.uint32)
+        cuts = np.flatnonzero(self.articulation_)
+        cut_rank = np.full(n, 0xFFFFFFFF, dtype=np.uint32)
+        cut_rank[cuts] = k + np.arange(cuts.shape[0], dtype=np.uint32)
+        nodes = k + cuts.shape[0]
+        rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(self.graph_.adj_indptr.astype(np.int64)))
+        at = self.articulation_[rows]
+        a, b = cut_rank[rows[at]].astype(np.int64), block_rank[self.block_.astype(np.int64)[at]].astype(np.int64)
+        key = np.unique(np.concatenate([a * max(nodes, 1) + b, b * max(nodes, 1) + a]))
+        indptr = np.zeros(nodes + 1, dtype=np.int64)
+        np.cumsum(np.bincount(key // max(nodes, 1), minlength=nodes), out=indptr[1:])
+        tree = io.CSRMatrix(nodes, nodes, np.ones(key.shape[0], dtype=np.float32), (key % max(nodes, 1)).astype(np.uint32), indptr.astype(np.uint32))
+        return tree, block_rank, cut_rank
 
 
 class BetweennessCentrality(_PatternApp):

@@ -58,7 +58,7 @@ EXT_EXPORTS = ["gl_color"]
 # tests check their own entry, build() checks every list against the library
 EXT_HEADERS = {"graphlily_hip_ext.h": EXT_EXPORTS, "graphlily_hip_truss.h": ["gl_truss"], "graphlily_hip_msf.h": ["gl_msf"],
                "graphlily_hip_match.h": ["gl_match"], "graphlily_hip_lpa.h": ["gl_lpa"],
-               "graphlily_hip_scc.h": ["gl_scc"], "graphlily_hip_louvain.h": ["gl_louvain_move"]}
+               "graphlily_hip_scc.h": ["gl_scc"], "graphlily_hip_louvain.h": ["gl_louvain_move"], "graphlily_hip_bicc.h": ["gl_bicc"]}
 
 
 class GraphLilyError(RuntimeError):
@@ -131,6 +131,7 @@ def lib():
         "gl_match": [vp, vp, vp, P(u64)],
         "gl_lpa": [vp, vp, vp, vp, u32, P(u64)],
         "gl_scc": [vp, vp, vp, vp, P(u64)],
+        "gl_bicc": [vp, vp, vp, vp, vp, P(u64)],
         "gl_louvain_move": [vp, vp, vp, vp, vp, u32, u64, P(u64)],
         "gl_bc_accumulate": [vp, vp, vp, vp, ctypes.c_double, i32, vp, P(u32)],
         "gl_spmv_run": [vp, vp, vp, vp, i32, f32, i32],
@@ -587,6 +588,19 @@ class SpMVPlan:
         garbage = 0xdeadbeefdeadbeef
         stats = (ctypes.c_uint64 * 5)(*([garbage] * 5))
         check(lib().gl_scc(ctypes.c_void_p(self.handle), ctypes.c_void_p(out.handle), _p(prio), _p(label), stats))
+        return tuple(int(x) for x in stats)
+
+    def bicc(self, block, vertex_blocks=None, edge_component=None, tree=None):
+        """gl_bicc: the biconnected components of this plan's graph (square, whole, rows strictly ascending sets, the pattern
+        symmetric: io.symmetrize_simple prepares it) -- block[j] = the smallest entry number of the block that holds entry j's
+        edge (nnz device words), and optionally vertex_blocks[v] = the blocks v belongs to (>= 2: an articulation point),
+        edge_component[v] = the smallest vertex of v's 2-edge-connected component (num_rows device words each) and `tree`, the
+        diagnostic copy of {level, parent, pre, nd, low, high} (6 num_rows device words) -> (blocks, articulation points,
+        bridges, depth, launches enqueued, trees).  Everything but `launches` is a function of the graph.  The call
+        SYNCHRONISES (it reads a control record back between batches of launches)."""
+        garbage = 0xdeadbeefdeadbeef
+        stats = (ctypes.c_uint64 * 6)(*([garbage] * 6))
+        check(lib().gl_bicc(ctypes.c_void_p(self.handle), _p(block), _p(vertex_blocks), _p(edge_component), _p(tree), stats))
         return tuple(int(x) for x in stats)
 
     def bc_accumulate(self, plan_out, level, bc, scale=1.0, accumulate=False, sigma=None, stats=True):

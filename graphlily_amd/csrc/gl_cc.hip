@@ -24,46 +24,17 @@
 //     that is no longer a root, which the compare-and-swap then refuses;
 //   * path shortening is atomicMin(&parent[x], grandparent) only, which keeps the invariant;
 //   * the only loops are the descending find and the retry.
-// Finish runs behind a launch boundary (plain loads): pointer doubling, ping-pong between parent and labels with one device
+// Finish runs behind a launch boundary (plain loads): pointer doubling (gl_unionfind.h, which holds it and the find / unite
+// above for gl_bicc.hip too), ping-pong between parent and labels with one device
 // "changed" word per round.  A round at least halves the depth, so ceil(log2 n) + 1 rounds suffice; that many are enqueued
 // and a round returns at once when its predecessor changed nothing (both arrays then hold the result).  A thread-per-vertex
 // walk to the root would not do: a path hooked in index order leaves a chain of length n.  One more pass counts the roots,
 // one ballot and one atomic add per wavefront.  No call synchronises with the host.
 // NO ROW SKIPPING: entries are stored one way only (row v lists the vertices v is pulled from), so a row skipped because its
 // vertex already sits in the giant component (Afforest's shortcut) may hold the only copy of an edge that leaves it.
-#include "gl_rounds.h"
+#include "gl_unionfind.h"
 
 namespace gl {
-
-constexpr uint32_t kCcMaxRounds = 36;      // ceil(log2 2^32) + 1, made odd, with room
-constexpr uint32_t kCcCtlBytes = 256;      // one "changed" word per finish round
-
-// the root below x (as far as this thread's loads can tell); every vertex passed on the way is pointed at its grandparent
-__device__ __forceinline__ uint32_t cc_find(uint32_t *parent, uint32_t x) {
-    uint32_t p = ga_load(parent + x);
-    while (p < x) {
-        const uint32_t g = ga_load(parent + p);
-        if (g < p) ga_min(parent + x, g);
-        x = p;
-        p = g;
-    }
-    return x;
-}
-
-// unite the components of a and b (a is an ancestor-or-self of the row's vertex); -> the row's new ancestor
-__device__ __forceinline__ uint32_t cc_unite(uint32_t *parent, uint32_t a, uint32_t b) {
-    for (;;) {
-        a = cc_find(parent, a);
-        b = cc_find(parent, b);
-        if (a == b) return a;
-        const uint32_t hi = max(a, b), lo = min(a, b);
-        uint32_t seen = hi;
-        if (ga_cas(parent + hi, seen, lo)) return lo;
-        // hi was hooked by somebody else meanwhile: go on from where it points now (seen < hi)
-        if (a == hi) a = seen;
-        else b = seen;
-    }
-}
 
 struct CcHookArgs {
     const uint32_t *row_ptr, *row_idx;
@@ -108,20 +79,6 @@ __global__ __launch_bounds__(256) void cc_begin_kernel(uint32_t *__restrict__ pa
     for (uint32_t v = blockIdx.x * 256u + threadIdx.x; v < n; v += gridDim.x * 256u) parent[v] = v;
 }
 
-// one round of pointer doubling: out[v] = in[in[v]]; changed[round] != 0 if some vertex moved.  A round whose predecessor
-// changed nothing returns at once: in == out already, element for element.
-__global__ __launch_bounds__(256) void cc_jump_kernel(const uint32_t *__restrict__ in, uint32_t *__restrict__ out, uint32_t n,
-                                                      uint32_t *__restrict__ changed, uint32_t round) {
-    if (round != 0u && changed[round - 1u] == 0u) return;
-    bool moved = false;
-    for (uint32_t v = blockIdx.x * 256u + threadIdx.x; v < n; v += gridDim.x * 256u) {
-        const uint32_t p = in[v], g = in[p];
-        out[v] = g;
-        moved |= g != p;
-    }
-    if (__any(moved) && (threadIdx.x & 63u) == 0u) atomicOr(changed + round, 1u);
-}
-
 __global__ __launch_bounds__(256) void cc_count_kernel(const uint32_t *__restrict__ labels, uint32_t n, uint32_t *__restrict__ count) {
     uint32_t roots = 0;   // per wavefront
     const uint32_t nround = (n + 255u) & ~255u;
@@ -130,14 +87,14 @@ __global__ __launch_bounds__(256) void cc_count_kernel(const uint32_t *__restric
     if ((threadIdx.x & 63u) == 0u && roots != 0u) atomicAdd(count, roots);
 }
 
-static int cc_begin(uint32_t *d_parent, uint32_t n) {
+int cc_begin(uint32_t *d_parent, uint32_t n) {
     if (!n) return GL_OK;
     cc_begin_kernel<<<rows_stream_grid(n), 256, 0, ctx().stream>>>(d_parent, n);
     GL_LAUNCH_CHECK();
     return GL_OK;
 }
 
-static int cc_hook(gl_spmv_plan p, uint32_t *d_parent) {
+int cc_hook(gl_spmv_plan p, uint32_t *d_parent) {
     const uint32_t rows = p->row_end - p->row_begin;
     if (!rows) return GL_OK;
     // A/B knobs (GRAPHLILY_DEBUG, read per call): cc_cut = entries a thread reads before the wavefront takes the row over,
@@ -161,21 +118,9 @@ static int cc_finish(uint32_t *d_parent, uint32_t n, uint32_t *d_labels, uint32_
     hipStream_t s = ctx().stream;
     if (d_count) GL_HIP(hipMemsetAsync(d_count, 0, 4, s));
     if (!n) return GL_OK;
-    uint32_t *&ctl = ctx().cc_ctl;
-    const int rc = plan_scratch(ctl, kCcCtlBytes, who, "control words");
+    const int rc = cc_double(d_parent, n, d_labels, who);
     if (rc != GL_OK) return rc;
-    GL_HIP(hipMemsetAsync(ctl, 0, kCcCtlBytes, s));
-    uint32_t rounds = 1;                      // ceil(log2 n) + 1 ...
-    while ((1ull << (rounds - 1u)) < n) rounds++;
-    rounds |= 1u;                             // ... made odd: the last round writes d_labels
-    static_assert(kCcMaxRounds * 4u <= kCcCtlBytes && kCcMaxRounds >= 33u, "one word per round");
     const unsigned grid = rows_stream_grid(n);
-    uint32_t *in = d_parent, *out = d_labels;
-    for (uint32_t r = 0; r < rounds; r++) {
-        cc_jump_kernel<<<grid, 256, 0, s>>>(in, out, n, ctl, r);
-        GL_LAUNCH_CHECK();
-        std::swap(in, out);
-    }
     if (d_count) {
         cc_count_kernel<<<grid, 256, 0, s>>>(d_labels, n, d_count);
         GL_LAUNCH_CHECK();

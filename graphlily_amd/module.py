@@ -394,6 +394,21 @@ class SpMVModule(BaseModule):
         self._finish(label_buf)
         return stats
 
+    def bicc(self, block_buf, vertex_blocks_buf=None, edge_component_buf=None, tree_buf=None):
+        """Extension (gl_bicc): the biconnected components of this module's matrix, read as an undirected simple graph -- rows as
+        strictly ascending sets N(v), the pattern symmetric -- into `block_buf` (get_nnz() words, aligned with the matrix's
+        entries: the smallest entry number of the block of every entry's edge) and, optionally, `vertex_blocks_buf` (the blocks
+        a vertex belongs to; >= 2: an articulation point), `edge_component_buf` (the smallest vertex of its 2-edge-connected
+        component; get_num_rows() words each) and `tree_buf` (6 get_num_rows() words: level, parent, pre, nd, low, high) ->
+        (blocks, articulation points, bridges, depth, launches, trees).  The call synchronises.  Raises GraphLilyError
+        (GL_ERR_UNSUPPORTED) when the plan keeps no row copy (only the (||,&&) layout does), is not square, is a row shard, or
+        its rows are no strictly ascending sets or its pattern is not symmetric (io.symmetrize_simple prepares the matrix)."""
+        if self.plan_ is None:
+            _fatal("SpMVModule.bicc: send_matrix_host_to_device first")
+        stats = self.plan_.bicc(block_buf, vertex_blocks_buf, edge_component_buf, tree_buf)
+        self._finish(block_buf, vertex_blocks_buf, edge_component_buf, tree_buf)
+        return stats
+
     def bc_accumulate(self, out_module, level_buf, bc_buf, scale=1.0, accumulate=False, sigma_buf=None, stats=True):
         """Extension (gl_bc_accumulate): adds scale x Brandes' dependency of the search whose levels are in `level_buf`
         (get_num_rows() floats) to `bc_buf` (as many doubles; accumulate=False: overwrites it).  This module's matrix is the

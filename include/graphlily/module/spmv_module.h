@@ -17,6 +17,7 @@
 #include "graphlily_hip_lpa.h"
 #include "graphlily_hip_louvain.h"
 #include "graphlily_hip_scc.h"
+#include "graphlily_hip_bicc.h"
 #include "graphlily/io/data_formatter.h"
 #include "graphlily/io/data_loader.h"
 #include "graphlily/module/base_module.h"
@@ -283,6 +284,18 @@ public:
     void scc(SpMVModule *out, DeviceBuffer label, const uint32_t *prio = nullptr, uint64_t *stats = nullptr) {
         barrier_();
         GRAPHLILY_CHECK(gl_scc(plan_, out ? out->plan_ : plan_, prio, (uint32_t *)label.ptr(), stats));
+        finish_();
+    }
+    // extension (gl_bicc, graphlily_hip_bicc.h): the biconnected components of this module's matrix, read as an undirected simple
+    // graph -- the (||,&&) layout, rows strictly ascending sets, the pattern symmetric (graphlily::io::util_symmetrize_simple
+    // prepares it) -- into `block` (get_nnz() device words, aligned with the matrix's entries: the smallest entry number of the block
+    // of every entry's edge), `vertex_blocks` (get_num_rows() device words: the blocks a vertex belongs to, >= 2 for an articulation
+    // point) and `edge_component` (as many: the smallest vertex of its 2-edge-connected component); the last two may be empty
+    // buffers (a null pointer: not wanted).  stats (optional, 6 host words) receives {blocks, articulation points, bridges, depth,
+    // launches, trees}.  The call synchronises.
+    void bicc(DeviceBuffer block, DeviceBuffer vertex_blocks, DeviceBuffer edge_component, uint64_t *stats = nullptr) {
+        barrier_();
+        GRAPHLILY_CHECK(gl_bicc(plan_, (uint32_t *)block.ptr(), (uint32_t *)vertex_blocks.ptr(), (uint32_t *)edge_component.ptr(), nullptr, stats));
         finish_();
     }
     // extension (gl_bc_accumulate): adds scale x Brandes' dependency of the search whose levels are in `level` (get_num_rows()
