@@ -1496,6 +1496,131 @@ def validate_biconnected(csr, block, vertex_blocks=None, edge_component=None):
     return int(np.count_nonzero(sizes))
 
 
+def _f32_keys(values):
+    """-> uint64: the monotone map of the f32 bits (gl_msf.hip's key), which orders non-NaN floats as < does"""
+    bits = np.ascontiguousarray(values, dtype=np.float32).view(np.uint32).astype(np.uint64)
+    return np.where(bits >> np.uint64(31) != 0, bits ^ np.uint64(0xFFFFFFFF), bits ^ np.uint64(0x80000000))
+
+
+def _concat_ranges(start, length):
+    """-> int64: start[0] .. start[0] + length[0] - 1, start[1] .. , ... in one array"""
+    length = np.asarray(length, np.int64)
+    total = int(length.sum())
+    first = np.cumsum(length) - length
+    return np.arange(total, dtype=np.int64) + np.repeat(np.asarray(start, np.int64) - first, length)
+
+
+def _topological_of(n, src, dst, w=None):
+    """Kahn's peeling, a whole level at a time in numpy, of the edges src[i] -> dst[i] (simple: no loops, no duplicates) with the
+    f32 weights w[i] -> (level uint32[n], dist float32[n] or None, parent uint32[n] or None): gl_topo's definitions -- level =
+    the edges of the longest path that ends in the vertex, 0xffffffff on a cycle or behind one; dist = the largest f32 dist[u] +
+    w over the predecessors, +0 on a source, the bits 0x7fc00000 when unpeeled; parent = the smallest u that attains it."""
+    src, dst = np.asarray(src, np.int64), np.asarray(dst, np.int64)
+    by_in = np.lexsort((src, dst))
+    in_src = src[by_in]
+    in_w = None if w is None else np.asarray(w, np.float32)[by_in]
+    in_ptr = np.concatenate([[0], np.cumsum(np.bincount(dst, minlength=n))]).astype(np.int64)
+    by_out = np.argsort(src, kind="stable")
+    out_dst = dst[by_out]
+    out_ptr = np.concatenate([[0], np.cumsum(np.bincount(src, minlength=n))]).astype(np.int64)
+    pending = np.diff(in_ptr)
+    level = np.full(n, 0xFFFFFFFF, dtype=np.uint32)
+    dist = parent = None
+    if w is not None:
+        dist = np.full(n, 0x7FC00000, dtype=np.uint32).view(np.float32)
+        parent = np.full(n, 0xFFFFFFFF, dtype=np.uint32)
+    front = np.flatnonzero(pending == 0)
+    lvl = 0
+    while front.size:
+        level[front] = lvl
+        if w is not None:
+            dist[front] = 0.0
+            fed = front[in_ptr[front + 1] > in_ptr[front]]
+            if fed.size:
+                lens = in_ptr[fed + 1] - in_ptr[fed]
+                e = _concat_ranges(in_ptr[fed], lens)
+                with np.errstate(over="ignore"):
+                    cand = (dist[in_src[e]] + in_w[e]).astype(np.float32)
+                word = (_f32_keys(cand) << np.uint64(32)) | (np.uint64(0xFFFFFFFF) - in_src[e].astype(np.uint64))
+                best = np.maximum.reduceat(word, np.cumsum(lens) - lens)
+                key = (best >> np.uint64(32)).astype(np.uint32)
+                dist[fed] = np.where(key >> 31 != 0, key ^ np.uint32(0x80000000), ~key).view(np.float32)
+                parent[fed] = (np.uint64(0xFFFFFFFF) - (best & np.uint64(0xFFFFFFFF))).astype(np.uint32)
+        e = _concat_ranges(out_ptr[front], out_ptr[front + 1] - out_ptr[front])
+        hit = np.bincount(out_dst[e], minlength=n)
+        pending -= hit
+        front = np.flatnonzero((hit > 0) & (pending == 0))
+        lvl += 1
+    return level, dist, parent
+
+
+def validate_topological(csr, level, dist=None, parent=None, weighted=False):
+    """Host-side check (numpy) that `level` -- and, with weighted=True, `dist` and `parent` -- are gl_topo's results on the directed
+    graph of `csr` as io.directed_weighted(csr, weighted) reads it: an edge u -> v for a stored entry A[v, u], u != v (unweighted:
+    a stored NON-ZERO entry).  Raises ValueError with the message of the first violation, naming the offender and the rule;
+    returns the number of peeled vertices among those `level` covers.  The rules:
+      1. every edge into a peeled vertex comes from a peeled vertex of a lower level;
+      2. a peeled vertex without predecessors has level 0, every other one a predecessor exactly one level below;
+      3. every unpeeled vertex (level 0xffffffff) has an unpeeled predecessor: it lies on a cycle or behind one;
+      4. level, dist and parent equal the host loop's (Kahn's peeling a level at a time; dist and parent to the bit).
+    The arrays may be longer than the matrix (the drivers pad it): the extra vertices are isolated."""
+    nr, nc = int(csr.num_rows), int(csr.num_cols)
+    lev = np.asarray(level).astype(np.int64)
+    n = lev.shape[0]
+    if lev.ndim != 1 or n < max(nr, nc):
+        raise ValueError("validate_topological: %d levels for a %d x %d matrix" % (n, nr, nc))
+    if weighted and (dist is None or parent is None):
+        raise ValueError("validate_topological: weighted=True needs dist and parent")
+
+    def first(bad):
+        return int(np.flatnonzero(bad)[0])
+
+    g = io.directed_weighted(csr, weighted)[0]
+    dst = np.repeat(np.arange(g.num_rows, dtype=np.int64), np.diff(g.adj_indptr.astype(np.int64)))
+    src = g.adj_indices.astype(np.int64)
+    none = 0xFFFFFFFF
+    peeled = lev != none
+    into = peeled[dst]
+    bad = into & (~peeled[src] | (lev[src] >= lev[dst]))
+    if np.any(bad):
+        k = first(bad)
+        raise ValueError("validate_topological: the edge %d -> %d goes from level %s to level %d (rule 1)"
+                         % (src[k], dst[k], "none" if lev[src[k]] == none else str(lev[src[k]]), lev[dst[k]]))
+    has_pred = np.zeros(n, dtype=bool)
+    has_pred[dst] = True
+    below = np.zeros(n, dtype=bool)
+    below[dst[into & (lev[src] + 1 == lev[dst])]] = True
+    bad = peeled & ((~has_pred & (lev != 0)) | (has_pred & ~below))
+    if np.any(bad):
+        k = first(bad)
+        raise ValueError("validate_topological: vertex %d has level %d and %s (rule 2)"
+                         % (k, lev[k], "a predecessor one level below is missing" if has_pred[k] else "no predecessor"))
+    waits = np.zeros(n, dtype=bool)
+    waits[dst[~peeled[src]]] = True
+    bad = ~peeled & ~waits
+    if np.any(bad):
+        k = first(bad)
+        raise ValueError("validate_topological: vertex %d is not peeled and has no unpeeled predecessor (rule 3)" % k)
+    w = g.adj_data if weighted else None
+    want_level, want_dist, want_parent = _topological_of(n, src, dst, w)
+    if not np.array_equal(want_level, lev.astype(np.uint32)):
+        k = first(want_level != lev.astype(np.uint32))
+        raise ValueError("validate_topological: vertex %d has level %d, the host loop gives %d (rule 4)" % (k, lev[k], want_level[k]))
+    if weighted:
+        got_dist = np.ascontiguousarray(dist, dtype=np.float32).view(np.uint32)
+        got_parent = np.asarray(parent).astype(np.uint32)
+        if got_dist.shape != (n,) or got_parent.shape != (n,):
+            raise ValueError("validate_topological: dist and parent must have %d words, as level" % n)
+        if not np.array_equal(got_dist, want_dist.view(np.uint32)):
+            k = first(got_dist != want_dist.view(np.uint32))
+            raise ValueError("validate_topological: vertex %d has dist %r (bits 0x%08x), the host loop gives %r (rule 4)"
+                             % (k, float(got_dist[k:k + 1].view(np.float32)[0]), got_dist[k], float(want_dist[k])))
+        if not np.array_equal(got_parent, want_parent):
+            k = first(got_parent != want_parent)
+            raise ValueError("validate_topological: vertex %d has parent %d, the host loop gives %d (rule 4)" % (k, got_parent[k], want_parent[k]))
+    return int(np.count_nonzero(peeled))
+
+
 class ModuleCollection:
     def __init__(self):
         self.modules_ = []
@@ -2866,6 +2991,127 @@ class BiconnectedComponents(_PatternApp):
         np.cumsum(np.bincount(key // max(nodes, 1), minlength=nodes), out=indptr[1:])
         tree = io.CSRMatrix(nodes, nodes, np.ones(key.shape[0], dtype=np.float32), (key % max(nodes, 1)).astype(np.uint32), indptr.astype(np.uint32))
         return tree, block_rank, cut_rank
+
+
+class TopologicalOrder(_PatternApp):
+    """Topological levels, a topological order and the critical path: gl_topo, Kahn's peeling with dependency
+    counters over the pattern and its transpose.  The matrix is read as a DIRECTED graph (io.directed_weighted: an edge u -> v for
+    a stored entry A[v, u], u != v; weighted=False is io.simple_pattern's reading, weighted=True keeps every stored entry with the
+    largest of its values, -0.0 as +0.0, NaN and inf refused); the transposed pattern lives in a second boolean SpMVModule, out_,
+    which exists only when the pattern is not symmetric.  Both plans are built from ones (the row copy would store a zero value
+    as no entry); the weights travel in buffers of their own, aligned with graph_.adj_indices and graph_out_.adj_indices.
+    load_and_format_matrix accepts a path or a CSRMatrix, so StronglyConnectedComponents.condensation()'s matrix goes straight in.
+    On a cyclic input the peeled vertices are those that are neither on a cycle nor behind one."""
+    _no_shards_ = ("gl_topo decrements the counter of every column of a row of the transposed pattern and reads the distance of "
+                   "every column of a row of the pattern, so every rank would need both whole patterns and every counter")
+    graph_ = graph_out_ = symmetric_ = weight_buf_ = weight_out_buf_ = None
+    level_ = is_dag_ = num_peeled_ = cyclic_ = num_levels_ = level_sizes_ = widest_ = launches_ = None
+    dist_ = parent_ = critical_length_ = order_ = position_ = None
+    weighted_ = False
+
+    def __init__(self, num_channels=M.num_hbm_channels, spmv_out_buf_len=0, vec_buf_len=0, comm=None, backend=None):
+        _PatternApp.__init__(self, num_channels, spmv_out_buf_len, vec_buf_len, comm, backend)
+        self.buf_lens_ = (spmv_out_buf_len, vec_buf_len)
+        self.out_ = None                 # the transposed pattern's module (a pattern that is not symmetric)
+
+    @staticmethod
+    def _ones_of(g):
+        return io.CSRMatrix(g.num_rows, g.num_cols, np.ones(g.nnz, dtype=np.float32), g.adj_indices, g.adj_indptr)
+
+    def _prepare(self, csr):
+        self.graph_, self.graph_out_, self.symmetric_ = io.directed_weighted(csr, self.weighted_)      # (after padding)
+        self.level_ = self.dist_ = self.parent_ = self.order_ = self.position_ = None
+        self.weight_buf_ = self.weight_out_buf_ = None
+        return self._ones_of(self.graph_)
+
+    def load_and_format_matrix(self, src, skip_empty_rows=True, weighted=False):
+        self.weighted_ = bool(weighted)
+        _PatternApp.load_and_format_matrix(self, src, skip_empty_rows)
+        self.modules_ = [self.SpMV_]
+        self.out_ = None
+        if not self.symmetric_:
+            self.out_ = self.backend.SpMVModule(self.num_channels_, *self.buf_lens_)
+            self.out_.set_semiring(M.LogicalSemiring)
+            self.out_.set_mask_type(M.kNoMask)
+            self.out_.blocking = False
+            self.out_.load_and_format_matrix(self._ones_of(self.graph_out_), skip_empty_rows)
+            self.add_module(self.out_)
+
+    def send_matrix_host_to_device(self):
+        _PatternApp.send_matrix_host_to_device(self)
+        if self.out_ is not None:
+            self.out_.send_matrix_host_to_device()
+        if self.weighted_:
+            for name, g in (("weight_buf_", self.graph_), ("weight_out_buf_", self.graph_out_)):
+                buf = self.backend.alloc(max(1, g.nnz), np.float32)
+                if g.nnz:
+                    self.backend.upload(buf, g.adj_data)
+                setattr(self, name, buf)
+
+    def run(self, reverse=False, order=False):
+        """-> uint32[n_]: level[v] = the edges of the longest path that ends in v, 0xffffffff for a vertex on a cycle or behind
+        one (padding vertices are isolated: level 0).  reverse=True swaps the two plans: HEIGHTS, the longest path that starts
+        in v, and (weighted) the distance to a sink with the successor tree.  Leaves level_, launches_ and, over the n_real_
+        real vertices, num_peeled_, is_dag_, cyclic_ (bool[n_real_]: not peeled), level_sizes_ (int64: the vertices of every
+        level), num_levels_ and widest_; on a weighted load also dist_ (float32[n_]: bits 0x7fc00000 when unpeeled), parent_
+        (uint32[n_]: the smallest neighbour that attains dist_, 0xffffffff on sources and unpeeled vertices) and
+        critical_length_ (the largest dist_ of a peeled real vertex; None when nothing is peeled); with order=True order_ (the
+        peeled real vertices sorted by (level, vertex): a topological order, canonicalised on the host from the device's queue)
+        and position_ (uint32[n_real_]: where a vertex stands in order_, 0xffffffff when unpeeled).  The call waits for the
+        device."""
+        self._require_sent()
+        B, n, nr = self.backend, self.n_, self.n_real_
+        pin, pout, wbuf = self.SpMV_, self.out_, self.weight_buf_
+        if reverse:
+            wbuf = self.weight_out_buf_
+            if self.out_ is not None:
+                pin, pout = self.out_, self.SpMV_
+        room = max(1, n)
+        out = B.alloc(4 * room, np.float32)                          # (32-bit words: level, queue, dist, parent)
+        w = self.weighted_
+        stats = pin.topo(pout, B.view(out, 0, room, 4), B.view(out, room, room, 4) if order else None, wbuf if w else None,
+                         B.view(out, 2 * room, room, 4) if w else None, B.view(out, 3 * room, room, 4) if w else None)
+        B.sync()
+        got = B.download(out, np.uint32, 4 * room)
+        self.level_ = got[:n].copy()
+        peeled = self.level_[:nr] != 0xFFFFFFFF
+        self.cyclic_ = ~peeled
+        self.num_peeled_ = int(np.count_nonzero(peeled))
+        self.is_dag_ = self.num_peeled_ == nr
+        self.level_sizes_ = np.bincount(self.level_[:nr][peeled].astype(np.int64)).astype(np.int64)
+        self.num_levels_ = int(self.level_sizes_.shape[0])
+        self.widest_ = int(self.level_sizes_.max()) if self.num_levels_ else 0
+        self.launches_ = stats[3]
+        assert stats[0] == self.num_peeled_ + (n - nr), "gl_topo's count of peeled vertices and its levels disagree"
+        self.dist_ = self.parent_ = self.critical_length_ = None
+        if w:
+            self.dist_ = got[2 * room:2 * room + n].copy().view(np.float32)
+            self.parent_ = got[3 * room:3 * room + n].copy()
+            if self.num_peeled_:
+                self.critical_length_ = float(self.dist_[:nr][peeled].max())
+        self.order_ = self.position_ = None
+        if order:
+            queue = got[room:room + int(stats[0])].astype(np.int64)
+            queue = queue[queue < nr]
+            self.order_ = queue[np.lexsort((queue, self.level_[queue]))].astype(np.uint32)
+            self.position_ = np.full(nr, 0xFFFFFFFF, dtype=np.uint32)
+            self.position_[self.order_.astype(np.int64)] = np.arange(self.order_.shape[0], dtype=np.uint32)
+        return self.level_
+
+    def critical_path(self):
+        """-> int64[k]: the vertices of a longest weighted path of the last run, from the smallest real vertex of largest dist_
+        back along parent_ to a vertex without one (reverse=False: the path's END comes first; reverse=True: its start)."""
+        if self.dist_ is None:
+            raise RuntimeError("TopologicalOrder.critical_path(): run() on a weighted load first")
+        if not self.num_peeled_:
+            return np.zeros(0, dtype=np.int64)
+        nr = self.n_real_
+        peeled = ~self.cyclic_
+        v = int(np.flatnonzero(peeled & (self.dist_[:nr] == np.float32(self.critical_length_)))[0])
+        path = [v]
+        while self.parent_[path[-1]] != 0xFFFFFFFF:
+            path.append(int(self.parent_[path[-1]]))
+        return np.asarray(path, dtype=np.int64)
 
 
 class BetweennessCentrality(_PatternApp):

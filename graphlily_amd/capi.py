@@ -58,7 +58,8 @@ EXT_EXPORTS = ["gl_color"]
 # tests check their own entry, build() checks every list against the library
 EXT_HEADERS = {"graphlily_hip_ext.h": EXT_EXPORTS, "graphlily_hip_truss.h": ["gl_truss"], "graphlily_hip_msf.h": ["gl_msf"],
                "graphlily_hip_match.h": ["gl_match"], "graphlily_hip_lpa.h": ["gl_lpa"],
-               "graphlily_hip_scc.h": ["gl_scc"], "graphlily_hip_louvain.h": ["gl_louvain_move"], "graphlily_hip_bicc.h": ["gl_bicc"]}
+               "graphlily_hip_scc.h": ["gl_scc"], "graphlily_hip_louvain.h": ["gl_louvain_move"], "graphlily_hip_bicc.h": ["gl_bicc"],
+               "graphlily_hip_topo.h": ["gl_topo"]}
 
 
 class GraphLilyError(RuntimeError):
@@ -132,6 +133,7 @@ def lib():
         "gl_lpa": [vp, vp, vp, vp, u32, P(u64)],
         "gl_scc": [vp, vp, vp, vp, P(u64)],
         "gl_bicc": [vp, vp, vp, vp, vp, P(u64)],
+        "gl_topo": [vp, vp, vp, vp, vp, vp, vp, P(u64)],
         "gl_louvain_move": [vp, vp, vp, vp, vp, u32, u64, P(u64)],
         "gl_bc_accumulate": [vp, vp, vp, vp, ctypes.c_double, i32, vp, P(u32)],
         "gl_spmv_run": [vp, vp, vp, vp, i32, f32, i32],
@@ -601,6 +603,25 @@ class SpMVPlan:
         garbage = 0xdeadbeefdeadbeef
         stats = (ctypes.c_uint64 * 6)(*([garbage] * 6))
         check(lib().gl_bicc(ctypes.c_void_p(self.handle), _p(block), _p(vertex_blocks), _p(edge_component), _p(tree), stats))
+        return tuple(int(x) for x in stats)
+
+    def topo(self, plan_out, level, order=None, weight=None, dist=None, parent=None):
+        """gl_topo with this plan as plan_in (row v: the predecessors of v) and `plan_out` as the transposed pattern's plan (None,
+        or this plan: the pattern is symmetric): the topological levels of the directed graph into `level` (num_rows device
+        words) -- the edges of the longest path that ends in v, 0xffffffff for a vertex on a cycle or behind one -- -> (peeled,
+        levels, widest, launches enqueued).  `order` (optional, num_rows device words) receives the peeled vertices grouped by
+        level, in no particular order inside a level, then 0xffffffff.  With `weight` (nnz device floats aligned with this
+        plan's row copy, finite, no -0.0) `dist` and `parent` (num_rows device words each, required then and only then) receive
+        the weighted longest path: dist[v] = the largest f32 dist[u] + w(u, v) over the predecessors, +0 on a source, the bits
+        0x7fc00000 on an unpeeled vertex; parent[v] = the smallest u that attains it, 0xffffffff on sources and unpeeled
+        vertices.  Swapping the two plans (weights aligned with the other plan) gives heights.  Both plans are square, whole,
+        their rows strictly ascending sets (io.directed_weighted prepares them).  Every output is fully written by the call,
+        which SYNCHRONISES (it reads a control record back between batches of launches)."""
+        out = self if plan_out is None else plan_out
+        garbage = 0xdeadbeefdeadbeef
+        stats = (ctypes.c_uint64 * 4)(*([garbage] * 4))
+        check(lib().gl_topo(ctypes.c_void_p(self.handle), ctypes.c_void_p(out.handle), _p(weight), _p(level), _p(order), _p(dist),
+                            _p(parent), stats))
         return tuple(int(x) for x in stats)
 
     def bc_accumulate(self, plan_out, level, bc, scale=1.0, accumulate=False, sigma=None, stats=True):

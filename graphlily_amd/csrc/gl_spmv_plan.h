@@ -281,6 +281,9 @@ struct gl_spmv_plan_s {
     // tops, fifteen arrays of num_rows words (the forest's six, the queue, the union-find's and the per-vertex flags) and num_rows
     // + 2 level offsets
     unsigned char *d_bicc_scratch = nullptr;
+    // gl_topo (gl_topo.hip), as plan_in: the call's scratch, allocated by the first call -- 256 bytes of control record, num_rows
+    // dependency counters and num_rows words of queue
+    unsigned char *d_topo_scratch = nullptr;
     // gl_bc_accumulate (gl_bc.hip), as plan_in, set up by the first call: the pass's scratch -- 256 bytes of control words, two
     // arrays of num_rows + 2 level offsets, num_rows words of queue, num_rows doubles each of sigma and coef -- the page-locked
     // room the offsets are read back to, and the verdict on the last plan_out that was not this plan itself: is it the

@@ -11,6 +11,7 @@ Mirrors (names, argument meaning, in-place behaviour):
   symmetrize_simple                              io/data_formatter.h (util_symmetrize_simple: an extension, no reference counterpart)
   symmetrize_weighted                            io/data_formatter.h (util_symmetrize_weighted: an extension, no reference counterpart)
   simple_pattern                                 io/data_formatter.h (util_simple_pattern: an extension, no reference counterpart)
+  directed_weighted                              io/data_formatter.h (util_directed_weighted: an extension, no reference counterpart)
 The FPGA-only formatters (csr2cpsr, formatCSC: io/data_formatter.h:54-721) have no counterpart here:
 the device layout is produced inside gl_spmv_plan_create / gl_spmspv_plan_create.
 """
@@ -298,6 +299,51 @@ def simple_pattern(csr_matrix):
     key_in, key_out = np.unique(rows * n + cols), np.unique(cols * n + rows)
     symmetric = bool(np.array_equal(key_in, key_out))
     return build(key_in), (None if symmetric else build(key_out)), symmetric
+
+
+def directed_weighted(csr_matrix, weighted=True):
+    """The matrix preparation of TopologicalOrder (an extension) -> (csr_in, csr_out, symmetric): simple_pattern's reading with
+    weights.  The diagonal is dropped; every other STORED entry A[v, u] is an edge u -> v, a stored 0 included (weight 0 is a
+    legitimate weight); an edge stored more than once gets its LARGEST value (the natural reading for a longest path); -0.0
+    becomes +0.0; NaN and +-inf raise ValueError naming the first offending entry.  Row v of csr_in lists the predecessors of
+    v, row u of csr_out (the transposed pattern) the successors of u, each with the edge's weight in adj_data; both are n x n,
+    n = max(num_rows, num_cols), the columns of every row ascending.  `symmetric` says whether the two PATTERNS are the same;
+    csr_out is returned even then, because its weights are the transposed ones.  weighted=False returns exactly what
+    simple_pattern returns (zero values are no edges, every value 1, csr_out None for a symmetric pattern).  Applied after
+    padding: padding vertices have empty rows."""
+    if not weighted:
+        return simple_pattern(csr_matrix)
+    n = max(int(csr_matrix.num_rows), int(csr_matrix.num_cols))
+    indptr = csr_matrix.adj_indptr.astype(np.int64)[:csr_matrix.num_rows + 1]
+    nnz = int(indptr[-1])
+    rows = np.repeat(np.arange(csr_matrix.num_rows, dtype=np.int64), np.diff(indptr))
+    cols = csr_matrix.adj_indices[:nnz].astype(np.int64)
+    w = np.asarray(csr_matrix.adj_data[:nnz], dtype=np.float32)
+    bad = ~np.isfinite(w) & (rows != cols)
+    if np.any(bad):
+        j = int(np.flatnonzero(bad)[0])
+        raise ValueError("directed_weighted: entry %d (%d, %d) is %s: a longest path needs finite weights" % (j, rows[j], cols[j], w[j]))
+    off = rows != cols
+    rows, cols, w = rows[off], cols[off], w[off] + np.float32(0.0)            # (-0.0 + 0.0 == +0.0)
+    if rows.shape[0] > 0xFFFFFFFF:
+        raise ValueError("directed_weighted: %d entries do not fit 32-bit offsets" % rows.shape[0])
+    key = rows * n + cols
+    order = np.lexsort((-w, key))                                             # by entry, the largest value of each first
+    key, w = key[order], w[order]
+    once = np.ones(key.shape[0], dtype=bool)
+    once[1:] = key[1:] != key[:-1]
+    key, w = key[once], w[once]
+
+    def build(key, w):      # (sorted by (row, column), once each)
+        a, b = key // n, key % n
+        ip = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(np.bincount(a, minlength=n), out=ip[1:])
+        return CSRMatrix(n, n, w.astype(np.float32), b.astype(np.uint32), ip.astype(np.uint32))
+
+    key_out = key % n * n + key // n
+    back = np.argsort(key_out, kind="stable")
+    symmetric = bool(np.array_equal(key, key_out[back]))
+    return build(key, w), build(key_out[back], w[back]), symmetric
 
 
 def sssp_add_self_edges(csr_matrix):

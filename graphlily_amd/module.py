@@ -409,6 +409,22 @@ class SpMVModule(BaseModule):
         self._finish(block_buf, vertex_blocks_buf, edge_component_buf, tree_buf)
         return stats
 
+    def topo(self, out_module, level_buf, order_buf=None, weight_buf=None, dist_buf=None, parent_buf=None):
+        """Extension (gl_topo): the topological levels of this module's matrix, read as a directed graph -- row v: the
+        predecessors of v, `out_module` (None: the pattern is symmetric) holds the transposed pattern -- into `level_buf`
+        (get_num_rows() words: the edges of the longest path that ends in v, 0xffffffff on a cycle or behind one) -> (peeled,
+        levels, widest, launches).  `order_buf` (optional, as many words) receives the peeled vertices grouped by level.  With
+        `weight_buf` (get_nnz() floats aligned with the matrix's entries, finite) `dist_buf` and `parent_buf` (get_num_rows()
+        words each) receive the weighted longest path and its predecessor tree (ties to the smallest predecessor).  The call
+        synchronises.  Raises GraphLilyError (GL_ERR_UNSUPPORTED) when a plan keeps no row copy (only the (||,&&) layout does),
+        is not square, is a row shard, its rows are no strictly ascending sets, or the two are not each other's transpose
+        (io.directed_weighted prepares them)."""
+        if self.plan_ is None or (out_module is not None and out_module.plan_ is None):
+            _fatal("SpMVModule.topo: send_matrix_host_to_device first")
+        stats = self.plan_.topo(None if out_module is None else out_module.plan_, level_buf, order_buf, weight_buf, dist_buf, parent_buf)
+        self._finish(level_buf, order_buf, dist_buf, parent_buf)
+        return stats
+
     def bc_accumulate(self, out_module, level_buf, bc_buf, scale=1.0, accumulate=False, sigma_buf=None, stats=True):
         """Extension (gl_bc_accumulate): adds scale x Brandes' dependency of the search whose levels are in `level_buf`
         (get_num_rows() floats) to `bc_buf` (as many doubles; accumulate=False: overwrites it).  This module's matrix is the

@@ -323,6 +323,55 @@ bool util_simple_pattern(CSRMatrix<data_type> const &m, CSRMatrix<data_type> &in
     return symmetric;
 }
 
+// The matrix preparation of app::TopologicalOrder (an extension), io.directed_weighted's words: util_simple_pattern's reading with
+// weights.  The diagonal is dropped; every other STORED entry A[v,u] is an edge u -> v, a stored 0 included; an edge stored more
+// than once gets its LARGEST value; -0.0 becomes +0.0; a NaN or an infinity prints and exits.  Row v of `in` lists the
+// predecessors of v, row u of `out` (the transposed pattern) the successors of u, each with the edge's weight in adj_data; both n
+// x n, n = max(num_rows, num_cols), columns ascending.  Returns whether the two PATTERNS are the same; `out` is filled even then
+// (its weights are the transposed ones).  weighted = false is util_simple_pattern itself.  Apply after padding.
+template <typename data_type>
+bool util_directed_weighted(CSRMatrix<data_type> const &m, CSRMatrix<data_type> &in, CSRMatrix<data_type> &out, bool weighted = true) {
+    if (!weighted) return util_simple_pattern(m, in, out);
+    const uint64_t n = std::max(m.num_rows, m.num_cols);
+    std::vector<std::pair<uint64_t, data_type>> entry;          // {row * n + column, weight}
+    entry.reserve((size_t)m.adj_indptr[m.num_rows]);
+    for (uint32_t v = 0; v < m.num_rows; v++)
+        for (uint32_t i = m.adj_indptr[v]; i < m.adj_indptr[v + 1]; i++) {
+            const uint64_t u = m.adj_indices[i];
+            if (u == v) continue;
+            const data_type w = m.adj_data[i] + data_type(0);   // (-0.0 + 0.0 == +0.0)
+            if (w != w || w - w != data_type(0)) {
+                printf("util_directed_weighted: entry %u (%u, %u) is %g: a longest path needs finite weights\n", i, v, (uint32_t)u, (double)w);
+                exit(EXIT_FAILURE);
+            }
+            entry.push_back(std::make_pair(v * n + u, w));
+        }
+    std::sort(entry.begin(), entry.end());                      // by entry, the largest value of each last
+    std::vector<std::pair<uint64_t, data_type>> once, back;
+    for (size_t i = 0; i < entry.size(); i++)
+        if (i + 1 == entry.size() || entry[i + 1].first != entry[i].first) once.push_back(entry[i]);
+    back.reserve(once.size());
+    for (auto const &e : once) back.push_back(std::make_pair(e.first % n * n + e.first / n, e.second));
+    std::sort(back.begin(), back.end());
+    auto build = [n](const std::vector<std::pair<uint64_t, data_type>> &es, CSRMatrix<data_type> &r) {
+        r.num_rows = r.num_cols = (uint32_t)n;
+        r.adj_indptr.assign(n + 1, 0);
+        r.adj_indices.clear();
+        r.adj_data.clear();
+        for (auto const &e : es) {
+            r.adj_indptr[e.first / n + 1]++;
+            r.adj_indices.push_back((uint32_t)(e.first % n));
+            r.adj_data.push_back(e.second);
+        }
+        for (uint64_t v = 0; v < n; v++) r.adj_indptr[v + 1] += r.adj_indptr[v];
+    };
+    build(once, in);
+    build(back, out);
+    bool symmetric = true;
+    for (size_t i = 0; i < once.size() && symmetric; i++) symmetric = once[i].first == back[i].first;
+    return symmetric;
+}
+
 }  // namespace io
 }  // namespace graphlily
 

@@ -18,6 +18,7 @@
 #include "graphlily_hip_louvain.h"
 #include "graphlily_hip_scc.h"
 #include "graphlily_hip_bicc.h"
+#include "graphlily_hip_topo.h"
 #include "graphlily/io/data_formatter.h"
 #include "graphlily/io/data_loader.h"
 #include "graphlily/module/base_module.h"
@@ -296,6 +297,20 @@ public:
     void bicc(DeviceBuffer block, DeviceBuffer vertex_blocks, DeviceBuffer edge_component, uint64_t *stats = nullptr) {
         barrier_();
         GRAPHLILY_CHECK(gl_bicc(plan_, (uint32_t *)block.ptr(), (uint32_t *)vertex_blocks.ptr(), (uint32_t *)edge_component.ptr(), nullptr, stats));
+        finish_();
+    }
+    // extension (gl_topo, graphlily_hip_topo.h): the topological levels of this module's matrix, read as a directed graph -- row v:
+    // the predecessors of v; `out` holds the transposed pattern (nullptr: the pattern is symmetric); both in the (||,&&) layout,
+    // rows strictly ascending (graphlily::io::util_directed_weighted prepares them) -- into `level` (get_num_rows() device words:
+    // the edges of the longest path that ends in v, 0xffffffff on a cycle or behind one).  `order` (as many device words, or
+    // nullptr) receives the peeled vertices grouped by level; with `weight` (get_nnz() device floats aligned with the matrix's
+    // entries, finite; nullptr: unweighted) `dist` and `parent` (get_num_rows() device words each, given iff weight is) receive
+    // the weighted longest path and its predecessor tree, ties to the smallest predecessor.  stats (optional, 4 host words)
+    // receives {peeled, levels, widest, launches}.  The call synchronises.
+    void topo(SpMVModule *out, DeviceBuffer level, uint32_t *order = nullptr, const float *weight = nullptr, float *dist = nullptr,
+              uint32_t *parent = nullptr, uint64_t *stats = nullptr) {
+        barrier_();
+        GRAPHLILY_CHECK(gl_topo(plan_, out ? out->plan_ : plan_, weight, (uint32_t *)level.ptr(), order, dist, parent, stats));
         finish_();
     }
     // extension (gl_bc_accumulate): adds scale x Brandes' dependency of the search whose levels are in `level` (get_num_rows()
