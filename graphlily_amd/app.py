@@ -1621,6 +1621,123 @@ def validate_topological(csr, level, dist=None, parent=None, weighted=False):
     return int(np.count_nonzero(peeled))
 
 
+def _hops_of(A_out, s, n):
+    """-> uint32[n]: the edges of a shortest path from s to every vertex on the host (0 on s, 0xffffffff unreached); A_out is the
+    scipy matrix whose row u holds the out-neighbours of u."""
+    hops = np.full(n, 0xFFFFFFFF, dtype=np.uint32)
+    frontier = np.array([s], dtype=np.int64)
+    hops[s] = 0
+    ip, idx = A_out.indptr, A_out.indices
+    d = 0
+    while frontier.size:
+        starts, lens = ip[frontier], ip[frontier + 1] - ip[frontier]
+        total = int(lens.sum())
+        if not total:
+            break
+        at = np.repeat(starts - (np.cumsum(lens) - lens), lens) + np.arange(total, dtype=np.int64)
+        nxt = np.unique(idx[at])
+        frontier = nxt[hops[nxt] == 0xFFFFFFFF]
+        d += 1
+        hops[frontier] = d
+    return hops
+
+
+def _closeness_sums(hops_rows, batch=64):
+    """gl_msbfs's three arrays from the sources' distance rows (uint32[k, n], 0xffffffff unreached), as a driver that deals the
+    sources into batches of `batch` accumulates them -> (far uint64[n], reach uint32[n], harmonic float64[n]).  The harmonic
+    sum is the device's ordered f64 loop: per batch the levels d ascending, c = the batch's sources at distance d, one division
+    and one addition where c > 0."""
+    hops_rows = np.asarray(hops_rows, dtype=np.uint32)
+    k, n = hops_rows.shape
+    far, reach, harmonic = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.float64)
+    for b in range(0, k, batch):
+        rows = hops_rows[b:b + batch]
+        finite = rows[(rows != 0xFFFFFFFF) & (rows != 0)]
+        for d in range(1, (int(finite.max()) if finite.size else 0) + 1):
+            c = np.count_nonzero(rows == d, axis=0)
+            hit = c > 0
+            far[hit] += (c[hit] * d).astype(np.uint64)
+            reach[hit] += c[hit].astype(np.uint32)
+            harmonic[hit] = harmonic[hit] + c[hit].astype(np.float64) / np.float64(d)
+    return far, reach, harmonic
+
+
+def closeness_of(far, reach, n, wf_improved=True):
+    """-> float64: the closeness centrality from gl_msbfs's integer arrays on a graph of n vertices, in f64 on the host: reach /
+    far (0 where far == 0), times reach / (n - 1) with wf_improved (Wasserman and Faust's scaling for graphs that are not
+    strongly connected) -- networkx.closeness_centrality's value when every vertex is a source."""
+    far, reach = np.asarray(far).astype(np.float64), np.asarray(reach).astype(np.float64)
+    live = far > 0
+    out = np.zeros(far.shape[0], dtype=np.float64)
+    out[live] = reach[live] / far[live]
+    if wf_improved:
+        out[live] = out[live] * (reach[live] / np.float64(n - 1)) if n > 1 else 0.0
+    return out
+
+
+def validate_closeness(csr, far, reach, harmonic=None, sources=None, directed=None, reverse=False, hops=None):
+    """Host-side check (numpy / scipy) that `far`, `reach` -- and `harmonic` and `hops` when given -- are gl_msbfs's results on the
+    simple graph of `csr`, as ClosenessCentrality reads it: an edge u -> v iff u != v and a stored non-zero entry A[v, u] exists;
+    directed=None reads it as undirected iff that pattern is symmetric, False takes every edge in both directions.  `sources`
+    (None: all csr.num_rows vertices) is the SEQUENCE the driver dealt into batches of 64; reverse=False measures the distances
+    from the sources (what every vertex sums is its INCOMING distance), True the distances to them.  Everything is recomputed
+    from one host BFS per source; the integers are compared exactly, `harmonic` as bits against the same ordered f64 loop,
+    `hops` (uint32[len(sources), n]) word by word.  Raises ValueError with the first violation; returns the diameter found (the
+    largest finite distance from a source).  The arrays may be longer than the matrix (the drivers pad it): the extra vertices
+    are isolated and must hold 0."""
+    nr, nc = int(csr.num_rows), int(csr.num_cols)
+    got_far, got_reach = np.asarray(far), np.asarray(reach)
+    n = got_far.shape[0] if got_far.ndim == 1 else -1
+    if n < max(nr, nc) or got_reach.shape != (n,):
+        raise ValueError("validate_closeness: %d and %d values for a %d x %d matrix" % (n, got_reach.shape[0] if got_reach.ndim == 1 else -1, nr, nc))
+    src = list(range(nr)) if sources is None else [int(s) for s in sources]
+    if any(s < 0 or s >= nr for s in src):
+        raise ValueError("validate_closeness: a source outside 0 .. %d" % (nr - 1))
+    if len(set(src)) != len(src):
+        raise ValueError("validate_closeness: a source is given twice")
+    cin, cout, directed = _bc_patterns(csr, directed)
+    A_in = _pattern_as_scipy(cin, n)
+    A_out = A_in.T.tocsr() if cout is None or not directed else _pattern_as_scipy(cout, n)      # row u: the out-neighbours of u
+    walk = A_in if reverse else A_out
+    walk.sort_indices()
+    rows = np.empty((len(src), n), dtype=np.uint32)
+    for j, s in enumerate(src):
+        rows[j] = _hops_of(walk, s, n)
+    want_far, want_reach, want_harmonic = _closeness_sums(rows)
+
+    def first(bad):
+        return int(np.flatnonzero(bad)[0])
+
+    if hops is not None:
+        got_hops = np.asarray(hops)
+        if got_hops.shape != rows.shape:
+            raise ValueError("validate_closeness: hops of shape %s, expected %s" % (got_hops.shape, rows.shape))
+        bad = got_hops.astype(np.int64) != rows.astype(np.int64)
+        if np.any(bad):
+            j, v = (int(x[0]) for x in np.nonzero(bad))
+            raise ValueError("validate_closeness: hops[%d, %d] is %d, vertex %d lies %d edges from source %d"
+                             % (j, v, got_hops[j, v], v, rows[j, v], src[j]))
+    bad = got_far.astype(np.uint64) != want_far
+    if np.any(bad):
+        v = first(bad)
+        raise ValueError("validate_closeness: vertex %d has far %d, its distances sum to %d" % (v, got_far[v], want_far[v]))
+    bad = got_reach.astype(np.int64) != want_reach.astype(np.int64)
+    if np.any(bad):
+        v = first(bad)
+        raise ValueError("validate_closeness: vertex %d has reach %d, %d sources reach it" % (v, got_reach[v], want_reach[v]))
+    if harmonic is not None:
+        got_h = np.ascontiguousarray(harmonic, dtype=np.float64)
+        if got_h.shape != (n,):
+            raise ValueError("validate_closeness: harmonic must have %d values, as far" % n)
+        bad = got_h.view(np.uint64) != want_harmonic.view(np.uint64)
+        if np.any(bad):
+            v = first(bad)
+            raise ValueError("validate_closeness: vertex %d has harmonic %.17g (bits 0x%016x), the ordered loop gives %.17g"
+                             % (v, got_h[v], got_h.view(np.uint64)[v], want_harmonic[v]))
+    finite = rows[rows != 0xFFFFFFFF]
+    return int(finite.max()) if finite.size else 0
+
+
 class ModuleCollection:
     def __init__(self):
         self.modules_ = []
@@ -3218,6 +3335,104 @@ class BetweennessCentrality(_PatternApp):
             warnings.warn("BetweennessCentrality.run(): the shortest-path counts of the searches from %s overflowed f64; these sources "
                           "contribute nothing" % self.overflowed_, RuntimeWarning, stacklevel=2)
         return self.bc_
+
+
+class ClosenessCentrality(_PatternApp):
+    """Closeness and harmonic centrality, eccentricities and hop distances (an extension: the reference has no such driver):
+    gl_msbfs, the bit-parallel breadth-first search that sweeps 64 sources at once.  The matrix is read as
+    BetweennessCentrality reads it (io.simple_pattern: an edge u -> v for a stored non-zero A[v, u], u != v); the transposed
+    pattern lives in a second boolean SpMVModule, out_, which exists only when the graph is directed."""
+    _no_shards_ = ("gl_msbfs reads the frontier word of every column of a row, so every rank would need the whole frontier after "
+                   "every level")
+    BATCH = 64
+    graph_ = graph_out_ = directed_ = None
+    far_ = reach_ = harmonic_ = closeness_ = hops_ = sources_ = batches_ = levels_ = launches_ = None
+    eccentricity_ = source_reach_ = source_far_ = diameter_ = radius_ = center_ = periphery_ = None
+
+    def __init__(self, num_channels=M.num_hbm_channels, spmv_out_buf_len=0, vec_buf_len=0, comm=None, backend=None):
+        _PatternApp.__init__(self, num_channels, spmv_out_buf_len, vec_buf_len, comm, backend)
+        self.buf_lens_ = (spmv_out_buf_len, vec_buf_len)
+        self.out_ = None                 # the transposed pattern's module (a directed graph)
+        self.want_directed_ = None
+
+    def _prepare(self, csr):
+        self.graph_, self.graph_out_, self.directed_ = _bc_patterns(csr, self.want_directed_)      # (after padding)
+        return self.graph_
+
+    def load_and_format_matrix(self, csr_float_npz_path, skip_empty_rows=True, directed=None):
+        """directed=None: undirected iff the pattern is symmetric; False on an asymmetric pattern takes every edge in both
+        directions (io.symmetrize_simple); True keeps two plans even when the pattern is symmetric."""
+        self.want_directed_ = directed
+        _PatternApp.load_and_format_matrix(self, csr_float_npz_path, skip_empty_rows)
+        self.modules_ = [self.SpMV_]
+        self.out_ = None
+        if self.graph_out_ is not None:
+            self.out_ = self.backend.SpMVModule(self.num_channels_, *self.buf_lens_)
+            self.out_.set_semiring(M.LogicalSemiring)
+            self.out_.set_mask_type(M.kNoMask)
+            self.out_.blocking = False
+            self.out_.load_and_format_matrix(self.graph_out_, skip_empty_rows)
+            self.add_module(self.out_)
+
+    def send_matrix_host_to_device(self):
+        _PatternApp.send_matrix_host_to_device(self)
+        if self.out_ is not None:
+            self.out_.send_matrix_host_to_device()
+
+    def run(self, sources=None, reverse=False, wf_improved=True, hops=False):
+        """-> float64[n_]: the closeness centrality of every vertex (padding vertices: 0) with respect to `sources` (a sequence
+        of distinct real vertices; None: all of them): reach / far, 0 where far == 0, times reach / (n_real_ - 1) with
+        wf_improved, computed on the host in f64 from gl_msbfs's integer arrays -- networkx.closeness_centrality when every
+        vertex is a source.  reverse=False sums at every vertex its INCOMING distances, d(s, v) over the sources s, which is
+        networkx's convention on a DiGraph for closeness_centrality and harmonic_centrality; reverse=True walks the transposed
+        pattern's plan and sums d(v, s).  The sources are dealt in the given order into batches of 64, one gl_msbfs call each,
+        accumulating from the second on.  Leaves far_ (uint64[n_]), reach_ (uint32[n_]), harmonic_ (float64[n_]: the sum of
+        1 / d, a function of the graph and the source SEQUENCE), closeness_, sources_, batches_, levels_ (the levels swept,
+        summed over the batches), launches_, per source eccentricity_, source_reach_ and source_far_ (int64[len(sources)]),
+        diameter_ (the largest eccentricity: exact when every vertex is a source, a lower bound otherwise), radius_ (the
+        smallest), center_ and periphery_ (the sources that attain them) and, with hops=True, hops_ (uint32[len(sources), n_]:
+        the distances from -- reverse: to -- every source, 0xffffffff unreached; otherwise None).  The call waits for the
+        device."""
+        self._require_sent()
+        B, n, nr = self.backend, self.n_, self.n_real_
+        src = list(range(nr)) if sources is None else [int(s) for s in sources]
+        if any(s < 0 or s >= nr for s in src):
+            raise ValueError("ClosenessCentrality.run(): a source outside the real vertices 0 .. %d" % (nr - 1))
+        if len(set(src)) != len(src):
+            raise ValueError("ClosenessCentrality.run(): a source is given twice")
+        module = self.out_ if reverse and self.out_ is not None else self.SpMV_
+        k_most = min(self.BATCH, max(1, len(src)))
+        out = B.alloc(5 * n + (k_most * n if hops else 0), np.float32)       # (32-bit words: far, harmonic, reach, a batch's hops)
+        far_buf, harmonic_buf, reach_buf = B.view(out, 0, n, 8), B.view(out, n, n, 8), B.view(out, 4 * n, n, 4)      # (first: in items)
+        hops_buf = B.view(out, 5 * n, k_most * n, 4) if hops else None
+        self.sources_, self.batches_, self.levels_, self.launches_ = src, 0, 0, 0
+        self.hops_ = np.empty((len(src), n), dtype=np.uint32) if hops else None
+        per_source = np.zeros((len(src), 3), dtype=np.int64)
+        for b in range(0, len(src), self.BATCH):
+            part = src[b:b + self.BATCH]
+            source_stats, stats = module.msbfs(part, far_buf, reach_buf, harmonic_buf, b > 0, hops_buf)
+            per_source[b:b + len(part)] = source_stats.astype(np.int64)
+            self.batches_ += 1
+            self.levels_ += stats[0]
+            self.launches_ += stats[2]
+            if hops:
+                B.sync()
+                self.hops_[b:b + len(part)] = B.download(hops_buf, np.uint32, len(part) * n).reshape(len(part), n)
+        B.sync()
+        if src:
+            self.far_ = B.download(far_buf, np.uint64, n)
+            self.harmonic_ = B.download(harmonic_buf, np.float64, n)
+            self.reach_ = B.download(reach_buf, np.uint32, n)
+        else:                                                        # no source: nothing was launched
+            self.far_, self.harmonic_, self.reach_ = np.zeros(n, np.uint64), np.zeros(n, np.float64), np.zeros(n, np.uint32)
+        self.source_reach_, self.source_far_, self.eccentricity_ = per_source[:, 0].copy(), per_source[:, 1].copy(), per_source[:, 2].copy()
+        ecc, who = self.eccentricity_, np.asarray(src, dtype=np.int64)
+        self.diameter_ = int(ecc.max()) if src else 0
+        self.radius_ = int(ecc.min()) if src else 0
+        self.center_ = who[ecc == self.radius_] if src else who
+        self.periphery_ = who[ecc == self.diameter_] if src else who
+        self.closeness_ = closeness_of(self.far_, self.reach_, nr, wf_improved)
+        return self.closeness_
 
 
 class PageRank(_GraphApp):

@@ -59,7 +59,7 @@ EXT_EXPORTS = ["gl_color"]
 EXT_HEADERS = {"graphlily_hip_ext.h": EXT_EXPORTS, "graphlily_hip_truss.h": ["gl_truss"], "graphlily_hip_msf.h": ["gl_msf"],
                "graphlily_hip_match.h": ["gl_match"], "graphlily_hip_lpa.h": ["gl_lpa"],
                "graphlily_hip_scc.h": ["gl_scc"], "graphlily_hip_louvain.h": ["gl_louvain_move"], "graphlily_hip_bicc.h": ["gl_bicc"],
-               "graphlily_hip_topo.h": ["gl_topo"]}
+               "graphlily_hip_topo.h": ["gl_topo"], "graphlily_hip_msbfs.h": ["gl_msbfs"]}
 
 
 class GraphLilyError(RuntimeError):
@@ -134,6 +134,7 @@ def lib():
         "gl_scc": [vp, vp, vp, vp, P(u64)],
         "gl_bicc": [vp, vp, vp, vp, vp, P(u64)],
         "gl_topo": [vp, vp, vp, vp, vp, vp, vp, P(u64)],
+        "gl_msbfs": [vp, vp, u32, i32, vp, vp, vp, vp, vp, vp],
         "gl_louvain_move": [vp, vp, vp, vp, vp, u32, u64, P(u64)],
         "gl_bc_accumulate": [vp, vp, vp, vp, ctypes.c_double, i32, vp, P(u32)],
         "gl_spmv_run": [vp, vp, vp, vp, i32, f32, i32],
@@ -623,6 +624,31 @@ class SpMVPlan:
         check(lib().gl_topo(ctypes.c_void_p(self.handle), ctypes.c_void_p(out.handle), _p(weight), _p(level), _p(order), _p(dist),
                             _p(parent), stats))
         return tuple(int(x) for x in stats)
+
+    def msbfs(self, sources, far, reach, harmonic, accumulate=False, hops=None):
+        """gl_msbfs: the bit-parallel breadth-first search from the k = len(sources) <= 64 vertices `sources` (host integers
+        below num_rows; a vertex given twice counts twice) over this plan's graph -- row v: the predecessors of v, so distances
+        run FROM the sources; the transposed pattern's plan measures them TO the sources -- -> (source_stats, stats):
+        source_stats = uint64[k, 3], per source {vertices at distance >= 1, the sum of those distances, the eccentricity},
+        stats = (levels swept, vertices that met all k sources, launches enqueued, 0).  `far` (num_rows device 64-bit words)
+        receives per vertex the sum of its finite distances >= 1 from the sources, `reach` (num_rows device words) their
+        number, `harmonic` (num_rows device doubles) the sum of c / d over the levels d ascending, c = the sources at distance
+        d; accumulate=True adds to the three instead of initialising them.  `hops` (optional, k * num_rows device words)
+        receives row j = the distances from sources[j], 0xffffffff when unreached.  The plan is square and whole; its rows need
+        be neither sorted nor sets nor symmetric.  Every output is fully written by the call, which SYNCHRONISES (it reads a
+        control word back between batches of launches)."""
+        src = np.ascontiguousarray(np.asarray(sources, dtype=np.int64).ravel())
+        if src.size and (src.min() < 0 or src.max() > 0xffffffff):
+            raise ValueError("SpMVPlan.msbfs: sources must be vertex numbers")
+        src = src.astype(np.uint32)
+        k = int(src.size)
+        garbage = 0xdeadbeefdeadbeef
+        source_stats = np.full((max(k, 1), 3), garbage, dtype=np.uint64)
+        stats = (ctypes.c_uint64 * 4)(*([garbage] * 4))
+        check(lib().gl_msbfs(ctypes.c_void_p(self.handle), ctypes.c_void_p((src if k else np.zeros(1, np.uint32)).ctypes.data), ctypes.c_uint32(k),
+                             1 if accumulate else 0, _p(far), _p(reach), _p(harmonic), _p(hops),
+                             ctypes.c_void_p(source_stats.ctypes.data), stats))
+        return source_stats[:k], tuple(int(x) for x in stats)
 
     def bc_accumulate(self, plan_out, level, bc, scale=1.0, accumulate=False, sigma=None, stats=True):
         """gl_bc_accumulate with this plan as plan_in (row v: the vertices v is pulled from) and `plan_out` as the transposed

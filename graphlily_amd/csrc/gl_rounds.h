@@ -1,5 +1,5 @@
 // The scheduling idiom of the round-based graph kernels on the row copy (gl_rows.h) -- gl_cc's hook, gl_kcore, gl_color, gl_truss,
-// gl_msf, gl_match, gl_lpa, gl_scc, gl_bicc's level search, gl_topo -- stated once: the atomics of the memory rule, the wavefront-aggregated append to a queue, the control
+// gl_msf, gl_match, gl_lpa, gl_scc, gl_bicc's level search, gl_topo, gl_msbfs (the atomics and the host loop) -- stated once: the atomics of the memory rule, the wavefront-aggregated append to a queue, the control
 // record of the two peeling kernels, and the host loop that enqueues gated batches blindly and reads the record back once per batch.
 //
 // MEMORY RULE (gfx950: eight XCDs with private L2s -- a plain store is not seen across them within a launch): a word that one
@@ -69,7 +69,7 @@ enum RoundsVerdict { kRoundsGoOn, kRoundsDone, kRoundsStuck };
 // The gated host loop.  Per batch: enqueue() enqueues `batch` steps and whatever rides behind them and returns the launches it
 // enqueued (`launches` is added to); copy() enqueues the copies of the record into the staging words and returns their hipError_t;
 // after ONE synchronisation verdict() reads the staging words; a run that is stuck, or not done after max_steps steps, ends with
-// what fail(steps) returns (set_error, in the caller's wording).  kcore(), color(), truss(), msf(), match(), lpa(), scc(), bicc() and topo() all fit without a flag.
+// what fail(steps) returns (set_error, in the caller's wording).  kcore(), color(), truss(), msf(), match(), lpa(), scc(), bicc(), topo() and msbfs() all fit without a flag.
 template <typename Enqueue, typename Copy, typename Verdict, typename Fail>
 int rounds_run(uint32_t batch, uint64_t max_steps, uint64_t &launches, Enqueue enqueue, Copy copy, Verdict verdict, Fail fail) {
     for (uint64_t steps = batch;; steps += batch) {

@@ -1,5 +1,5 @@
 // The plain CSR row copy that a GL_PLAN_BOOLEAN plan keeps (gl_spmv_plan.h: d_csr_indptr / d_csr_indices / csr_nz_base), as the
-// graph kernels that walk it see it -- gl_bfs_parents, gl_cc, gl_tc, gl_kcore, gl_color, gl_truss, gl_bc, gl_scc, gl_bicc, gl_topo, gl_lpa, and gl_msf,
+// graph kernels that walk it see it -- gl_bfs_parents, gl_cc, gl_tc, gl_kcore, gl_color, gl_truss, gl_bc, gl_scc, gl_bicc, gl_topo, gl_msbfs, gl_lpa, and gl_msf,
 // gl_match and gl_louvain (which also take a value per entry of the copy from their caller): what a caller may require of it,
 // the verdicts about it that the plan caches, the few helpers every such kernel wants, and the walk over a row -- a thread per
 // row, then the wavefront -- that ten of them run and gl_bc copies (rows_walk_*, at the end; gl_tc and gl_truss intersect rows
@@ -85,7 +85,7 @@ __device__ __forceinline__ uint32_t rows_lower_bound(P s, uint32_t n, uint32_t w
 }
 
 // THE WALK over the entries [beg, end) of one row per lane, 64 rows per wavefront (gl_bfs_parents, gl_cc, gl_kcore, gl_msf, gl_match,
-// gl_color, gl_scc, gl_bicc and gl_topo run all of it -- match_collect_kernel with a copy of the thread steps in which every lane takes every step --,
+// gl_color, gl_scc, gl_bicc, gl_topo and gl_msbfs run all of it -- match_collect_kernel with a copy of the thread steps in which every lane takes every step --,
 // gl_lpa and gl_louvain the takeover and the wavefront's steps behind a thread path of their own; DESIGN.md 4.13.  bc_sweep_kernel of
 // gl_bc keeps a copy of its own, in the same forms: through these templates its accumulate figure on one stand-in was 1 - 2 % above
 // the parent's worse run in two visits, EXPERIMENTS.md Round 21):

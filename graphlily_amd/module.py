@@ -425,6 +425,22 @@ class SpMVModule(BaseModule):
         self._finish(level_buf, order_buf, dist_buf, parent_buf)
         return stats
 
+    def msbfs(self, sources, far_buf, reach_buf, harmonic_buf, accumulate=False, hops_buf=None):
+        """Extension (gl_msbfs): the bit-parallel breadth-first search from up to 64 `sources` (host vertex numbers) over this
+        module's matrix, read as a directed graph -- row v: the predecessors of v, so the distances run FROM the sources; the
+        transposed pattern's module measures them TO the sources -- -> (source_stats, stats): uint64[k, 3] of {vertices at
+        distance >= 1, the sum of those distances, the eccentricity} per source, and (levels, vertices that met every source,
+        launches, 0).  `far_buf` (get_num_rows() 64-bit words), `reach_buf` (as many words) and `harmonic_buf` (as many
+        doubles) receive per vertex the sum and the number of its finite distances >= 1 and the sum of their reciprocals, or
+        are added to with accumulate=True; `hops_buf` (optional, k * get_num_rows() words) receives the distances themselves,
+        0xffffffff when unreached.  The call synchronises.  Raises GraphLilyError (GL_ERR_UNSUPPORTED) when the plan keeps no
+        row copy (only the (||,&&) layout does), is not square or is a row shard; the rows may hold anything."""
+        if self.plan_ is None:
+            _fatal("SpMVModule.msbfs: send_matrix_host_to_device first")
+        out = self.plan_.msbfs(sources, far_buf, reach_buf, harmonic_buf, accumulate, hops_buf)
+        self._finish(far_buf, reach_buf, harmonic_buf, hops_buf)
+        return out
+
     def bc_accumulate(self, out_module, level_buf, bc_buf, scale=1.0, accumulate=False, sigma_buf=None, stats=True):
         """Extension (gl_bc_accumulate): adds scale x Brandes' dependency of the search whose levels are in `level_buf`
         (get_num_rows() floats) to `bc_buf` (as many doubles; accumulate=False: overwrites it).  This module's matrix is the

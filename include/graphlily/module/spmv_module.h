@@ -19,6 +19,7 @@
 #include "graphlily_hip_scc.h"
 #include "graphlily_hip_bicc.h"
 #include "graphlily_hip_topo.h"
+#include "graphlily_hip_msbfs.h"
 #include "graphlily/io/data_formatter.h"
 #include "graphlily/io/data_loader.h"
 #include "graphlily/module/base_module.h"
@@ -311,6 +312,21 @@ public:
               uint32_t *parent = nullptr, uint64_t *stats = nullptr) {
         barrier_();
         GRAPHLILY_CHECK(gl_topo(plan_, out ? out->plan_ : plan_, weight, (uint32_t *)level.ptr(), order, dist, parent, stats));
+        finish_();
+    }
+    // extension (gl_msbfs, graphlily_hip_msbfs.h): the bit-parallel breadth-first search from the k <= 64 vertices `sources` (host
+    // words) over this module's matrix, read as a directed graph -- row v: the predecessors of v, so distances run FROM the
+    // sources; the transposed pattern's module measures them TO the sources; the (||,&&) layout, rows of any kind.  `far`
+    // (get_num_rows() device 64-bit words), `reach` (as many words) and `harmonic` (as many doubles) receive per vertex the sum
+    // and the number of its finite distances >= 1 and the sum of c / d over the levels d ascending, or are added to with
+    // accumulate; `hops` (k * get_num_rows() device words, or nullptr) the distances, 0xffffffff when unreached.  source_stats
+    // (optional, 3 k host words) receives {reached, sum of distances, eccentricity} per source, stats (optional, 4 host words)
+    // {levels, vertices that met every source, launches, 0}.  The call synchronises.
+    void msbfs(const uint32_t *sources, uint32_t k, bool accumulate, DeviceBuffer far, DeviceBuffer reach, DeviceBuffer harmonic,
+               uint32_t *hops = nullptr, uint64_t *source_stats = nullptr, uint64_t *stats = nullptr) {
+        barrier_();
+        GRAPHLILY_CHECK(gl_msbfs(plan_, sources, k, accumulate ? 1 : 0, (uint64_t *)far.ptr(), (uint32_t *)reach.ptr(),
+                                 (double *)harmonic.ptr(), hops, source_stats, stats));
         finish_();
     }
     // extension (gl_bc_accumulate): adds scale x Brandes' dependency of the search whose levels are in `level` (get_num_rows()
