@@ -1738,6 +1738,104 @@ def validate_closeness(csr, far, reach, harmonic=None, sources=None, directed=No
     return int(finite.max()) if finite.size else 0
 
 
+SIMILARITY_MEASURES = ("common", "jaccard", "overlap", "sorensen", "cosine", "preferential_attachment", "adamic_adar",
+                       "resource_allocation")
+
+
+def similarity_shift(max_degree):
+    """-> the fixed point of Similarity's weight tables: 62 - bit_length(max degree).  A weight is below 2^(shift + 1) (1 / ln 2
+    < 2), a pair has at most max degree < 2^bit_length common neighbours, so every sum stays below 2^63: gl_similarity's
+    64-bit sums never wrap in the driver."""
+    return 62 - int(max_degree).bit_length()
+
+
+def similarity_tables(degrees):
+    """-> (aa uint64[n], ra uint64[n], shift): aa[w] = round(2^shift / ln(deg w)) and ra[w] = round(2^shift / deg w) where deg w
+    >= 2, else 0 (a common neighbour of two distinct vertices has degree at least 2).  One f64 division and one rounding to
+    nearest-even per distinct degree; the logarithm is the C library's, as in the C++ driver."""
+    deg = np.asarray(degrees).astype(np.int64)
+    shift = similarity_shift(int(deg.max()) if deg.size else 0)
+    distinct, inverse = np.unique(deg, return_inverse=True)
+    one = math.ldexp(1.0, shift)
+    aa = np.array([np.rint(one / math.log(d)) if d >= 2 else 0.0 for d in distinct.tolist()], dtype=np.float64)
+    ra = np.array([np.rint(one / float(d)) if d >= 2 else 0.0 for d in distinct.tolist()], dtype=np.float64)
+    return aa.astype(np.uint64)[inverse].reshape(deg.shape), ra.astype(np.uint64)[inverse].reshape(deg.shape), shift
+
+
+def similarity_measure(name, common, du, dv, weighted=None, shift=0):
+    """-> one measure of SIMILARITY_MEASURES for pairs with `common` common neighbours and degrees du, dv, in f64 on the host
+    from the integers (0.0 where a denominator is 0); `weighted` is gl_similarity's fixed-point sum for the two weighted
+    measures.  common and preferential_attachment stay integers (uint32, uint64)."""
+    c, a, b = np.asarray(common).astype(np.float64), np.asarray(du).astype(np.float64), np.asarray(dv).astype(np.float64)
+    if name == "common":
+        return np.asarray(common).astype(np.uint32)
+    if name == "preferential_attachment":
+        return np.asarray(du).astype(np.uint64) * np.asarray(dv).astype(np.uint64)
+    if name in ("adamic_adar", "resource_allocation"):
+        return np.asarray(weighted).astype(np.uint64).astype(np.float64) * math.ldexp(1.0, -shift)
+    if name == "jaccard":
+        num, den = c, a + b - c
+    elif name == "overlap":
+        num, den = c, np.minimum(a, b)
+    elif name == "sorensen":
+        num, den = 2.0 * c, a + b
+    elif name == "cosine":
+        num, den = c, np.sqrt(a * b)
+    else:
+        raise ValueError("similarity: unknown measure %r (one of %s)" % (name, ", ".join(SIMILARITY_MEASURES)))
+    out = np.zeros(c.shape[0], dtype=np.float64)
+    np.divide(num, den, out=out, where=den > 0)
+    return out
+
+
+def validate_similarity(csr, pairs, result):
+    """Host-side check (numpy / scipy) that `result` -- the dict of Similarity.run: measure name -> array aligned with `pairs`
+    (int[m, 2]) -- holds those measures on the undirected simple graph of `csr`, as Similarity reads it (io.symmetrize_simple).
+    The statement is independent of the kernel's search: with S the symmetric 0/1 pattern as a scipy matrix of 64-bit integers,
+    the common neighbours are the row products S[u] . S[v]^T and the weighted sums S[u] . diag(w) . S[v]^T with the fixed-point
+    tables of similarity_tables (exact: every sum is below 2^63); the measures follow by similarity_measure.  Integers are
+    compared exactly and the f64 values as bits.  Raises ValueError with the first violation."""
+    import scipy.sparse as sp
+    pr = np.asarray(pairs)
+    if pr.ndim != 2 or pr.shape[1] != 2:
+        raise ValueError("validate_similarity: pairs must have the shape [m, 2], not %s" % (pr.shape,))
+    pr = pr.astype(np.int64)
+    m = pr.shape[0]
+    sym, deg = io.symmetrize_simple(csr.copy())
+    n = sym.num_rows
+    if m and (pr.min() < 0 or pr.max() >= n):
+        raise ValueError("validate_similarity: a pair names a vertex outside 0 .. %d" % (n - 1))
+    for name in result:
+        if name not in SIMILARITY_MEASURES:
+            raise ValueError("validate_similarity: unknown measure %r" % (name,))
+        if np.asarray(result[name]).shape != (m,):
+            raise ValueError("validate_similarity: %s has the shape %s for %d pairs" % (name, np.asarray(result[name]).shape, m))
+    S = _pattern_as_scipy(sym, n).astype(np.int64)
+    aa, ra, shift = similarity_tables(deg)
+    want = {"common": np.zeros(m, np.int64), "adamic_adar": np.zeros(m, np.int64), "resource_allocation": np.zeros(m, np.int64)}
+    tables = {"adamic_adar": aa, "resource_allocation": ra}
+    for b in range(0, m, 1 << 16):
+        u, v = pr[b:b + (1 << 16), 0], pr[b:b + (1 << 16), 1]
+        Su, Sv = S[u], S[v]
+        want["common"][b:b + u.shape[0]] = np.asarray(Su.multiply(Sv).sum(axis=1)).ravel()
+        for name, table in tables.items():
+            if name in result:
+                D = sp.diags(table.astype(np.int64), dtype=np.int64, format="csr")
+                want[name][b:b + u.shape[0]] = np.asarray((Su @ D).multiply(Sv).sum(axis=1)).ravel()
+    du, dv = deg[pr[:, 0]], deg[pr[:, 1]]
+    for name in result:
+        got = np.asarray(result[name])
+        exp = similarity_measure(name, want["common"], du, dv, want.get(name), shift)
+        if exp.dtype == np.float64:
+            bad = np.ascontiguousarray(got, dtype=np.float64).view(np.uint64) != exp.view(np.uint64)
+        else:
+            bad = got.astype(np.int64) != exp.astype(np.int64) if name == "common" else got.astype(np.uint64) != exp
+        if np.any(bad):
+            i = int(np.flatnonzero(bad)[0])
+            raise ValueError("validate_similarity: pair %d = (%d, %d) has %s %r, the row product gives %r (%d common neighbours, degrees %d and %d)"
+                             % (i, pr[i, 0], pr[i, 1], name, got[i].item(), exp[i].item(), want["common"][i], du[i], dv[i]))
+
+
 class ModuleCollection:
     def __init__(self):
         self.modules_ = []
@@ -3433,6 +3531,126 @@ class ClosenessCentrality(_PatternApp):
         self.periphery_ = who[ecc == self.diameter_] if src else who
         self.closeness_ = closeness_of(self.far_, self.reach_, nr, wf_improved)
         return self.closeness_
+
+
+class Similarity(_PatternApp):
+    """Neighbourhood similarity and link prediction (an extension: the reference has no such driver): gl_similarity (DESIGN.md
+    4.27), the common neighbours of caller-chosen pairs of vertices -- which need not be edges -- and their sums of a weight per
+    common neighbour.  The matrix is read as an undirected simple graph, as KCore reads it (io.symmetrize_simple).  The kernel
+    returns integers; the weighted measures travel as fixed point (similarity_tables) and every measure is computed on the host
+    in f64 from the integers (similarity_measure)."""
+    _no_shards_ = "gl_similarity reads the rows of both vertices of a pair, so every rank would need the whole symmetric matrix"
+    MEASURES = SIMILARITY_MEASURES
+    degrees_ = graph_ = shift_ = aa_ = ra_ = aa_buf_ = ra_buf_ = None
+    common_ = pairs_ = edges_ = launches_ = deferred_ = weighted_ = None
+
+    def _prepare(self, csr):
+        csr, self.degrees_ = io.symmetrize_simple(csr)
+        self.graph_ = csr
+        self.aa_, self.ra_, self.shift_ = similarity_tables(self.degrees_)
+        return csr
+
+    def send_matrix_host_to_device(self):
+        """... and the two fixed-point weight tables, n_ 64-bit words each"""
+        _PatternApp.send_matrix_host_to_device(self)
+        B, n = self.backend, self.n_
+        self.aa_buf_, self.ra_buf_ = B.alloc(2 * max(1, n), np.float32), B.alloc(2 * max(1, n), np.float32)
+        if n:
+            B.upload(self.aa_buf_, self.aa_)
+            B.upload(self.ra_buf_, self.ra_)
+
+    @classmethod
+    def _measures(cls, measures):
+        names = (measures,) if isinstance(measures, str) else tuple(measures)
+        for name in names:
+            if name not in cls.MEASURES:
+                raise ValueError("Similarity: unknown measure %r (one of %s)" % (name, ", ".join(cls.MEASURES)))
+        return names
+
+    def run(self, pairs, measures=("common", "jaccard")):
+        """-> {measure: array[m]} aligned with `pairs` (int[m, 2], real vertices; a pair may be an edge or not, u == v is legal).
+        common is uint32, preferential_attachment uint64 (no kernel), the others float64 (similarity_measure: 0.0 where a
+        denominator is 0).  gl_similarity is called once per distinct weight table needed -- at most twice, without a table
+        when neither adamic_adar nor resource_allocation is asked for.  Leaves common_ (uint32[m]), pairs_ (int64[m, 2]),
+        weighted_ ({measure: uint64[m]}, the fixed-point sums at shift_), deferred_ and launches_.  The call waits for the
+        device."""
+        names = self._measures(measures)
+        self._require_sent()
+        pr = np.asarray(pairs)
+        if pr.size == 0:
+            pr = pr.reshape(0, 2)
+        if pr.ndim != 2 or pr.shape[1] != 2 or pr.dtype.kind not in "iu":
+            raise ValueError("Similarity.run(): pairs must be an integer array of shape [m, 2]")
+        pr = pr.astype(np.int64)
+        m = pr.shape[0]
+        if m and (pr.min() < 0 or pr.max() >= self.n_real_):
+            raise ValueError("Similarity.run(): a pair names a vertex outside the real vertices 0 .. %d" % (self.n_real_ - 1))
+        if m > 0xFFFFFFFF:
+            raise ValueError("Similarity.run(): %d pairs, at most 2^32 - 1 per call" % m)
+        B = self.backend
+        tables = [(name, buf) for name, buf in (("adamic_adar", self.aa_buf_), ("resource_allocation", self.ra_buf_)) if name in names]
+        self.pairs_, self.launches_, self.deferred_, self.weighted_ = pr, 0, 0, {}
+        self.common_ = np.zeros(0, dtype=np.uint32)
+        needs_kernel = any(name != "preferential_attachment" for name in names)
+        if m and needs_kernel:
+            out = B.alloc(5 * m, np.float32)                         # (32-bit words: the weighted sums, the pairs, the counts)
+            weighted_buf, pairs_buf, common_buf = B.view(out, 0, m, 8), B.view(out, 2 * m, 2 * m, 4), B.view(out, 4 * m, m, 4)
+            B.upload(pairs_buf, pr.astype(np.uint32).ravel())
+            for name, table in tables or [(None, None)]:
+                stats = self.SpMV_.similarity(pairs_buf, common_buf, weighted_buf if table is not None else None, table, True, m)
+                self.deferred_ = stats[1]
+                self.launches_ += stats[2]
+                if name is not None:
+                    self.weighted_[name] = B.download(weighted_buf, np.uint64, m)
+            self.common_ = B.download(common_buf, np.uint32, m)
+        elif needs_kernel:
+            self.weighted_ = {name: np.zeros(0, dtype=np.uint64) for name, _ in tables}
+        du, dv = self.degrees_[pr[:, 0]], self.degrees_[pr[:, 1]]
+        return {name: similarity_measure(name, self.common_ if needs_kernel else np.zeros(m, np.uint32), du, dv,
+                                         self.weighted_.get(name), self.shift_) for name in names}
+
+    def run_edges(self, measures=("common", "jaccard")):
+        """-> run() over every edge {u, v}, u < v, of the prepared graph, ascending; leaves edges_ (int64[edges, 2])"""
+        self._measures(measures)
+        self._require_sent()
+        g = self.graph_
+        rows = np.repeat(np.arange(g.num_rows, dtype=np.int64), np.diff(g.adj_indptr.astype(np.int64)))
+        cols = g.adj_indices[:rows.shape[0]].astype(np.int64)
+        once = cols > rows
+        self.edges_ = np.stack([rows[once], cols[once]], axis=1)
+        return self.run(self.edges_, measures)
+
+    def two_hop_pairs(self, sources, limit=None):
+        """-> int64[p, 2]: the distinct pairs (s, v) with v != s, v not adjacent to s and at least one common neighbour, for the
+        given sources (real vertices), ordered by (s, v): the candidates of link prediction.  Host code (numpy on graph_, the prepared
+        matrix -- what SpMV_.csr_matrix_ holds --, no device work), meant for a handful of sources.  Raises ValueError if more than `limit` pairs would result."""
+        g = self.graph_
+        if g is None:
+            raise RuntimeError("Similarity.two_hop_pairs(): load_and_format_matrix first")
+        ip, idx = g.adj_indptr.astype(np.int64), g.adj_indices
+        src = sorted({int(s) for s in np.asarray(sources, dtype=np.int64).ravel().tolist()})
+        if src and (src[0] < 0 or src[-1] >= self.n_real_):
+            raise ValueError("Similarity.two_hop_pairs(): a source outside the real vertices 0 .. %d" % (self.n_real_ - 1))
+        parts, total = [], 0
+        for s in src:
+            near = idx[ip[s]:ip[s + 1]].astype(np.int64)
+            far = np.unique(np.concatenate([idx[ip[w]:ip[w + 1]] for w in near.tolist()] or [np.zeros(0, idx.dtype)])).astype(np.int64)
+            far = far[(far != s) & ~np.isin(far, near)]
+            total += far.shape[0]
+            if limit is not None and total > limit:
+                raise ValueError("Similarity.two_hop_pairs(): more than limit = %d pairs" % limit)
+            parts.append(np.stack([np.full(far.shape[0], s, dtype=np.int64), far], axis=1))
+        return np.concatenate(parts) if parts else np.zeros((0, 2), dtype=np.int64)
+
+    def top_k(self, source, k, measure="jaccard"):
+        """-> (vertices int64[<= k], scores): the k best link candidates of `source` among two_hop_pairs([source]) by `measure`,
+        ordered by (-score, vertex)"""
+        (name,) = self._measures((measure,))
+        self._require_sent()
+        pairs = self.two_hop_pairs([source])
+        scores = self.run(pairs, (name,))[name]
+        order = np.lexsort((pairs[:, 1], -scores.astype(np.float64)))[:max(0, int(k))]
+        return pairs[order, 1], scores[order]
 
 
 class PageRank(_GraphApp):

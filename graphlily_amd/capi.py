@@ -59,7 +59,8 @@ EXT_EXPORTS = ["gl_color"]
 EXT_HEADERS = {"graphlily_hip_ext.h": EXT_EXPORTS, "graphlily_hip_truss.h": ["gl_truss"], "graphlily_hip_msf.h": ["gl_msf"],
                "graphlily_hip_match.h": ["gl_match"], "graphlily_hip_lpa.h": ["gl_lpa"],
                "graphlily_hip_scc.h": ["gl_scc"], "graphlily_hip_louvain.h": ["gl_louvain_move"], "graphlily_hip_bicc.h": ["gl_bicc"],
-               "graphlily_hip_topo.h": ["gl_topo"], "graphlily_hip_msbfs.h": ["gl_msbfs"]}
+               "graphlily_hip_topo.h": ["gl_topo"], "graphlily_hip_msbfs.h": ["gl_msbfs"],
+               "graphlily_hip_sim.h": ["gl_similarity"]}
 
 
 class GraphLilyError(RuntimeError):
@@ -135,6 +136,7 @@ def lib():
         "gl_bicc": [vp, vp, vp, vp, vp, P(u64)],
         "gl_topo": [vp, vp, vp, vp, vp, vp, vp, P(u64)],
         "gl_msbfs": [vp, vp, u32, i32, vp, vp, vp, vp, vp, vp],
+        "gl_similarity": [vp, vp, u64, vp, vp, vp, vp],
         "gl_louvain_move": [vp, vp, vp, vp, vp, u32, u64, P(u64)],
         "gl_bc_accumulate": [vp, vp, vp, vp, ctypes.c_double, i32, vp, P(u32)],
         "gl_spmv_run": [vp, vp, vp, vp, i32, f32, i32],
@@ -649,6 +651,21 @@ class SpMVPlan:
                              1 if accumulate else 0, _p(far), _p(reach), _p(harmonic), _p(hops),
                              ctypes.c_void_p(source_stats.ctypes.data), stats))
         return source_stats[:k], tuple(int(x) for x in stats)
+
+    def similarity(self, pairs, common, weighted=None, vertex_weight=None, stats=False, count=None):
+        """gl_similarity: common[i] = |N(u_i) & N(v_i)| for the m pairs u0 v0 u1 v1 ... of `pairs` (2 m device words; `count` =
+        m, by default what the buffer holds), N(x) = row x of this plan -- a strictly ascending set: io.symmetrize_simple /
+        io.simple_pattern prepare such a matrix; on a directed pattern the common PREDECESSORS, the transposed plan gives the
+        common successors.  `common` receives m words, `weighted` (optional, m device 64-bit words; needs `vertex_weight`,
+        num_rows device 64-bit words) the sum of vertex_weight[w] over the common neighbours w in 64-bit unsigned integers,
+        wrapping modulo 2^64.  The pairs need not be edges; u == v gives the whole row; a pair with a vertex >= num_rows gets
+        0xffffffff and 0.  stats=False only enqueues and returns None; stats=True SYNCHRONISES and -> (pairs out of range,
+        pairs that took the deferred path, launches enqueued, 0)."""
+        m = int(pairs.nbytes // 8 if count is None else count)
+        out = (ctypes.c_uint64 * 4)(*([0xdeadbeefdeadbeef] * 4)) if stats else None
+        check(lib().gl_similarity(ctypes.c_void_p(self.handle), _p(pairs), ctypes.c_uint64(m), _p(vertex_weight), _p(common),
+                                  _p(weighted), out))
+        return tuple(int(x) for x in out) if stats else None
 
     def bc_accumulate(self, plan_out, level, bc, scale=1.0, accumulate=False, sigma=None, stats=True):
         """gl_bc_accumulate with this plan as plan_in (row v: the vertices v is pulled from) and `plan_out` as the transposed

@@ -1,8 +1,8 @@
 // The plain CSR row copy that a GL_PLAN_BOOLEAN plan keeps (gl_spmv_plan.h: d_csr_indptr / d_csr_indices / csr_nz_base), as the
-// graph kernels that walk it see it -- gl_bfs_parents, gl_cc, gl_tc, gl_kcore, gl_color, gl_truss, gl_bc, gl_scc, gl_bicc, gl_topo, gl_msbfs, gl_lpa, and gl_msf,
+// graph kernels that walk it see it -- gl_bfs_parents, gl_cc, gl_tc, gl_kcore, gl_color, gl_truss, gl_bc, gl_scc, gl_bicc, gl_topo, gl_msbfs, gl_sim, gl_lpa, and gl_msf,
 // gl_match and gl_louvain (which also take a value per entry of the copy from their caller): what a caller may require of it,
 // the verdicts about it that the plan caches, the few helpers every such kernel wants, and the walk over a row -- a thread per
-// row, then the wavefront -- that ten of them run and gl_bc copies (rows_walk_*, at the end; gl_tc and gl_truss intersect rows
+// row, then the wavefront -- that ten of them run and gl_bc copies (rows_walk_*, at the end; gl_tc, gl_truss and gl_sim intersect rows
 // instead).  gl_rows.hip holds the check kernels.  A new caller adds itself to tests/test_gpu_rows.py (the contract) and
 // tests/test_gpu_walk.py (the walk).
 // gl_rounds.h, on top of this, holds what the kernels that run in rounds over a queue share: the atomics of their memory rule,

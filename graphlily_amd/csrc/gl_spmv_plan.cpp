@@ -885,6 +885,7 @@ int gl_spmv_plan_destroy(gl_spmv_plan p) {
     (void)hipFree(p->d_bicc_scratch);
     (void)hipFree(p->d_topo_scratch);
     (void)hipFree(p->d_msbfs_scratch);
+    (void)hipFree(p->d_sim_scratch);
     (void)hipFree(p->d_bc_scratch);
     if (p->h_bc_pinned) (void)hipHostFree(p->h_bc_pinned);
     (void)hipFree(p->d_csr_data);

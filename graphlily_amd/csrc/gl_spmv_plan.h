@@ -287,6 +287,9 @@ struct gl_spmv_plan_s {
     // gl_msbfs (gl_msbfs.hip): the call's scratch, allocated by the first call -- 256 bytes of control record, 1280 bytes of
     // per-source counters, then three arrays of num_rows 64-bit words: the seen words and the two frontiers
     unsigned char *d_msbfs_scratch = nullptr;
+    // gl_similarity (gl_sim.hip): the call's scratch, allocated by the first call -- 256 bytes of control record and the list of
+    // deferred pairs, 2^20 words: a fixed size, the pairs are taken in chunks of at most 2^20
+    unsigned char *d_sim_scratch = nullptr;
     // gl_bc_accumulate (gl_bc.hip), as plan_in, set up by the first call: the pass's scratch -- 256 bytes of control words, two
     // arrays of num_rows + 2 level offsets, num_rows words of queue, num_rows doubles each of sigma and coef -- the page-locked
     // room the offsets are read back to, and the verdict on the last plan_out that was not this plan itself: is it the

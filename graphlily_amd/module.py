@@ -441,6 +441,21 @@ class SpMVModule(BaseModule):
         self._finish(far_buf, reach_buf, harmonic_buf, hops_buf)
         return out
 
+    def similarity(self, pairs_buf, common_buf, weighted_buf=None, vertex_weight_buf=None, stats=False, count=None):
+        """Extension (gl_similarity): common_buf[i] = the number of common neighbours of the pair (u_i, v_i) of `pairs_buf` (2 m
+        words u0 v0 u1 v1 ...; `count` = m, by default what the buffer holds) in this module's matrix, whose rows are read as
+        sets -- io.symmetrize_simple / io.simple_pattern prepare it; on a directed pattern the common predecessors.
+        `weighted_buf` (optional, m 64-bit words) receives the sum of `vertex_weight_buf` (get_num_rows() 64-bit unsigned
+        words) over the common neighbours, modulo 2^64.  The pairs need not be edges; a vertex >= get_num_rows() gives
+        0xffffffff and 0.  stats=False only enqueues; stats=True waits -> (pairs out of range, deferred pairs, launches, 0).
+        Raises GraphLilyError (GL_ERR_UNSUPPORTED) when the plan keeps no row copy (only the (||,&&) layout does), is not
+        square, is a row shard, or its rows are not strictly ascending sets."""
+        if self.plan_ is None:
+            _fatal("SpMVModule.similarity: send_matrix_host_to_device first")
+        out = self.plan_.similarity(pairs_buf, common_buf, weighted_buf, vertex_weight_buf, stats, count)
+        self._finish(common_buf, weighted_buf)
+        return out
+
     def bc_accumulate(self, out_module, level_buf, bc_buf, scale=1.0, accumulate=False, sigma_buf=None, stats=True):
         """Extension (gl_bc_accumulate): adds scale x Brandes' dependency of the search whose levels are in `level_buf`
         (get_num_rows() floats) to `bc_buf` (as many doubles; accumulate=False: overwrites it).  This module's matrix is the

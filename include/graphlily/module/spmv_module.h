@@ -20,6 +20,7 @@
 #include "graphlily_hip_bicc.h"
 #include "graphlily_hip_topo.h"
 #include "graphlily_hip_msbfs.h"
+#include "graphlily_hip_sim.h"
 #include "graphlily/io/data_formatter.h"
 #include "graphlily/io/data_loader.h"
 #include "graphlily/module/base_module.h"
@@ -327,6 +328,18 @@ public:
         barrier_();
         GRAPHLILY_CHECK(gl_msbfs(plan_, sources, k, accumulate ? 1 : 0, (uint64_t *)far.ptr(), (uint32_t *)reach.ptr(),
                                  (double *)harmonic.ptr(), hops, source_stats, stats));
+        finish_();
+    }
+    // extension (gl_similarity, graphlily_hip_sim.h): common[i] = the number of common neighbours of the pair (u_i, v_i) of `pairs`
+    // (2 m device words u0 v0 u1 v1 ...) in this module's matrix, whose rows are read as sets -- util_symmetrize_simple /
+    // util_simple_pattern prepare it, the (||,&&) layout; on a directed pattern the common predecessors.  `weighted` (m device
+    // 64-bit words, or nullptr) receives the sum of `vertex_weight` (get_num_rows() device 64-bit unsigned words) over the common
+    // neighbours, modulo 2^64.  The pairs need not be edges; a vertex >= get_num_rows() gives 0xffffffff and 0.  Without `stats`
+    // the call only enqueues; with it (4 host words: {pairs out of range, deferred pairs, launches, 0}) it waits.
+    void similarity(const uint32_t *pairs, uint64_t m, uint32_t *common, uint64_t *weighted = nullptr,
+                    const uint64_t *vertex_weight = nullptr, uint64_t *stats = nullptr) {
+        barrier_();
+        GRAPHLILY_CHECK(gl_similarity(plan_, pairs, m, vertex_weight, common, weighted, stats));
         finish_();
     }
     // extension (gl_bc_accumulate): adds scale x Brandes' dependency of the search whose levels are in `level` (get_num_rows()
