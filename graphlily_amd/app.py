@@ -279,6 +279,42 @@ def validate_triangles(csr, triangles):
     return int(want.sum()) // 3
 
 
+def validate_cliques(csr, k, cliques):
+    """Host-side check that cliques[v] is the number of k-cliques through v in the undirected simple graph of `csr` -- an edge
+    {u, v} iff u != v and a stored non-zero entry A[v, u] or A[u, v] exists, as validate_triangles reads it.  An independent
+    statement from Python sets, with no rank and no bit matrix: every clique is listed once, smallest vertex first, by
+    intersecting the sets of larger neighbours.  Raises ValueError naming the first offending vertex and both values; returns
+    the number of k-cliques.  `cliques` may be longer than the matrix (the drivers pad it): the extra vertices are in none.
+    For small graphs: the work is the number of cliques of every size up to k."""
+    if int(k) != k or k < 2:
+        raise ValueError("validate_cliques: k = %r" % (k,))
+    sym, _ = io.symmetrize_simple(csr)
+    n = sym.num_rows
+    t = np.asarray(cliques)
+    if t.ndim != 1 or t.shape[0] < n:
+        raise ValueError("validate_cliques: %s counts for a %d x %d matrix" % (list(t.shape), int(csr.num_rows), int(csr.num_cols)))
+    indptr = sym.adj_indptr.astype(np.int64)
+    above = [set(int(u) for u in sym.adj_indices[indptr[v]:indptr[v + 1]] if u > v) for v in range(n)]
+    want = [0] * t.shape[0]
+    total = 0
+    stack = [((v,), above[v]) for v in range(n)]
+    while stack:
+        prefix, cand = stack.pop()
+        if len(prefix) == k - 1:
+            for u in cand:
+                want[u] += 1
+            for u in prefix:
+                want[u] += len(cand)
+            total += len(cand)
+            continue
+        for u in cand:
+            stack.append((prefix + (u,), cand & above[u]))
+    for v in range(t.shape[0]):
+        if int(t[v]) != want[v]:
+            raise ValueError("validate_cliques: vertex %d is given %d %d-cliques, it lies in %d" % (v, int(t[v]), k, want[v]))
+    return total
+
+
 def _core_numbers_of(indptr, indices, n):
     """Core numbers of a symmetric simple CSR over n vertices: a peel by whole SETS in numpy (kept apart from the device's queue:
     validate_cores checks one with the other).  At level k every live vertex of degree <= k is removed at once, gets core k, and
@@ -2604,6 +2640,52 @@ class TriangleCount(_PatternApp):
         out = np.zeros(self.n_, dtype=np.float64)
         np.divide(2.0 * self.triangles_.astype(np.float64), pairs, out=out, where=pairs > 0)
         return out
+
+
+class CliqueCount(_PatternApp):
+    """k-clique counting, 3 <= k <= 8: gl_clique_count.  The matrix is read as an undirected simple graph, as in
+    TriangleCount, and oriented on the host by a rank (io.orient_by_rank), so that every k-clique is found exactly once, from its
+    lowest-ranked vertex, inside the bit matrix of that vertex's row."""
+    _no_shards_ = "gl_clique_count reads row u for every column u of a row, so every rank would need the whole oriented matrix"
+    degrees_ = rank_ = num_cliques_ = cliques_ = k_ = bins_ = None
+
+    def _prepare(self, csr):
+        csr, self.degrees_ = io.orient_by_rank(csr, self.rank_)
+        return csr
+
+    def load_and_format_matrix(self, csr_float_npz_path, rank=None, skip_empty_rows=True):
+        """`rank`: any unsigned integer array over the PADDED vertices (a KCore of the same matrix has as many); row v keeps the
+        neighbours u with (rank[u], u) > (rank[v], v).  None means the degrees, TriangleCount's orientation, whose rows are at
+        most about sqrt(2 m) long.  The kernel builds a bit matrix per row and refuses rows above 8192 entries; the remedy is the
+        degeneracy rank, which bounds every row by the degeneracy:
+            kc = app.KCore(...); kc.load_and_format_matrix(src); kc.send_matrix_host_to_device(); kc.run(order=True)
+            position = np.empty(kc.n_, dtype=np.uint32); position[kc.order_] = np.arange(kc.n_, dtype=np.uint32)
+            cc.load_and_format_matrix(src, rank=position)"""
+        self.rank_ = rank
+        _PatternApp.load_and_format_matrix(self, csr_float_npz_path, skip_empty_rows)
+
+    def run(self, k, per_vertex=True):
+        """-> uint64[n_]: cliques[v] = k-cliques through v (padding vertices: 0); with per_vertex=False -> the number of
+        k-cliques as an int (kernels without the per-vertex bookkeeping).  Leaves num_cliques_, cliques_ (None for a total-only
+        run), k_ and bins_ = (rows in the tiny and mid bins, rows in the wide bin, rows in the long bin, launches)."""
+        self._require_sent()
+        B, n = self.backend, self.n_
+        words = n + 1 if per_vertex else 1
+        out = B.alloc(2 * words, np.float32)      # (64-bit words: the total, then the per-vertex counts)
+        self.bins_ = self.SpMV_.clique_count(k, B.view(out, 0, 1, 8), B.view(out, 1, n, 8) if per_vertex else None, stats=True)
+        B.sync()
+        got = B.download(out, np.uint64, words)
+        self.k_ = int(k)
+        self.num_cliques_ = int(got[0])           # (the orientation gives every clique once)
+        self.cliques_ = got[1:] if per_vertex else None
+        return self.cliques_ if per_vertex else self.num_cliques_
+
+    def clique_density(self):
+        """-> float: num_cliques_ / C(n_real_, k_) of the last run, 0.0 where there is no k-subset"""
+        if self.num_cliques_ is None:
+            raise RuntimeError("CliqueCount.clique_density(): run() first")
+        subsets = math.comb(self.n_real_, self.k_)
+        return self.num_cliques_ / subsets if subsets else 0.0
 
 
 class KCore(_PatternApp):

@@ -60,7 +60,7 @@ EXT_HEADERS = {"graphlily_hip_ext.h": EXT_EXPORTS, "graphlily_hip_truss.h": ["gl
                "graphlily_hip_match.h": ["gl_match"], "graphlily_hip_lpa.h": ["gl_lpa"],
                "graphlily_hip_scc.h": ["gl_scc"], "graphlily_hip_louvain.h": ["gl_louvain_move"], "graphlily_hip_bicc.h": ["gl_bicc"],
                "graphlily_hip_topo.h": ["gl_topo"], "graphlily_hip_msbfs.h": ["gl_msbfs"],
-               "graphlily_hip_sim.h": ["gl_similarity"]}
+               "graphlily_hip_sim.h": ["gl_similarity"], "graphlily_hip_clique.h": ["gl_clique_count"]}
 
 
 class GraphLilyError(RuntimeError):
@@ -137,6 +137,7 @@ def lib():
         "gl_topo": [vp, vp, vp, vp, vp, vp, vp, P(u64)],
         "gl_msbfs": [vp, vp, u32, i32, vp, vp, vp, vp, vp, vp],
         "gl_similarity": [vp, vp, u64, vp, vp, vp, vp],
+        "gl_clique_count": [vp, u32, vp, vp, P(u64)],
         "gl_louvain_move": [vp, vp, vp, vp, vp, u32, u64, P(u64)],
         "gl_bc_accumulate": [vp, vp, vp, vp, ctypes.c_double, i32, vp, P(u32)],
         "gl_spmv_run": [vp, vp, vp, vp, i32, f32, i32],
@@ -478,6 +479,16 @@ class SpMVPlan:
         whole, its rows strictly ascending (io.triangle_orient gives each triangle once).  Both are zeroed by the call.  Enqueued;
         the plan's first call waits once."""
         check(lib().gl_tc_count(ctypes.c_void_p(self.handle), _p(total), _p(per_vertex)))
+
+    def clique_count(self, k, total, per_vertex=None, stats=False):
+        """gl_clique_count: total = the number of sequences (v1 .. vk), 3 <= k <= 8, with vj in N+(vi) for every i < j over this
+        plan's rows as sets, into the 64-bit device word `total`; `per_vertex` (optional, num_rows 64-bit words): every sequence
+        credits each of its positions.  The plan is square, whole, its rows strictly ascending (io.orient_by_rank gives each
+        k-clique once; for k = 3 both outputs are tc_count's).  Both are zeroed by the call.  Enqueued; the plan's first call
+        waits once.  stats=True -> (rows in the tiny and mid bins, rows in the wide bin, rows in the long bin, launches)."""
+        out = (ctypes.c_uint64 * 4)(*([0xdeadbeefdeadbeef] * 4)) if stats else None
+        check(lib().gl_clique_count(ctypes.c_void_p(self.handle), ctypes.c_uint32(k), _p(total), _p(per_vertex), out))
+        return tuple(int(x) for x in out) if stats else None
 
     def kcore(self, core, order=None):
         """gl_kcore: the core numbers of this plan's graph into `core` (num_rows device words) and, optionally, a peeling order

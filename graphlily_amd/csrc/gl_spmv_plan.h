@@ -290,6 +290,13 @@ struct gl_spmv_plan_s {
     // gl_similarity (gl_sim.hip): the call's scratch, allocated by the first call -- 256 bytes of control record and the list of
     // deferred pairs, 2^20 words: a fixed size, the pairs are taken in chunks of at most 2^20
     unsigned char *d_sim_scratch = nullptr;
+    // gl_clique_count (gl_clique.hip), set up by the first call: the rows of two entries and more binned by length -- row numbers
+    // of the tiny, mid, wide and long bin (clique_items[b] rows, the longest of clique_cap[b] entries rounded up to 2), longest
+    // first -- and the long bin's matrices: clique_grid_long slabs of clique_slab_words words, one per resident workgroup
+    unsigned char *d_clique_scratch = nullptr;
+    uint32_t *d_clique_slab = nullptr;
+    uint32_t clique_items[4] = {0, 0, 0, 0}, clique_cap[4] = {0, 0, 0, 0}, clique_grid_long = 0, clique_slab_words = 0;
+    bool clique_diagonal = false;   // some v is in its own row: a row shorter than k - 1 may hold a sequence
     // gl_bc_accumulate (gl_bc.hip), as plan_in, set up by the first call: the pass's scratch -- 256 bytes of control words, two
     // arrays of num_rows + 2 level offsets, num_rows words of queue, num_rows doubles each of sigma and coef -- the page-locked
     // room the offsets are read back to, and the verdict on the last plan_out that was not this plan itself: is it the

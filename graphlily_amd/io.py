@@ -8,6 +8,7 @@ Mirrors (names, argument meaning, in-place behaviour):
   util_round_csr_matrix_dim                      io/data_formatter.h:18-33
   util_normalize_csr_matrix_by_outdegree         io/data_formatter.h:36-51
   triangle_orient                                io/data_formatter.h (util_triangle_orient: an extension, no reference counterpart)
+  orient_by_rank                                 io/data_formatter.h (util_orient_by_rank: an extension, no reference counterpart)
   symmetrize_simple                              io/data_formatter.h (util_symmetrize_simple: an extension, no reference counterpart)
   symmetrize_weighted                            io/data_formatter.h (util_symmetrize_weighted: an extension, no reference counterpart)
   simple_pattern                                 io/data_formatter.h (util_simple_pattern: an extension, no reference counterpart)
@@ -104,6 +105,32 @@ def triangle_orient(csr_matrix):
         raise ValueError("triangle_orient: %d entries do not fit 32-bit offsets" % int(out_indptr[n]))
     oriented = CSRMatrix(n, n, np.ones(b.shape[0], dtype=np.float32), b.astype(np.uint32), out_indptr.astype(np.uint32))
     return oriented, deg.astype(np.uint32)
+
+
+def orient_by_rank(csr_matrix, rank=None):
+    """The matrix preparation of CliqueCount (an extension) -> (oriented CSRMatrix with every value 1, undirected degrees as
+    uint32[n]), n = max(num_rows, num_cols): triangle_orient's reading of the matrix -- zero values and the diagonal dropped,
+    the rest symmetrised and deduplicated -- oriented by a CALLER'S rank: row v keeps exactly the neighbours u with
+    (rank[u], u) > (rank[v], v), columns ascending, so ties are broken by vertex and any `rank` (an unsigned integer array over
+    the n vertices) gives an acyclic orientation, in which every k-clique appears once in gl_clique_count's set formula.
+    rank=None means the degrees: the arrays triangle_orient returns.  A vertex's position in a degeneracy ordering
+    (KCore.run(order=True): position[order_] = arange(n)) bounds every row by the degeneracy."""
+    sym, deg = symmetrize_simple(csr_matrix)
+    n = sym.num_rows
+    if rank is None:
+        rank = deg
+    rank = np.asarray(rank)
+    if rank.shape != (n,) or rank.dtype.kind != "u":
+        raise ValueError("orient_by_rank: rank must be an unsigned integer array over the %d vertices, got %s%s"
+                         % (n, rank.dtype, list(rank.shape)))
+    a = np.repeat(np.arange(n, dtype=np.int64), np.diff(sym.adj_indptr.astype(np.int64)))
+    b = sym.adj_indices.astype(np.int64)
+    up = (rank[b] > rank[a]) | ((rank[b] == rank[a]) & (b > a))
+    a, b = a[up], b[up]                                                       # (still sorted: columns ascend inside a row)
+    out_indptr = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(np.bincount(a, minlength=n), out=out_indptr[1:])
+    oriented = CSRMatrix(n, n, np.ones(b.shape[0], dtype=np.float32), b.astype(np.uint32), out_indptr.astype(np.uint32))
+    return oriented, deg
 
 
 def symmetrize_simple(csr_matrix):

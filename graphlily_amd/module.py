@@ -283,6 +283,20 @@ class SpMVModule(BaseModule):
         self.plan_.tc_count(total_buf, per_vertex_buf)
         self._finish(total_buf, per_vertex_buf)
 
+    def clique_count(self, k, total_buf, per_vertex_buf=None, stats=False):
+        """Extension (gl_clique_count): the k-clique count, 3 <= k <= 8, of this module's matrix -- rows as strictly ascending
+        sets N+(v), total = the sequences (v1 .. vk) with vj in N+(vi) for every i < j -- into the 64-bit word `total_buf`;
+        `per_vertex_buf` (optional, get_num_rows() 64-bit words) gets one credit per position of every sequence.  stats=True ->
+        (rows in the tiny and mid bins, rows in the wide bin, rows in the long bin, launches).  Raises GraphLilyError
+        (GL_ERR_UNSUPPORTED) when the plan keeps no row copy (only the (||,&&) layout does), is not square, is a row shard, its
+        rows are no such sets (io.orient_by_rank prepares them), or a row has more than 8192 entries (orient by a degeneracy
+        rank); GL_ERR_INVALID_ARG for any other k."""
+        if self.plan_ is None:
+            _fatal("SpMVModule.clique_count: send_matrix_host_to_device first")
+        out = self.plan_.clique_count(k, total_buf, per_vertex_buf, stats)
+        self._finish(total_buf, per_vertex_buf)
+        return out
+
     def kcore(self, core_buf, order_buf=None):
         """Extension (gl_kcore): the core numbers of this module's matrix, read as a graph -- rows as strictly ascending sets
         N(v), the pattern symmetric -- into `core_buf` (get_num_rows() words) and, optionally, a peeling order into `order_buf`

@@ -78,6 +78,47 @@ CSRMatrix<data_type> util_triangle_orient(CSRMatrix<data_type> const &m, std::ve
     return out;
 }
 
+// The matrix preparation of app::CliqueCount (an extension): util_triangle_orient's reading of m, oriented by a CALLER'S rank.  Row
+// v of the result keeps exactly the neighbours u with (rank[u], u) > (rank[v], v), columns ascending, every value 1: ties are
+// broken by vertex, so any rank over the n vertices gives an acyclic orientation, in which every k-clique appears once in
+// gl_clique_count's set formula.  An EMPTY rank means the degrees: util_triangle_orient's result.  A vertex's position in a
+// degeneracy ordering bounds every row by the degeneracy.  `degrees` receives the undirected degrees; apply after padding.
+template <typename data_type>
+CSRMatrix<data_type> util_orient_by_rank(CSRMatrix<data_type> const &m, std::vector<uint32_t> const &rank, std::vector<uint32_t> &degrees) {
+    const uint64_t n = std::max(m.num_rows, m.num_cols);
+    if (!rank.empty() && rank.size() != n) {
+        printf("util_orient_by_rank: %zu ranks for %llu vertices\n", rank.size(), (unsigned long long)n);
+        exit(EXIT_FAILURE);
+    }
+    std::vector<uint64_t> key;
+    key.reserve(2 * (size_t)m.adj_indptr[m.num_rows]);
+    for (uint32_t v = 0; v < m.num_rows; v++)
+        for (uint32_t i = m.adj_indptr[v]; i < m.adj_indptr[v + 1]; i++) {
+            const uint64_t u = m.adj_indices[i];
+            if (u == v || m.adj_data[i] == data_type(0)) continue;
+            key.push_back(v * n + u);
+            key.push_back(u * n + v);
+        }
+    std::sort(key.begin(), key.end());
+    key.erase(std::unique(key.begin(), key.end()), key.end());
+    degrees.assign(n, 0);
+    for (uint64_t k : key) degrees[k / n]++;
+    std::vector<uint32_t> const &r = rank.empty() ? degrees : rank;
+    CSRMatrix<data_type> out;
+    out.num_rows = out.num_cols = (uint32_t)n;
+    out.adj_indptr.assign(n + 1, 0);
+    for (uint64_t k : key) {      // (sorted by (row, column): the kept columns of a row ascend)
+        const uint64_t a = k / n, b = k % n;
+        if (r[b] > r[a] || (r[b] == r[a] && b > a)) {
+            out.adj_indices.push_back((uint32_t)b);
+            out.adj_indptr[a + 1]++;
+        }
+    }
+    for (uint64_t v = 0; v < n; v++) out.adj_indptr[v + 1] += out.adj_indptr[v];
+    out.adj_data.assign(out.adj_indices.size(), data_type(1));
+    return out;
+}
+
 // The matrix preparation of app::KCore (an extension): the undirected simple graph of m -- an edge {u, v} iff u != v and a
 // stored non-zero entry A[v,u] or A[u,v] exists -- stored in BOTH directions, once each: row v of the result lists the
 // neighbours of v, columns ascending, every value 1; `degrees` receives the row lengths.  n = max(num_rows, num_cols); apply

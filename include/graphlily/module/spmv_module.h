@@ -21,6 +21,7 @@
 #include "graphlily_hip_topo.h"
 #include "graphlily_hip_msbfs.h"
 #include "graphlily_hip_sim.h"
+#include "graphlily_hip_clique.h"
 #include "graphlily/io/data_formatter.h"
 #include "graphlily/io/data_loader.h"
 #include "graphlily/module/base_module.h"
@@ -199,6 +200,16 @@ public:
     void tc_count(DeviceBuffer total, uint64_t *per_vertex = nullptr) {
         barrier_();
         GRAPHLILY_CHECK(gl_tc_count(plan_, (uint64_t *)total.ptr(), per_vertex));
+        finish_();
+    }
+    // extension (gl_clique_count, graphlily_hip_clique.h): the k-clique count, 3 <= k <= 8, of this module's matrix -- rows as
+    // strictly ascending sets N+(v), total = the sequences (v1 .. vk) with vj in N+(vi) for every i < j -- into the 64-bit word
+    // `total`; `per_vertex` (optional, get_num_rows() 64-bit device words) gets one credit per position of every sequence;
+    // `stats` (optional, 4 host words): rows in the tiny and mid bins, in the wide bin, in the long bin, launches.  The matrix is
+    // square and whole, in the (||,&&) layout (graphlily::io::util_orient_by_rank prepares it).
+    void clique_count(uint32_t k, DeviceBuffer total, uint64_t *per_vertex = nullptr, uint64_t *stats = nullptr) {
+        barrier_();
+        GRAPHLILY_CHECK(gl_clique_count(plan_, k, (uint64_t *)total.ptr(), per_vertex, stats));
         finish_();
     }
     // extension (gl_kcore): the core numbers of this module's matrix, read as a graph -- rows as strictly ascending sets N(v),
