@@ -315,6 +315,56 @@ def validate_cliques(csr, k, cliques):
     return total
 
 
+def validate_spgemm(a, b, c, semiring, mask=None, complement=False):
+    """Host-side check that the CSR `c` is A (+).(x) B as include/graphlily_hip_spgemm.h defines it: a plain row loop over
+    Python ints and f64, no other code of the library.  `a`, `b` (None: a) and `mask` (None: no mask) are square CSRs over the
+    same vertices whose rows hold every column once; `semiring` is a SemiringType or its op.  The PATTERN must be exactly the
+    structural one -- row i holds column j iff some k has (i, k) in a and (k, j) in b and the mask admits (i, j): stored in
+    `mask`, with complement=True not stored -- with the columns of every row strictly ascending.  The VALUES: (||,&&) 1.0;
+    (min,+) the minimum of the f32 sums a + b, to the bit; (+,x) within 2^-24 |ref| + p 2^-52 sum|a b| + 2^-149 of ref, the
+    math.fsum of the p exact f64 products -- one f32 rounding on top of an f64 sum in any order.  Raises ValueError naming
+    the first offending row; returns nnz(C)."""
+    op = getattr(semiring, "op", semiring)
+    b = a if b is None else b
+    n = a.num_rows
+    if not (a.num_cols == n and b.num_rows == n and b.num_cols == n and c.num_rows == n and (mask is None or mask.num_rows == n)):
+        raise ValueError("validate_spgemm: the matrices are not square over the same %d vertices" % n)
+    ap, bp, cp = (m.adj_indptr.astype(np.int64) for m in (a, b, c))
+    mp = mask.adj_indptr.astype(np.int64) if mask is not None else None
+    if int(cp[0]) != 0 or cp.shape[0] != n + 1:
+        raise ValueError("validate_spgemm: c.adj_indptr does not start at 0 with %d words" % (n + 1))
+    for i in range(n):
+        terms = {}
+        for e in range(ap[i], ap[i + 1]):
+            k, av = int(a.adj_indices[e]), a.adj_data[e]
+            for f in range(bp[k], bp[k + 1]):
+                terms.setdefault(int(b.adj_indices[f]), []).append((av, b.adj_data[f]))
+        if mask is not None:
+            stored = set(int(j) for j in mask.adj_indices[mp[i]:mp[i + 1]])
+            terms = {j: t for j, t in terms.items() if (j in stored) != bool(complement)}
+        want = sorted(terms)
+        got = [int(j) for j in c.adj_indices[cp[i]:cp[i + 1]]]
+        if got != want:
+            if sorted(got) == want:
+                raise ValueError("validate_spgemm: the columns of row %d do not ascend: %s" % (i, got[:16]))
+            missing, extra = sorted(set(want) - set(got)), sorted(set(got) - set(want))
+            raise ValueError("validate_spgemm: row %d: missing columns %s, columns that do not belong %s" % (i, missing[:8], extra[:8]))
+        for j, v in zip(want, c.adj_data[cp[i]:cp[i + 1]]):
+            t = terms[j]
+            if op == M.kLogicalAndOr:
+                ok, ref = float(v) == 1.0, 1.0
+            elif op == M.kAddMin:
+                ref = min(np.float32(x) + np.float32(y) for x, y in t)
+                ok = np.float32(v) == ref
+            else:
+                prods = [float(x) * float(y) for x, y in t]
+                ref = math.fsum(prods)
+                ok = abs(float(v) - ref) <= 2.0 ** -24 * abs(ref) + len(t) * 2.0 ** -52 * math.fsum(abs(q) for q in prods) + 2.0 ** -149
+            if not ok:
+                raise ValueError("validate_spgemm: C[%d, %d] is %r, the %d products give %r" % (i, j, float(v), len(t), float(ref)))
+    return int(cp[n])
+
+
 def _core_numbers_of(indptr, indices, n):
     """Core numbers of a symmetric simple CSR over n vertices: a peel by whole SETS in numpy (kept apart from the device's queue:
     validate_cores checks one with the other).  At level k every live vertex of degree <= k is removed at once, gets core k, and
@@ -2686,6 +2736,64 @@ class CliqueCount(_PatternApp):
             raise RuntimeError("CliqueCount.clique_density(): run() first")
         subsets = math.comb(self.n_real_, self.k_)
         return self.num_cliques_ / subsets if subsets else 0.0
+
+
+class TwoHop:
+    """Two-hop neighbourhoods of a simple undirected graph (an extension: the reference has no such driver): one masked product
+    A A of gl_spgemm on ONE SpGEMMModule: one plan of the graph, two masks.  The matrix is read as KCore reads it (io.symmetrize_simple):
+    duplicates, the diagonal, zero-valued entries and direction are ignored.
+      run("paths")       -> CSR: the number of paths of length two between every pair of DISTINCT vertices that has one,
+                            adjacent or not: A A under (+,x) on all-ones values, masked by the complement of the identity
+      run("candidates")  -> CSR: the pattern of the pairs at distance exactly two: A A under (||,&&), masked by the complement
+                            of A + I.  Row s holds what Similarity.two_hop_pairs([s]) lists on the host."""
+    SEMIRINGS = {"paths": M.ArithmeticSemiring, "candidates": M.LogicalSemiring}
+
+    def __init__(self):
+        self.graph_ = self.degrees_ = self.n_ = self.stats_ = None
+        self.SpGEMM_ = M.SpGEMMModule()
+        self.sent_ = False
+
+    def set_up_runtime(self, xclbin_file_path=None):
+        self.SpGEMM_.set_up_runtime(xclbin_file_path)
+
+    def load_and_format_matrix(self, csr_float_npz_path):
+        src = csr_float_npz_path
+        csr = io.load_csr_matrix_from_float_npz(src) if isinstance(src, (str, bytes)) else src.copy()
+        self.graph_, self.degrees_ = io.symmetrize_simple(csr)
+        self.n_ = self.graph_.num_rows
+        self.SpGEMM_.load_and_format_matrices(self.graph_)
+        for what in self.SEMIRINGS:
+            self.SpGEMM_.load_mask_matrix(self._mask(what), what)
+        self.sent_ = False
+
+    def _mask(self, what):
+        """-> CSR: the identity, for "candidates" joined with the graph"""
+        g, n = self.graph_, self.n_
+        eye = np.arange(n, dtype=np.int64)
+        if what == "paths":
+            return io.CSRMatrix(n, n, np.ones(n, np.float32), eye, np.arange(n + 1))
+        rows = np.concatenate([np.repeat(eye, np.diff(g.adj_indptr.astype(np.int64))), eye])
+        key = np.unique(rows * n + np.concatenate([g.adj_indices.astype(np.int64), eye]))
+        indptr = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(np.bincount(key // max(n, 1), minlength=n), out=indptr[1:])
+        return io.CSRMatrix(n, n, np.ones(key.shape[0], np.float32), key % max(n, 1), indptr)
+
+    def send_matrix_host_to_device(self):
+        self.SpGEMM_.set_up_runtime()
+        self.SpGEMM_.send_matrices_host_to_device()
+        self.sent_ = True
+
+    def run(self, what="candidates"):
+        if what not in self.SEMIRINGS:
+            raise ValueError("TwoHop.run(): %r is neither \"paths\" nor \"candidates\"" % (what,))
+        if not self.sent_:
+            raise RuntimeError("TwoHop.run(): send_matrix_host_to_device first")
+        m = self.SpGEMM_
+        m.set_semiring(self.SEMIRINGS[what])
+        m.set_mask_type(M.kMaskWriteToZero, what)
+        m.run()
+        self.stats_ = m.stats_
+        return m.send_results_device_to_host()
 
 
 class KCore(_PatternApp):

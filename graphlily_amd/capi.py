@@ -60,7 +60,8 @@ EXT_HEADERS = {"graphlily_hip_ext.h": EXT_EXPORTS, "graphlily_hip_truss.h": ["gl
                "graphlily_hip_match.h": ["gl_match"], "graphlily_hip_lpa.h": ["gl_lpa"],
                "graphlily_hip_scc.h": ["gl_scc"], "graphlily_hip_louvain.h": ["gl_louvain_move"], "graphlily_hip_bicc.h": ["gl_bicc"],
                "graphlily_hip_topo.h": ["gl_topo"], "graphlily_hip_msbfs.h": ["gl_msbfs"],
-               "graphlily_hip_sim.h": ["gl_similarity"], "graphlily_hip_clique.h": ["gl_clique_count"]}
+               "graphlily_hip_sim.h": ["gl_similarity"], "graphlily_hip_clique.h": ["gl_clique_count"],
+               "graphlily_hip_spgemm.h": ["gl_spgemm_numeric", "gl_spgemm_symbolic"]}
 
 
 class GraphLilyError(RuntimeError):
@@ -138,6 +139,8 @@ def lib():
         "gl_msbfs": [vp, vp, u32, i32, vp, vp, vp, vp, vp, vp],
         "gl_similarity": [vp, vp, u64, vp, vp, vp, vp],
         "gl_clique_count": [vp, u32, vp, vp, P(u64)],
+        "gl_spgemm_symbolic": [vp, vp, vp, u32, vp, P(u64)],
+        "gl_spgemm_numeric": [vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, P(u64)],
         "gl_louvain_move": [vp, vp, vp, vp, vp, u32, u64, P(u64)],
         "gl_bc_accumulate": [vp, vp, vp, vp, ctypes.c_double, i32, vp, P(u32)],
         "gl_spmv_run": [vp, vp, vp, vp, i32, f32, i32],
@@ -378,6 +381,7 @@ GL_PLAN_DEVICE_FORMAT = 16
 GL_PLAN_REFERENCE_ORDER = 32
 PLAN_ARRAYS = {"entries": 0, "bases": 1, "units": 2, "hub_rows": 3, "spans": 4, "hot": 5, "hot_hdr": 6, "present": 7}
 GL_ERR_UNSUPPORTED = -5
+GL_SPGEMM_MASK_COMPLEMENT = 1     # graphlily_hip_spgemm.h
 
 
 class _PlanDesc(ctypes.Structure):
@@ -488,6 +492,27 @@ class SpMVPlan:
         waits once.  stats=True -> (rows in the tiny and mid bins, rows in the wide bin, rows in the long bin, launches)."""
         out = (ctypes.c_uint64 * 4)(*([0xdeadbeefdeadbeef] * 4)) if stats else None
         check(lib().gl_clique_count(ctypes.c_void_p(self.handle), ctypes.c_uint32(k), _p(total), _p(per_vertex), out))
+        return tuple(int(x) for x in out) if stats else None
+
+    def spgemm_symbolic(self, b, c_indptr, mask=None, complement=False):
+        """gl_spgemm_symbolic: the row offsets of C = self (+).(x) b into `c_indptr` (num_rows + 1 device words); `mask` (a plan,
+        optional) admits (i, j) where it stores it, with complement=True where it does not.  All plans are square, whole, over
+        the same vertices, their rows strictly ascending.  Waits.  -> (nnz(C), products, rows that took the workgroup path, rows
+        that took the slab path)."""
+        out = (ctypes.c_uint64 * 4)(*([0xdeadbeefdeadbeef] * 4))
+        check(lib().gl_spgemm_symbolic(ctypes.c_void_p(self.handle), ctypes.c_void_p(b.handle), ctypes.c_void_p(mask.handle if mask else 0),
+                                       ctypes.c_uint32(GL_SPGEMM_MASK_COMPLEMENT if complement else 0), _p(c_indptr), out))
+        return tuple(int(x) for x in out)
+
+    def spgemm_numeric(self, b, semiring, a_val, b_val, c_indptr, c_indices, c_val, mask=None, complement=False, stats=False):
+        """gl_spgemm_numeric: the columns (ascending in every row) and values of C = self (+).(x) b into `c_indices` / `c_val`
+        (nnz(C) words each), from the `c_indptr` that spgemm_symbolic wrote for the same plans and mask.  `a_val` / `b_val`: an
+        f32 per entry of each plan's rows; `semiring` a GL_OP_*; under GL_OP_ANDOR all three value buffers may be None.
+        Enqueued, unless stats=True -> the four figures of spgemm_symbolic, the paths now chosen by |C(i)|."""
+        out = (ctypes.c_uint64 * 4)(*([0xdeadbeefdeadbeef] * 4)) if stats else None
+        check(lib().gl_spgemm_numeric(ctypes.c_void_p(self.handle), ctypes.c_void_p(b.handle), ctypes.c_void_p(mask.handle if mask else 0),
+                                      ctypes.c_uint32(GL_SPGEMM_MASK_COMPLEMENT if complement else 0), ctypes.c_uint32(semiring),
+                                      _p(a_val), _p(b_val), _p(c_indptr), _p(c_indices), _p(c_val), out))
         return tuple(int(x) for x in out) if stats else None
 
     def kcore(self, core, order=None):

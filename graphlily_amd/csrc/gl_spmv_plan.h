@@ -297,6 +297,15 @@ struct gl_spmv_plan_s {
     uint32_t *d_clique_slab = nullptr;
     uint32_t clique_items[4] = {0, 0, 0, 0}, clique_cap[4] = {0, 0, 0, 0}, clique_grid_long = 0, clique_slab_words = 0;
     bool clique_diagonal = false;   // some v is in its own row: a row shorter than k - 1 may hold a sequence
+    // gl_spgemm_* (gl_spgemm.hip), as plan a, set up by the first call with a partner b (remembered by handle and uid, as
+    // bc_partner below) and redone for another: the scratch -- 256 bytes of control words, the rows' product bounds, the words of
+    // gl_compact.h's block counts and six bin lists of num_rows + 1 records (symbolic by the bound: wavefront, workgroup, slab;
+    // the same three per numeric call by |C(i)|) --, the slabs of the slab path, and what the host keeps: the bins' sizes, the
+    // sum of the bounds, the knobs the first call read
+    unsigned char *d_spgemm_scratch = nullptr, *d_spgemm_slab = nullptr;
+    const gl_spmv_plan_s *spgemm_partner = nullptr;
+    uint64_t spgemm_partner_uid = 0, spgemm_products = 0;
+    uint32_t spgemm_bins[3] = {0, 0, 0}, spgemm_wave_slots = 0, spgemm_lds_slots = 0, spgemm_group = 0, spgemm_slabs = 0;
     // gl_bc_accumulate (gl_bc.hip), as plan_in, set up by the first call: the pass's scratch -- 256 bytes of control words, two
     // arrays of num_rows + 2 level offsets, num_rows words of queue, num_rows doubles each of sigma and coef -- the page-locked
     // room the offsets are read back to, and the verdict on the last plan_out that was not this plan itself: is it the

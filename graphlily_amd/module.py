@@ -505,6 +505,119 @@ class SpMVModule(BaseModule):
         return self.results_buf.read(np.float32, self.get_num_rows())
 
 
+class SpGEMMModule(BaseModule):
+    """Extension (gl_spgemm_symbolic / gl_spgemm_numeric): C = A (+).(x) B with a sparse result, under the three
+    semirings, with an optional structural mask.  The interface mirrors SpMVModule's.  A, B and the mask are square matrices over
+    the same vertices.  The plans are boolean plans of all-ones values -- a zero VALUE is a legitimate value here, and the row
+    copy would store it as no entry -- and the values travel in buffers of their own, in the order of the sorted rows."""
+
+    def __init__(self):
+        super().__init__()
+        self.semiring_ = ArithmeticSemiring
+        self.mask_type_ = kNoMask
+        self.mask_slot_ = 0
+        self.a_ = self.b_ = None                                   # host CSRs, rows strictly ascending
+        self.masks_, self.plan_masks_ = {}, {}                     # by slot
+        self.plan_a_ = self.plan_b_ = None
+        self.a_val_buf = self.b_val_buf = None
+        self.c_indptr_buf = self.c_indices_buf = self.c_val_buf = None
+        self.nnz_ = 0
+        self.stats_ = None
+
+    def set_semiring(self, semiring):
+        self.semiring_ = semiring
+
+    def set_mask_type(self, mask_type, slot=0):
+        """kNoMask; kMaskWriteToOne: C is written where the matrix of load_mask_matrix(csr, slot) stores an entry;
+        kMaskWriteToZero: where it stores none (the complement) -- SpMVModule's reading of the two, with "stored" for
+        "non-zero"."""
+        assert mask_type in (kNoMask, kMaskWriteToZero, kMaskWriteToOne)
+        self.mask_type_, self.mask_slot_ = mask_type, slot
+
+    @staticmethod
+    def _sorted_rows(csr, who):
+        """-> the square matrix with the columns of every row ascending, the values carried along; duplicates are refused"""
+        n = int(csr.num_rows)
+        if n != int(csr.num_cols):
+            raise ValueError("SpGEMMModule.%s: a %d x %d matrix: rectangular operands are out of scope" % (who, n, int(csr.num_cols)))
+        indptr = np.asarray(csr.adj_indptr).astype(np.int64)[:n + 1]
+        nnz = int(indptr[-1])
+        key = np.repeat(np.arange(n, dtype=np.int64), np.diff(indptr)) * n + np.asarray(csr.adj_indices[:nnz]).astype(np.int64)
+        order = np.argsort(key, kind="stable")
+        key = key[order]
+        if np.any(key[1:] == key[:-1]):
+            j = int(np.flatnonzero(key[1:] == key[:-1])[0])
+            raise ValueError("SpGEMMModule.%s: entry (%d, %d) is stored twice" % (who, key[j] // n, key[j] % n))
+        return type(csr)(n, n, np.asarray(csr.adj_data[:nnz], dtype=np.float32)[order], (key % max(n, 1)).astype(np.uint32), indptr.astype(np.uint32))
+
+    def get_num_rows(self):
+        return self.a_.num_rows
+
+    def load_and_format_matrices(self, a_csr, b_csr=None):
+        """b_csr=None: C = A (+).(x) A on one plan"""
+        self.a_ = self._sorted_rows(a_csr, "load_and_format_matrices")
+        self.b_ = self.a_ if b_csr is None else self._sorted_rows(b_csr, "load_and_format_matrices")
+        if self.b_.num_rows != self.a_.num_rows:
+            raise ValueError("SpGEMMModule.load_and_format_matrices: %d and %d vertices" % (self.a_.num_rows, self.b_.num_rows))
+
+    def load_mask_matrix(self, csr, slot=0):
+        """several masks may be loaded, one per slot: they share the plans of A and B"""
+        self.masks_[slot] = self._sorted_rows(csr, "load_mask_matrix")
+
+    @staticmethod
+    def _ones_plan(m):
+        return capi.SpMVPlan(m.num_rows, m.num_cols, m.adj_indptr, m.adj_indices, np.ones(m.adj_indices.shape[0], dtype=np.float32), 0,
+                             m.num_rows, capi.GL_PLAN_BOOLEAN | capi.GL_PLAN_NO_MULADD)
+
+    def send_matrices_host_to_device(self):
+        self.plan_a_ = self._ones_plan(self.a_)
+        self.a_val_buf = capi.DeviceBuffer.from_host(self.a_.adj_data if self.a_.adj_data.shape[0] else np.zeros(1, np.float32))
+        if self.b_ is self.a_:
+            self.plan_b_, self.b_val_buf = self.plan_a_, self.a_val_buf
+        else:
+            self.plan_b_ = self._ones_plan(self.b_)
+            self.b_val_buf = capi.DeviceBuffer.from_host(self.b_.adj_data if self.b_.adj_data.shape[0] else np.zeros(1, np.float32))
+        self.plan_masks_ = {}
+        for slot, mask in self.masks_.items():
+            if mask.num_rows != self.a_.num_rows:
+                raise ValueError("SpGEMMModule: a mask is over %d vertices, the operands over %d" % (mask.num_rows, self.a_.num_rows))
+            self.plan_masks_[slot] = self._ones_plan(mask)
+        self._finish(self.a_val_buf, self.b_val_buf)
+
+    def run(self):
+        """symbolic, then the buffers of C, then numeric.  Leaves nnz_ and stats_ = (nnz(C), products, rows that took the
+        workgroup path, rows that took the slab path) of the symbolic call.  NaN values are refused under every semiring,
+        +-inf under (+,x) (ValueError)."""
+        if self.plan_a_ is None:
+            _fatal("SpGEMMModule.run: send_matrices_host_to_device first")
+        op = self.semiring_.op
+        for name, m in (("A", self.a_), ("B", self.b_)):
+            if op != kLogicalAndOr and (np.isnan(m.adj_data).any() or (op == kMulAdd and np.isinf(m.adj_data).any())):
+                raise ValueError("SpGEMMModule.run: %s holds a NaN%s value" % (name, " or an infinite" if op == kMulAdd else ""))
+        mask = None
+        if self.mask_type_ != kNoMask:
+            if self.mask_slot_ not in self.plan_masks_:
+                _fatal("SpGEMMModule.run: load_mask_matrix before send_matrices_host_to_device")
+            mask = self.plan_masks_[self.mask_slot_]
+        complement = self.mask_type_ == kMaskWriteToZero
+        n = self.a_.num_rows
+        self.c_indptr_buf = capi.DeviceBuffer(4 * (n + 1))
+        self.stats_ = self.plan_a_.spgemm_symbolic(self.plan_b_, self.c_indptr_buf, mask, complement)
+        self.nnz_ = self.stats_[0]
+        self.c_indices_buf = capi.DeviceBuffer(4 * max(1, self.nnz_))
+        self.c_val_buf = capi.DeviceBuffer(4 * max(1, self.nnz_))
+        self.plan_a_.spgemm_numeric(self.plan_b_, op, self.a_val_buf, self.b_val_buf, self.c_indptr_buf, self.c_indices_buf, self.c_val_buf,
+                                    mask, complement)
+        self._finish(self.c_indptr_buf, self.c_indices_buf, self.c_val_buf)
+
+    def send_results_device_to_host(self):
+        """-> io.CSRMatrix: C, the columns of every row ascending; under (||,&&) every value is 1"""
+        from . import io
+        n = self.a_.num_rows
+        return io.CSRMatrix(n, n, self.c_val_buf.read(np.float32, self.nnz_), self.c_indices_buf.read(np.uint32, self.nnz_),
+                            self.c_indptr_buf.read(np.uint32, n + 1))
+
+
 class SpMSpVModule(BaseModule):
     def __init__(self, out_buf_len=0):
         super().__init__()
