@@ -365,6 +365,57 @@ def validate_spgemm(a, b, c, semiring, mask=None, complement=False):
     return int(cp[n])
 
 
+def _quotient_of(graph, labels, weights, vertex_weights):
+    """The DIRECTED statement of the quotient, by np.unique on keys -> io.aggregate_communities' tuple.  `graph`: a simple
+    pattern without diagonal (io.simple_pattern's csr_in); an entry (v, u) gives (part[v], part[u])."""
+    n = int(graph.num_rows)
+    indptr = graph.adj_indptr.astype(np.int64)[:n + 1]
+    rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(indptr))
+    cols = graph.adj_indices[:int(indptr[-1])].astype(np.int64)
+    w = np.ones(cols.shape[0], dtype=np.int64) if weights is None else np.asarray(weights).astype(np.int64)
+    kv = np.bincount(rows[rows != cols], w[rows != cols], n).astype(np.int64) if vertex_weights is None else np.asarray(vertex_weights).astype(np.int64)
+    _, part = np.unique(np.asarray(labels), return_inverse=True)
+    part = part.astype(np.int64).reshape(n)
+    k = int(part.max()) + 1 if n else 0
+    a, b = part[rows], part[cols]
+    key, inverse = np.unique(a[a != b] * k + b[a != b], return_inverse=True)
+    wsum = np.bincount(inverse.reshape(-1), w[a != b], key.shape[0]).astype(np.int64)
+    tot = np.bincount(part, kv, k).astype(np.int64)
+    if (wsum.size and int(wsum.max()) > 0xFFFFFFFF) or (k and int(tot.max()) > 0xFFFFFFFF):
+        raise ValueError("validate_quotient: a summed weight does not fit 32 bits")
+    indptr_c = np.zeros(k + 1, dtype=np.int64)
+    np.cumsum(np.bincount(key // max(k, 1), minlength=k), out=indptr_c[1:])
+    c = io.CSRMatrix(k, k, np.ones(key.shape[0], dtype=np.float32), (key % max(k, 1)).astype(np.uint32), indptr_c.astype(np.uint32))
+    return c, wsum.astype(np.uint32), tot.astype(np.uint32), part.astype(np.uint32)
+
+
+def validate_quotient(csr, labels, result, directed=None, weights=None, vertex_weights=None):
+    """Host-side check that `result` -- (CSRMatrix, uint32 weights, uint32 tot, community_of), QuotientGraph.run's tuple -- is
+    the quotient of the simple graph of `csr` by `labels` (one per vertex), recomputed on the host: the undirected reading
+    (directed=False; None: iff the pattern is symmetric, as QuotientGraph decides) by io.aggregate_communities on
+    io.symmetrize_simple's matrix, the directed one by a np.unique over the keys part[v] k + part[u] of io.simple_pattern's
+    entries.  `weights` / `vertex_weights` as in QuotientGraph.run.  Every array must be equal.  Raises ValueError naming the
+    first array that differs; returns the number of groups."""
+    cin, _, symmetric = io.simple_pattern(csr)
+    directed = (not symmetric) if directed is None else bool(directed)
+    lab = np.asarray(labels)
+    if directed:
+        want = _quotient_of(cin, lab, weights, vertex_weights)
+    else:
+        want = io.aggregate_communities(io.symmetrize_simple(csr)[0], weights, vertex_weights, lab)
+    got_c, want_c = result[0], want[0]
+    pairs = (("adj_indptr", got_c.adj_indptr, want_c.adj_indptr), ("adj_indices", got_c.adj_indices, want_c.adj_indices),
+             ("weights", result[1], want[1]), ("tot", result[2], want[2]), ("community_of", result[3], want[3]))
+    for name, got, ref in pairs:
+        got, ref = np.asarray(got), np.asarray(ref)
+        if got.shape != ref.shape:
+            raise ValueError("validate_quotient: %s has %s words, the host finds %s" % (name, got.shape, ref.shape))
+        if not np.array_equal(got, ref):
+            at = int(np.flatnonzero(got != ref)[0])
+            raise ValueError("validate_quotient: %s[%d] is %d, the host finds %d" % (name, at, int(got[at]), int(ref[at])))
+    return int(want_c.num_rows)
+
+
 def _core_numbers_of(indptr, indices, n):
     """Core numbers of a symmetric simple CSR over n vertices: a peel by whole SETS in numpy (kept apart from the device's queue:
     validate_cores checks one with the other).  At level k every live vertex of degree <= k is removed at once, gets core k, and
@@ -1086,13 +1137,13 @@ def _smallest_member_labels(community_of, n):
     return smallest[community_of].astype(np.uint32)
 
 
-def _louvain_levels(sym, degrees, move, color, tol, max_sweeps, max_levels):
+def _louvain_levels(sym, degrees, move, color, tol, max_sweeps, max_levels, aggregate=None):
     """Louvain's level loop, shared by the driver (move and color run on the device) and the host model (they run on the
     host) -> a dict of the results.  move(level, graph, weights, k, colors, min_gain) -> (labels, sweeps, moves, evaluations,
     launches-or-0, reason, q_first, q_last); color(level, graph, degrees) -> (colors, num_colors).  Level 0 is `sym` with every
     weight 1 and k = degrees; a level is ACCEPTED iff it moved something and its q_last is strictly above the last accepted Q
     (at the start: the singletons' Q); otherwise it is discarded and the run ends, as it does when a level merges nothing or
-    max_levels is reached."""
+    max_levels is reached.  aggregate(level, graph, weights, k, labels) -> io.aggregate_communities' tuple (None: that function)."""
     n = sym.num_rows
     graph, weights, k = sym, None, np.asarray(degrees).astype(np.uint32)
     community_of = np.arange(n, dtype=np.int64)
@@ -1116,7 +1167,10 @@ def _louvain_levels(sym, degrees, move, color, tol, max_sweeps, max_levels):
         if moves == 0 or int(q_last) <= accepted:
             break
         accepted = int(q_last)
-        smaller, weights, k, part = io.aggregate_communities(graph, weights, k, labels[:graph.num_rows])
+        if aggregate is None:
+            smaller, weights, k, part = io.aggregate_communities(graph, weights, k, labels[:graph.num_rows])
+        else:
+            smaller, weights, k, part = aggregate(level, graph, weights, k, labels[:graph.num_rows])
         community_of = part.astype(np.int64)[community_of]
         out["dendrogram"].append(community_of.astype(np.uint32))
         out["levels"] += 1
@@ -3120,7 +3174,7 @@ class Louvain(_PatternApp):
         self.labels_ = None
         return self.graph_
 
-    def run(self, tol=1e-7, max_sweeps=100, max_levels=32, order="largest_first", seed=0):
+    def run(self, tol=1e-7, max_sweeps=100, max_levels=32, order="largest_first", seed=0, aggregate="device"):
         """-> uint32[n_]: labels[v] = the SMALLEST original vertex of v's community (ConnectedComponents' convention; isolated
         and padding vertices keep their own numbers).  Level 0 runs on this driver's own module, every later level on a fresh
         SpMVModule plan of the aggregated pattern; each level is coloured by SpMV.color under io.coloring_priorities(that
@@ -3132,8 +3186,14 @@ class Louvain(_PatternApp):
         level_q_ (int64[runs, 2]: q_first and q_last, modularity x two_m^2), level_colorings_ (the colourings used);
         launches_ (gl_louvain_move's alone), dendrogram_ (per accepted level, uint32[n_]: the community of every original
         vertex), num_communities_, community_labels_ (ascending) and community_sizes_ over the real vertices, and timings_
-        (seconds: color, move, aggregate, plan).  The call waits for the device."""
+        (seconds: color, move, aggregate, plan).  aggregate="device" contracts every accepted level with gl_contract on the
+        level's own plan, from the labels, weights and k the move call left on the device, and downloads only the smaller
+        graph (the default: faster end to end on every stand-in measured, EXPERIMENTS.md Round 33); aggregate="host" calls
+        io.aggregate_communities.  Every result is the same to the bit.  The call waits for the
+        device."""
         self._require_sent()
+        if aggregate not in ("host", "device"):
+            raise ValueError("Louvain.run(): aggregate %r is neither \"host\" nor \"device\"" % (aggregate,))
         B = self.backend
         clock = {"color": 0.0, "move": 0.0, "aggregate": 0.0, "plan": 0.0}
         live = {}
@@ -3189,11 +3249,20 @@ class Louvain(_PatternApp):
                                      k_buf if level else None, max_sweeps, min_gain)
             B.sync()
             labels = B.download(buf, np.uint32, rows)
+            live.update(move_level=level, label_buf=label_buf, k_buf=k_buf if level else None, w_buf=w_buf if level and nnz else None)
             clock["move"] += time.perf_counter() - t0
             return (labels,) + tuple(stats)
 
+        def contract(level, graph, weights, k, labels):
+            assert live.get("move_level") == level
+            mod, _ = module_of(level, graph)
+            smaller, w, tot, part, stats = mod.contract(live["label_buf"], graph.num_rows, live["w_buf"], live["k_buf"])
+            if stats[5]:
+                raise ValueError("aggregate_communities: a summed weight does not fit 32 bits")
+            return smaller, w, tot, part
+
         t_all = time.perf_counter()
-        res = _louvain_levels(self.graph_, self.degrees_, move, color, tol, max_sweeps, max_levels)
+        res = _louvain_levels(self.graph_, self.degrees_, move, color, tol, max_sweeps, max_levels, contract if aggregate == "device" else None)
         clock["aggregate"] = time.perf_counter() - t_all - clock["color"] - clock["move"] - clock["plan"]
         live.clear()
         self.labels_ = res["labels"]
@@ -3219,6 +3288,69 @@ class Louvain(_PatternApp):
         if lab is None:
             raise RuntimeError("Louvain.modularity(): run() first")
         return _modularity_of(self.graph_, self.degrees_, lab)
+
+
+class QuotientGraph(_PatternApp):
+    """The quotient of a graph by a labelling of its vertices: gl_contract.  Vertices with one label become
+    one vertex, parallel edges are summed, what falls inside a group goes to the group's weight: C = S^T A S in exact 32-bit
+    integers -- Louvain's aggregation step, the condensation of strong components.  The matrix is read as a simple graph
+    (zero values, the diagonal and duplicates dropped): undirected and stored in both directions (io.symmetrize_simple), or
+    directed (io.simple_pattern's csr_in: an entry (v, u) for an edge u -> v)."""
+    _no_shards_ = ("gl_contract walks the rows of all members of a group, which lie anywhere in the matrix, so every rank would "
+                   "need every row")
+    graph_ = directed_ = quotient_ = weights_ = tot_ = community_of_ = num_groups_ = inside_weight_ = paths_ = None
+    _directed_asked_ = None
+
+    def _prepare(self, csr):
+        cin, _, symmetric = io.simple_pattern(csr)                  # (after padding: padding vertices have empty rows)
+        self.directed_ = (not symmetric) if self._directed_asked_ is None else bool(self._directed_asked_)
+        self.graph_ = cin if self.directed_ else io.symmetrize_simple(csr)[0]
+        self.quotient_ = None
+        return self.graph_
+
+    def load_and_format_matrix(self, csr_float_npz_path, skip_empty_rows=True, directed=None):
+        """directed=None: undirected iff the pattern is symmetric, as BetweennessCentrality decides; False on an asymmetric
+        pattern takes every edge in both directions; True keeps the direction."""
+        self._directed_asked_ = directed
+        _PatternApp.load_and_format_matrix(self, csr_float_npz_path, skip_empty_rows)
+
+    def run(self, labels, weights=None, vertex_weights=None):
+        """-> (CSRMatrix, uint32 weights, uint32 tot, community_of): io.aggregate_communities' tuple for graph_ (made
+        direction-aware: a directed graph_ gives the entry (part[v], part[u]) for its entry (v, u)).  `labels`: one vertex
+        number per vertex, n_real_ or n_ words (the labels of ConnectedComponents, StronglyConnectedComponents, Louvain ...);
+        `weights`: a uint32 per entry of graph_ (None: all 1); `vertex_weights`: a uint32 per labelled vertex (None: the sums of
+        its entries' weights).  The groups are numbered in ascending order of their labels.  Leaves quotient_, weights_, tot_,
+        community_of_, num_groups_, inside_weight_ (the summed weight of the entries inside groups) and paths_ (the groups
+        that took the wavefront, workgroup and slab path of the numeric call).  A summed weight above 0xffffffff raises
+        ValueError, as on the host.  The call waits for the device."""
+        self._require_sent()
+        B, g = self.backend, self.graph_
+        lab = np.asarray(labels)
+        if lab.ndim != 1 or lab.shape[0] not in (self.n_real_, self.n_):
+            raise ValueError("QuotientGraph.run(): labels of shape %s, expected %d or %d words" % (lab.shape, self.n_real_, self.n_))
+        nv, nnz = int(lab.shape[0]), int(g.nnz)
+        if nv and (int(lab.min()) < 0 or int(lab.max()) >= nv):
+            raise ValueError("QuotientGraph.run(): labels are vertex numbers below %d" % nv)
+        w = None if weights is None else np.asarray(weights)
+        vw = None if vertex_weights is None else np.asarray(vertex_weights)
+        if (w is not None and w.shape != (nnz,)) or (vw is not None and vw.shape != (nv,)):
+            raise ValueError("QuotientGraph.run(): %d entry weights and %d vertex weights are expected" % (nnz, nv))
+        buf = B.alloc(2 * max(1, nv) + max(1, nnz), np.float32)     # (32-bit words: the labels, k, the entry weights)
+        label_buf, k_buf, w_buf = B.view(buf, 0, nv, 4), B.view(buf, max(1, nv), nv, 4), B.view(buf, 2 * max(1, nv), nnz, 4)
+        B.upload(label_buf, lab.astype(np.uint32))
+        if vw is not None and nv:
+            B.upload(k_buf, vw.astype(np.uint32))
+        if w is not None and nnz:
+            B.upload(w_buf, w.astype(np.uint32))
+        c, cw, tot, part, stats = self.SpMV_.contract(label_buf, nv, w_buf if w is not None and nnz else None, k_buf if vw is not None else None)
+        if stats[5]:
+            raise ValueError("QuotientGraph.run(): %d summed weights do not fit 32 bits" % stats[5])
+        self.quotient_, self.weights_, self.tot_, self.community_of_, self.num_groups_ = c, cw, tot, part, int(stats[0])
+        total = nnz if w is None else int(w.astype(np.int64).sum())
+        self.inside_weight_ = total - int(cw.astype(np.int64).sum())
+        rows_with = int(np.count_nonzero(np.diff(c.adj_indptr.astype(np.int64))))
+        self.paths_ = (rows_with - int(stats[3]) - int(stats[4]), int(stats[3]), int(stats[4]))
+        return c, cw, tot, part
 
 
 class StronglyConnectedComponents(_PatternApp):

@@ -61,7 +61,8 @@ EXT_HEADERS = {"graphlily_hip_ext.h": EXT_EXPORTS, "graphlily_hip_truss.h": ["gl
                "graphlily_hip_scc.h": ["gl_scc"], "graphlily_hip_louvain.h": ["gl_louvain_move"], "graphlily_hip_bicc.h": ["gl_bicc"],
                "graphlily_hip_topo.h": ["gl_topo"], "graphlily_hip_msbfs.h": ["gl_msbfs"],
                "graphlily_hip_sim.h": ["gl_similarity"], "graphlily_hip_clique.h": ["gl_clique_count"],
-               "graphlily_hip_spgemm.h": ["gl_spgemm_numeric", "gl_spgemm_symbolic"]}
+               "graphlily_hip_spgemm.h": ["gl_spgemm_numeric", "gl_spgemm_symbolic"],
+               "graphlily_hip_contract.h": ["gl_contract_numeric", "gl_contract_symbolic"]}
 
 
 class GraphLilyError(RuntimeError):
@@ -142,6 +143,8 @@ def lib():
         "gl_spgemm_symbolic": [vp, vp, vp, u32, vp, P(u64)],
         "gl_spgemm_numeric": [vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, P(u64)],
         "gl_louvain_move": [vp, vp, vp, vp, vp, u32, u64, P(u64)],
+        "gl_contract_symbolic": [vp, u32, vp, vp, vp, P(u64)],
+        "gl_contract_numeric": [vp, u32, vp, u32, vp, vp, vp, vp, vp, vp, P(u64)],
         "gl_bc_accumulate": [vp, vp, vp, vp, ctypes.c_double, i32, vp, P(u32)],
         "gl_spmv_run": [vp, vp, vp, vp, i32, f32, i32],
         "gl_prof_begin": [u32, u32], "gl_prof_end": [P(ctypes.c_double), P(u32)], "gl_span_begin": [], "gl_span_end": [P(ctypes.c_double)],
@@ -513,6 +516,29 @@ class SpMVPlan:
         check(lib().gl_spgemm_numeric(ctypes.c_void_p(self.handle), ctypes.c_void_p(b.handle), ctypes.c_void_p(mask.handle if mask else 0),
                                       ctypes.c_uint32(GL_SPGEMM_MASK_COMPLEMENT if complement else 0), ctypes.c_uint32(semiring),
                                       _p(a_val), _p(b_val), _p(c_indptr), _p(c_indices), _p(c_val), out))
+        return tuple(int(x) for x in out) if stats else None
+
+    def contract_symbolic(self, num_vertices, label, part, c_indptr):
+        """gl_contract_symbolic: the quotient of this plan's graph by `label` (num_vertices device words, each a vertex number
+        below num_vertices): the group numbers into `part` (num_vertices device words; the groups are ranked by ascending label)
+        and the row offsets of C into `c_indptr` (room for num_vertices + 1 device words, k + 1 are written).  The plan is
+        square, whole, its rows strictly ascending (symmetry is not required); rows at and behind num_vertices are empty.
+        Waits.  -> (k, nnz(C), bound = the sum of the row lengths, groups that took the workgroup path, groups that took the
+        slab path, 0)."""
+        out = (ctypes.c_uint64 * 6)(*([0xdeadbeefdeadbeef] * 6))
+        check(lib().gl_contract_symbolic(ctypes.c_void_p(self.handle), ctypes.c_uint32(num_vertices), _p(label), _p(part), _p(c_indptr), out))
+        return tuple(int(x) for x in out)
+
+    def contract_numeric(self, num_vertices, part, k, c_indptr, c_indices, c_weight=None, tot=None, weight=None, vertex_weight=None, stats=False):
+        """gl_contract_numeric: the columns (ascending in every row) and summed uint32 weights of C into `c_indices` / `c_weight`
+        (nnz(C) words each; c_weight=None: the pattern only) and the groups' vertex weights into `tot` (k words, optional), from
+        the `part`, `k` and `c_indptr` of this plan's LAST contract_symbolic call.  `weight`: a uint32 per entry of the plan's
+        rows (None: all 1); `vertex_weight`: a uint32 per vertex (None: the sums of the rows' entry weights off the diagonal).
+        A sum above 0xffffffff is stored as 0xffffffff and counted.  Enqueued, unless stats=True -> the six figures of
+        contract_symbolic, the paths now chosen by |C(a)|, the last one the saturated sums."""
+        out = (ctypes.c_uint64 * 6)(*([0xdeadbeefdeadbeef] * 6)) if stats else None
+        check(lib().gl_contract_numeric(ctypes.c_void_p(self.handle), ctypes.c_uint32(num_vertices), _p(part), ctypes.c_uint32(k), _p(weight),
+                                        _p(vertex_weight), _p(c_indptr), _p(c_indices), _p(c_weight), _p(tot), out))
         return tuple(int(x) for x in out) if stats else None
 
     def kcore(self, core, order=None):

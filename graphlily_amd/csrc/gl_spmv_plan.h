@@ -306,6 +306,12 @@ struct gl_spmv_plan_s {
     const gl_spmv_plan_s *spgemm_partner = nullptr;
     uint64_t spgemm_partner_uid = 0, spgemm_products = 0;
     uint32_t spgemm_bins[3] = {0, 0, 0}, spgemm_wave_slots = 0, spgemm_lds_slots = 0, spgemm_group = 0, spgemm_slabs = 0;
+    // gl_contract_* (gl_contract.hip): the scratch, allocated by the first call -- 256 bytes of control words, num_rows 64-bit
+    // vertex weights, the label bitmap and its popcount prefix, five arrays of num_rows (+ 1) words (group sizes / cursors, entry
+    // bounds, member offsets, members, gl_compact.h's counts) and three bin lists of num_rows + 1 records --, the slabs of the slab
+    // path, and what the host keeps of the last symbolic call for the numeric call behind it: k, num_vertices, its bins, the knobs it read
+    unsigned char *d_contract_scratch = nullptr, *d_contract_slab = nullptr;
+    uint32_t contract_k = 0xffffffffu, contract_nv = 0, contract_bins[3] = {0, 0, 0}, contract_slabs = 0, contract_wave_slots = 0, contract_lds_slots = 0;
     // gl_bc_accumulate (gl_bc.hip), as plan_in, set up by the first call: the pass's scratch -- 256 bytes of control words, two
     // arrays of num_rows + 2 level offsets, num_rows words of queue, num_rows doubles each of sigma and coef -- the page-locked
     // room the offsets are read back to, and the verdict on the last plan_out that was not this plan itself: is it the

@@ -394,6 +394,36 @@ class SpMVModule(BaseModule):
         self._finish(label_buf)
         return stats
 
+    def contract(self, label_buf, num_vertices=None, weight_buf=None, vertex_weight_buf=None):
+        """Extension (gl_contract_symbolic + gl_contract_numeric): the quotient of this module's matrix, read as a graph -- rows as
+        strictly ascending sets, directed or not --, by the labelling in `label_buf` (num_vertices words, default
+        get_num_rows(); every label a vertex number below num_vertices), under the uint32 entry weights in `weight_buf`
+        (get_nnz() words aligned with the matrix's entries; None: all 1) and the vertex weights in `vertex_weight_buf` (None: the
+        sums of the rows' entry weights) -> (io.CSRMatrix of the k groups, uint32 weights, uint32 tot, uint32 part, stats): on
+        the host, io.aggregate_communities' tuple and gl_contract_numeric's six figures.  The groups are numbered in ascending
+        order of their labels.  The call synchronises; only C, tot and part cross to the host.  Raises GraphLilyError
+        (GL_ERR_UNSUPPORTED) when the plan keeps no row copy (only the (||,&&) layout does), is not square, is a row shard, its
+        rows are no such sets or a row at or behind num_vertices is not empty, and (GL_ERR_INVALID_ARG) for a label >=
+        num_vertices."""
+        if self.plan_ is None:
+            _fatal("SpMVModule.contract: send_matrix_host_to_device first")
+        nv = self.get_num_rows() if num_vertices is None else int(num_vertices)
+        head = capi.DeviceBuffer(4 * (2 * nv + 1 + 1))                     # (32-bit words: part, then the offsets of C)
+        part_buf = capi.DeviceBuffer(4 * max(nv, 1), ptr=head.ptr, keepalive=head)
+        indptr_buf = capi.DeviceBuffer(4 * (nv + 1), ptr=head.ptr + 4 * max(nv, 1), keepalive=head)
+        k, nnz = self.plan_.contract_symbolic(nv, label_buf, part_buf, indptr_buf)[:2]
+        body = capi.DeviceBuffer(4 * (2 * nnz + k + 1))                    # (the columns, the weights, tot)
+        idx_buf = capi.DeviceBuffer(4 * max(nnz, 1), ptr=body.ptr, keepalive=body)
+        w_buf = capi.DeviceBuffer(4 * max(nnz, 1), ptr=body.ptr + 4 * nnz, keepalive=body)
+        tot_buf = capi.DeviceBuffer(4 * max(k, 1), ptr=body.ptr + 8 * nnz, keepalive=body)
+        stats = self.plan_.contract_numeric(nv, part_buf, k, indptr_buf, idx_buf, w_buf, tot_buf, weight_buf, vertex_weight_buf, stats=True)
+        words = head.read(np.uint32, 2 * nv + 1 + 1)
+        part, indptr = words[:nv], words[max(nv, 1):max(nv, 1) + k + 1]
+        out = body.read(np.uint32, 2 * nnz + k + 1)
+        from .io import CSRMatrix
+        c = CSRMatrix(k, k, np.ones(nnz, dtype=np.float32), out[:nnz].copy(), indptr.copy())
+        return c, out[nnz:2 * nnz].copy(), out[2 * nnz:2 * nnz + k].copy(), part.copy(), stats
+
     def scc(self, out_module, label_buf, prio_buf=None):
         """Extension (gl_scc): the strongly connected components of this module's matrix, read as a directed graph -- row v: the
         predecessors of v, `out_module` (None: the pattern is symmetric) holds the transposed pattern -- into `label_buf`
