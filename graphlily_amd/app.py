@@ -1761,6 +1761,69 @@ def validate_topological(csr, level, dist=None, parent=None, weighted=False):
     return int(np.count_nonzero(peeled))
 
 
+def _shortest_paths_of(g_in, g_out, sources):
+    """Dijkstra's algorithm in f32 on the host (heapq) over io.directed_weighted's pair -> (dist float32[n], parent uint32[n]):
+    gl_sssp_delta's definitions, the parents from the finished distances by SSSP.parents()'s rule."""
+    import heapq
+    n = int(g_in.num_rows)
+    ptr, idx, w = g_out.adj_indptr.astype(np.int64), g_out.adj_indices, g_out.adj_data.astype(np.float32)
+    dist = np.full(n, np.inf, dtype=np.float32)
+    heap = []
+    for s in np.unique(np.asarray(sources, dtype=np.int64)).tolist():
+        dist[s] = 0.0
+        heap.append((0.0, s))
+    rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(g_in.adj_indptr.astype(np.int64)))
+    cols = g_in.adj_indices.astype(np.int64)
+    with np.errstate(over="ignore"):                                 # (a sum may overflow to +inf: such a vertex is unreached)
+        while heap:
+            d, u = heapq.heappop(heap)
+            if d > dist[u]:
+                continue
+            for j in range(ptr[u], ptr[u + 1]):
+                cand = np.float32(dist[u] + w[j])                    # float32 + float32
+                if cand < dist[idx[j]]:
+                    dist[idx[j]] = cand
+                    heapq.heappush(heap, (float(cand), int(idx[j])))
+        fits = np.isfinite(dist[rows]) & (dist[cols] < dist[rows]) & (dist[cols] + g_in.adj_data.astype(np.float32) == dist[rows])
+    parent = np.full(n, n, dtype=np.int64)
+    np.minimum.at(parent, rows[fits], cols[fits])
+    parent[parent == n] = NO_PARENT
+    src = np.asarray(sources, dtype=np.int64)
+    parent[src] = src
+    return dist, parent.astype(np.uint32)
+
+
+def validate_shortest_paths(csr, sources, dist, parent=None):
+    """Host-side check (heapq, numpy) that `dist` -- and `parent`, when given -- are gl_sssp_delta's results on the directed
+    graph of `csr` (io.directed_weighted with keep="smallest": every stored off-diagonal entry A[v, u] an edge u -> v) from
+    `sources`: a Dijkstra in f32 on the host, compared to the bit, and SSSP.parents()'s rule.  `dist` / `parent` may be longer
+    than the matrix (the drivers pad it): the extra vertices are isolated.  Raises ValueError naming the first offending vertex;
+    returns the number of reached vertices."""
+    g_in, g_out, _ = io.directed_weighted(csr, True, "smallest")
+    n = int(g_in.num_rows)
+    got = np.asarray(dist, dtype=np.float32)
+    if got.shape[0] < n or (parent is not None and np.asarray(parent).shape[0] != got.shape[0]):
+        raise ValueError("validate_shortest_paths: %d distances for %d vertices" % (got.shape[0], n))
+    src = np.atleast_1d(np.asarray(sources)).astype(np.int64)
+    want, want_parent = _shortest_paths_of(g_in, g_out, src[src < n])
+    pad = np.ones(got.shape[0] - n, dtype=bool)
+    pad[src[src >= n] - n] = False
+    if np.any(pad & np.isfinite(got[n:])):
+        raise ValueError("validate_shortest_paths: the isolated vertex %d is reached" % (n + int(np.flatnonzero(pad & np.isfinite(got[n:]))[0])))
+    bad = got[:n].view(np.uint32) != want.view(np.uint32)
+    if np.any(bad):
+        k = int(np.flatnonzero(bad)[0])
+        raise ValueError("validate_shortest_paths: vertex %d has distance %r (bits 0x%08x), Dijkstra on the host gives %r: too %s"
+                         % (k, float(got[k]), got[:n].view(np.uint32)[k], float(want[k]), "short" if got[k] < want[k] else "long"))
+    if parent is not None:
+        bad = np.asarray(parent)[:n].astype(np.uint32) != want_parent
+        if np.any(bad):
+            k = int(np.flatnonzero(bad)[0])
+            raise ValueError("validate_shortest_paths: vertex %d has parent %d, the smallest predecessor that fits is %d"
+                             % (k, np.asarray(parent)[k], want_parent[k]))
+    return int(np.count_nonzero(np.isfinite(got)))
+
+
 def _hops_of(A_out, s, n):
     """-> uint32[n]: the edges of a shortest path from s to every vertex on the host (0 on s, 0xffffffff unreached); A_out is the
     scipy matrix whose row u holds the out-neighbours of u."""
@@ -3530,21 +3593,16 @@ class BiconnectedComponents(_PatternApp):
         return tree, block_rank, cut_rank
 
 
-class TopologicalOrder(_PatternApp):
-    """Topological levels, a topological order and the critical path: gl_topo (DESIGN.md 4.25), Kahn's peeling with dependency
-    counters over the pattern and its transpose.  The matrix is read as a DIRECTED graph (io.directed_weighted: an edge u -> v for
-    a stored entry A[v, u], u != v; weighted=False is io.simple_pattern's reading, weighted=True keeps every stored entry with the
-    largest of its values, -0.0 as +0.0, NaN and inf refused); the transposed pattern lives in a second boolean SpMVModule, out_,
-    which exists only when the pattern is not symmetric.  Both plans are built from ones (the row copy would store a zero value
-    as no entry); the weights travel in buffers of their own, aligned with graph_.adj_indices and graph_out_.adj_indices.
-    load_and_format_matrix accepts a path or a CSRMatrix, so StronglyConnectedComponents.condensation()'s matrix goes straight in.
-    On a cyclic input the peeled vertices are those that are neither on a cycle nor behind one."""
-    _no_shards_ = ("gl_topo decrements the counter of every column of a row of the transposed pattern and reads the distance of "
-                   "every column of a row of the pattern, so every rank would need both whole patterns and every counter")
+class _DirectedPairApp(_PatternApp):
+    """... and of those whose kernels take a directed pattern as TWO plans with a weight per entry of each (TopologicalOrder,
+    ShortestPaths): io.directed_weighted's matrices stay in graph_ and graph_out_; the transposed pattern lives in a second
+    boolean SpMVModule, out_, which exists only when the pattern is not symmetric.  Both plans are built from ones (the row copy
+    would store a zero value as no entry); the weights travel in buffers of their own, aligned with graph_.adj_indices and
+    graph_out_.adj_indices -- on a weighted load, or always with _unit_weights_ (the kernel wants weights: ones then)."""
     graph_ = graph_out_ = symmetric_ = weight_buf_ = weight_out_buf_ = None
-    level_ = is_dag_ = num_peeled_ = cyclic_ = num_levels_ = level_sizes_ = widest_ = launches_ = None
-    dist_ = parent_ = critical_length_ = order_ = position_ = None
     weighted_ = False
+    _keep_ = "largest"                   # which of an edge's parallel values io.directed_weighted keeps
+    _unit_weights_ = False
 
     def __init__(self, num_channels=M.num_hbm_channels, spmv_out_buf_len=0, vec_buf_len=0, comm=None, backend=None):
         _PatternApp.__init__(self, num_channels, spmv_out_buf_len, vec_buf_len, comm, backend)
@@ -3555,9 +3613,12 @@ class TopologicalOrder(_PatternApp):
     def _ones_of(g):
         return io.CSRMatrix(g.num_rows, g.num_cols, np.ones(g.nnz, dtype=np.float32), g.adj_indices, g.adj_indptr)
 
+    def _forget_results(self):
+        pass
+
     def _prepare(self, csr):
-        self.graph_, self.graph_out_, self.symmetric_ = io.directed_weighted(csr, self.weighted_)      # (after padding)
-        self.level_ = self.dist_ = self.parent_ = self.order_ = self.position_ = None
+        self.graph_, self.graph_out_, self.symmetric_ = io.directed_weighted(csr, self.weighted_, self._keep_)      # (after padding)
+        self._forget_results()
         self.weight_buf_ = self.weight_out_buf_ = None
         return self._ones_of(self.graph_)
 
@@ -3578,12 +3639,28 @@ class TopologicalOrder(_PatternApp):
         _PatternApp.send_matrix_host_to_device(self)
         if self.out_ is not None:
             self.out_.send_matrix_host_to_device()
-        if self.weighted_:
-            for name, g in (("weight_buf_", self.graph_), ("weight_out_buf_", self.graph_out_)):
+        if self.weighted_ or self._unit_weights_:
+            for name, g in (("weight_buf_", self.graph_), ("weight_out_buf_", self.graph_ if self.graph_out_ is None else self.graph_out_)):
                 buf = self.backend.alloc(max(1, g.nnz), np.float32)
                 if g.nnz:
                     self.backend.upload(buf, g.adj_data)
                 setattr(self, name, buf)
+
+
+class TopologicalOrder(_DirectedPairApp):
+    """Topological levels, a topological order and the critical path: gl_topo (DESIGN.md 4.25), Kahn's peeling with dependency
+    counters over the pattern and its transpose.  The matrix is read as a DIRECTED graph (io.directed_weighted: an edge u -> v for
+    a stored entry A[v, u], u != v; weighted=False is io.simple_pattern's reading, weighted=True keeps every stored entry with the
+    largest of its values, -0.0 as +0.0, NaN and inf refused); the two plans and the weight buffers are _DirectedPairApp's.
+    load_and_format_matrix accepts a path or a CSRMatrix, so StronglyConnectedComponents.condensation()'s matrix goes straight in.
+    On a cyclic input the peeled vertices are those that are neither on a cycle nor behind one."""
+    _no_shards_ = ("gl_topo decrements the counter of every column of a row of the transposed pattern and reads the distance of "
+                   "every column of a row of the pattern, so every rank would need both whole patterns and every counter")
+    level_ = is_dag_ = num_peeled_ = cyclic_ = num_levels_ = level_sizes_ = widest_ = launches_ = None
+    dist_ = parent_ = critical_length_ = order_ = position_ = None
+
+    def _forget_results(self):
+        self.level_ = self.dist_ = self.parent_ = self.order_ = self.position_ = None
 
     def run(self, reverse=False, order=False):
         """-> uint32[n_]: level[v] = the edges of the longest path that ends in v, 0xffffffff for a vertex on a cycle or behind
@@ -3647,6 +3724,88 @@ class TopologicalOrder(_PatternApp):
         v = int(np.flatnonzero(peeled & (self.dist_[:nr] == np.float32(self.critical_length_)))[0])
         path = [v]
         while self.parent_[path[-1]] != 0xFFFFFFFF:
+            path.append(int(self.parent_[path[-1]]))
+        return np.asarray(path, dtype=np.int64)
+
+
+class ShortestPaths(_DirectedPairApp):
+    """Weighted single- and multi-source shortest paths run to convergence: gl_sssp_delta, delta-stepping over
+    the pattern and its transpose.  The matrix is read as a DIRECTED graph (io.directed_weighted with keep="smallest": an edge
+    u -> v for a stored entry A[v, u], u != v, parallel edges collapse to the shortest); weighted=False gives every edge the
+    weight 1 (io.simple_pattern's reading: a stored zero is no edge).  Negative, NaN and infinite weights are refused.  Where
+    SSSP runs the reference's Bellman-Ford for a number of iterations its caller guesses, this driver needs none."""
+    _no_shards_ = ("gl_sssp_delta lowers the distance of every column of a row of the transposed pattern, so every rank would "
+                   "need both whole patterns and every distance")
+    _keep_ = "smallest"
+    _unit_weights_ = True
+    dist_ = parent_ = orphans_ = reached_ = delta_ = buckets_ = rounds_ = relaxations_ = launches_ = sources_ = None
+
+    def _forget_results(self):
+        self.dist_ = self.parent_ = self.orphans_ = self.reached_ = self.sources_ = None
+
+    def _prepare(self, csr):
+        if self.weighted_:
+            indptr = csr.adj_indptr.astype(np.int64)[:csr.num_rows + 1]
+            rows = np.repeat(np.arange(csr.num_rows, dtype=np.int64), np.diff(indptr))
+            cols = csr.adj_indices[:int(indptr[-1])].astype(np.int64)
+            w = np.asarray(csr.adj_data[:int(indptr[-1])], dtype=np.float32)
+            bad = ~(np.isfinite(w) & (w >= 0)) & (rows != cols)
+            if np.any(bad):
+                j = int(np.flatnonzero(bad)[0])
+                raise ValueError("ShortestPaths: entry %d (%d, %d) is %s: delta-stepping needs finite weights >= 0" % (j, rows[j], cols[j], w[j]))
+        return _DirectedPairApp._prepare(self, csr)
+
+    def load_and_format_matrix(self, src, skip_empty_rows=True, weighted=True):
+        _DirectedPairApp.load_and_format_matrix(self, src, skip_empty_rows, weighted)
+
+    def default_delta(self):
+        """32 * mean weight / mean out-degree over the real vertices -- about one wavefront of light entries per settled vertex;
+        +inf when every weight is 0 or there is no edge.  A labelled guess (EXPERIMENTS.md Round 34)."""
+        g = self.graph_
+        if g.nnz == 0 or self.n_real_ == 0:
+            return np.float32(np.inf)
+        delta = 32.0 * float(np.mean(g.adj_data, dtype=np.float64)) * self.n_real_ / g.nnz
+        return np.float32(delta) if 0 < delta < 3e38 and np.float32(delta) > 0 else np.float32(np.inf)
+
+    def run(self, sources, delta=None, parents=True):
+        """-> float32[n_]: dist[v] = the length of the shortest path from the nearest of `sources` (an int or an array, all at
+        distance 0) to v, summed in f32 along the path -- Dijkstra's f32 result to the bit, whatever `delta` --, +inf when
+        unreached (padding vertices are isolated).  delta=None takes default_delta(); +inf is frontier Bellman-Ford.  Leaves
+        dist_, sources_, delta_, reached_, buckets_, rounds_, relaxations_, launches_ (only reached_ is a function of the input)
+        and, with parents=True, parent_ (uint32[n_]: SSSP.parents()'s definition -- v on a source, 0xffffffff when unreached,
+        else the smallest u with A[v, u] stored, d[u] < d[v] and (float)(d[u] + w) == d[v]) and orphans_ (reached vertices that
+        are no source and have no such u: only behind zero-weight edges).  The call waits for the device."""
+        self._require_sent()
+        B, n = self.backend, self.n_
+        src = np.atleast_1d(np.asarray(sources)).astype(np.int64).ravel()
+        if src.size and (src.min() < 0 or src.max() >= n):
+            raise ValueError("ShortestPaths.run(): source %d of %d vertices" % (src[(src < 0) | (src >= n)][0], n))
+        delta = self.default_delta() if delta is None else np.float32(delta)
+        if not delta > 0:
+            raise ValueError("ShortestPaths.run(): delta is %s, not a float > 0 or +inf" % delta)
+        room = max(1, n)
+        out = B.alloc(2 * room, np.float32)                          # (32-bit words: dist, parent)
+        stats = self.SpMV_.sssp_delta(self.out_, self.weight_buf_, self.weight_out_buf_, src, float(delta), B.view(out, 0, room, 4),
+                                      B.view(out, room, room, 4) if parents else None)
+        B.sync()
+        got = B.download(out, np.uint32, 2 * room)
+        self.dist_ = got[:n].copy().view(np.float32)
+        self.sources_, self.delta_ = src, delta
+        self.reached_, self.buckets_, self.rounds_, self.relaxations_, self.launches_ = stats
+        self.parent_ = self.orphans_ = None
+        if parents:
+            self.parent_ = got[room:room + n].copy()
+            self.orphans_ = int(np.count_nonzero(np.isfinite(self.dist_) & (self.parent_ == NO_PARENT)))
+        assert self.reached_ == int(np.count_nonzero(np.isfinite(self.dist_))), "gl_sssp_delta's count of reached vertices and its distances disagree"
+        return self.dist_
+
+    def path(self, v):
+        """-> int64[k]: v, parent_[v], ... back to a source of the last run (or to an orphan, whose path ends there); empty when v
+        is unreached."""
+        if self.parent_ is None:
+            raise RuntimeError("ShortestPaths.path(): run() with parents=True first")
+        path = [int(v)] if np.isfinite(self.dist_[int(v)]) else []
+        while path and self.parent_[path[-1]] not in (path[-1], NO_PARENT):
             path.append(int(self.parent_[path[-1]]))
         return np.asarray(path, dtype=np.int64)
 

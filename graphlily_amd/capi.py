@@ -62,7 +62,8 @@ EXT_HEADERS = {"graphlily_hip_ext.h": EXT_EXPORTS, "graphlily_hip_truss.h": ["gl
                "graphlily_hip_topo.h": ["gl_topo"], "graphlily_hip_msbfs.h": ["gl_msbfs"],
                "graphlily_hip_sim.h": ["gl_similarity"], "graphlily_hip_clique.h": ["gl_clique_count"],
                "graphlily_hip_spgemm.h": ["gl_spgemm_numeric", "gl_spgemm_symbolic"],
-               "graphlily_hip_contract.h": ["gl_contract_numeric", "gl_contract_symbolic"]}
+               "graphlily_hip_contract.h": ["gl_contract_numeric", "gl_contract_symbolic"],
+               "graphlily_hip_sssp_delta.h": ["gl_sssp_delta"]}
 
 
 class GraphLilyError(RuntimeError):
@@ -138,6 +139,7 @@ def lib():
         "gl_bicc": [vp, vp, vp, vp, vp, P(u64)],
         "gl_topo": [vp, vp, vp, vp, vp, vp, vp, P(u64)],
         "gl_msbfs": [vp, vp, u32, i32, vp, vp, vp, vp, vp, vp],
+        "gl_sssp_delta": [vp, vp, vp, vp, vp, u32, f32, vp, vp, P(u64)],
         "gl_similarity": [vp, vp, u64, vp, vp, vp, vp],
         "gl_clique_count": [vp, u32, vp, vp, P(u64)],
         "gl_spgemm_symbolic": [vp, vp, vp, u32, vp, P(u64)],
@@ -687,6 +689,29 @@ class SpMVPlan:
         stats = (ctypes.c_uint64 * 4)(*([garbage] * 4))
         check(lib().gl_topo(ctypes.c_void_p(self.handle), ctypes.c_void_p(out.handle), _p(weight), _p(level), _p(order), _p(dist),
                             _p(parent), stats))
+        return tuple(int(x) for x in stats)
+
+    def sssp_delta(self, plan_out, weight_in, weight_out, sources, delta, dist, parent=None):
+        """gl_sssp_delta with this plan as plan_in (row v: the predecessors of v) and `plan_out` as the transposed pattern's plan
+        (None, or this plan: the pattern is symmetric): delta-stepping shortest paths from `sources` (host integers; all at
+        distance 0, one >= num_rows is ignored) into `dist` (num_rows device floats: the least fixed point of d[v] = min
+        (float)(d[u] + w) in f32, Dijkstra's result to the bit whatever `delta`; the bits 0x7f800000 when unreached) -> (reached,
+        buckets visited, rounds, relaxations that lowered a distance, launches enqueued); only `reached` is a function of the
+        input.  `weight_in` / `weight_out` (nnz device floats each, aligned with this plan's and plan_out's row copies) are
+        finite and >= +0.0; `delta` is a float > 0, +inf included (one bucket: frontier Bellman-Ford).  `parent` (optional,
+        num_rows device words) receives SSSP.parents()'s tree: v on a source, 0xffffffff when unreached or an orphan, else the
+        smallest u with d[u] < d[v] and (float)(d[u] + w) == d[v].  Both plans are square, whole, their rows strictly ascending
+        sets (io.directed_weighted prepares them).  Every output is fully written by the call, which SYNCHRONISES (it reads a
+        control record back between batches of launches)."""
+        out = self if plan_out is None else plan_out
+        src = np.ascontiguousarray(np.asarray(sources, dtype=np.int64).ravel())
+        if src.size and (src.min() < 0 or src.max() > 0xffffffff):
+            raise ValueError("SpMVPlan.sssp_delta: sources must be vertex numbers")
+        d_src = DeviceBuffer.from_host(src.astype(np.uint32)) if src.size else None
+        garbage = 0xdeadbeefdeadbeef
+        stats = (ctypes.c_uint64 * 5)(*([garbage] * 5))
+        check(lib().gl_sssp_delta(ctypes.c_void_p(self.handle), ctypes.c_void_p(out.handle), _p(weight_in), _p(weight_out), _p(d_src),
+                                  ctypes.c_uint32(int(src.size)), ctypes.c_float(delta), _p(dist), _p(parent), stats))
         return tuple(int(x) for x in stats)
 
     def msbfs(self, sources, far, reach, harmonic, accumulate=False, hops=None):

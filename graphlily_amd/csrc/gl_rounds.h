@@ -28,6 +28,9 @@ __device__ __forceinline__ uint32_t ga_add(uint32_t *p, uint32_t v) { return __h
 __device__ __forceinline__ uint32_t ga_sub(uint32_t *p, uint32_t v) { return __hip_atomic_fetch_sub((ga_u32 *)p, v, GA_ORDER); }
 __device__ __forceinline__ void ga_min(uint32_t *p, uint32_t v) { (void)__hip_atomic_fetch_min((ga_u32 *)p, v, GA_ORDER); }
 __device__ __forceinline__ void ga_max(uint32_t *p, uint32_t v) { (void)__hip_atomic_fetch_max((ga_u32 *)p, v, GA_ORDER); }
+// ... and the two that return the word's value before, for the callers that act on "was I the one who changed it?" (gl_sssp_delta)
+__device__ __forceinline__ uint32_t ga_fetch_min(uint32_t *p, uint32_t v) { return __hip_atomic_fetch_min((ga_u32 *)p, v, GA_ORDER); }
+__device__ __forceinline__ uint32_t ga_fetch_max(uint32_t *p, uint32_t v) { return __hip_atomic_fetch_max((ga_u32 *)p, v, GA_ORDER); }
 // -> did the swap take place?  `expect` becomes the value found either way: a retry goes on from it, never from a re-read
 __device__ __forceinline__ bool ga_cas(uint32_t *p, uint32_t &expect, uint32_t desired) {
     return __hip_atomic_compare_exchange_strong((ga_u32 *)p, &expect, desired, __ATOMIC_RELAXED, GA_ORDER);

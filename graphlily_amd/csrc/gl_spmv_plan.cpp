@@ -884,6 +884,7 @@ int gl_spmv_plan_destroy(gl_spmv_plan p) {
     (void)hipFree(p->d_scc_scratch);
     (void)hipFree(p->d_bicc_scratch);
     (void)hipFree(p->d_topo_scratch);
+    (void)hipFree(p->d_sssp_delta_scratch);
     (void)hipFree(p->d_msbfs_scratch);
     (void)hipFree(p->d_sim_scratch);
     (void)hipFree(p->d_clique_scratch);

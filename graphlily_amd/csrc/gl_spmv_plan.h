@@ -284,6 +284,10 @@ struct gl_spmv_plan_s {
     // gl_topo (gl_topo.hip), as plan_in: the call's scratch, allocated by the first call -- 256 bytes of control record, num_rows
     // dependency counters and num_rows words of queue
     unsigned char *d_topo_scratch = nullptr;
+    // gl_sssp_delta (gl_sssp_delta.hip), as plan_in: the call's scratch, allocated by the first call -- 256 bytes of control record
+    // and nine arrays of num_rows words: the two queues, the two far piles, the bucket's settled list, three stamps and the
+    // distance every vertex was last expanded at
+    unsigned char *d_sssp_delta_scratch = nullptr;
     // gl_msbfs (gl_msbfs.hip): the call's scratch, allocated by the first call -- 256 bytes of control record, 1280 bytes of
     // per-source counters, then three arrays of num_rows 64-bit words: the seen words and the two frontiers
     unsigned char *d_msbfs_scratch = nullptr;

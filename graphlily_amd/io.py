@@ -328,16 +328,19 @@ def simple_pattern(csr_matrix):
     return build(key_in), (None if symmetric else build(key_out)), symmetric
 
 
-def directed_weighted(csr_matrix, weighted=True):
-    """The matrix preparation of TopologicalOrder (an extension) -> (csr_in, csr_out, symmetric): simple_pattern's reading with
-    weights.  The diagonal is dropped; every other STORED entry A[v, u] is an edge u -> v, a stored 0 included (weight 0 is a
-    legitimate weight); an edge stored more than once gets its LARGEST value (the natural reading for a longest path); -0.0
+def directed_weighted(csr_matrix, weighted=True, keep="largest"):
+    """The matrix preparation of TopologicalOrder and ShortestPaths (extensions) -> (csr_in, csr_out, symmetric): simple_pattern's
+    reading with weights.  The diagonal is dropped; every other STORED entry A[v, u] is an edge u -> v, a stored 0 included
+    (weight 0 is a legitimate weight); an edge stored more than once gets its LARGEST value (the natural reading for a longest
+    path; keep="smallest": the SMALLEST, as parallel edges collapse for a shortest one -- symmetrize_weighted's argument); -0.0
     becomes +0.0; NaN and +-inf raise ValueError naming the first offending entry.  Row v of csr_in lists the predecessors of
     v, row u of csr_out (the transposed pattern) the successors of u, each with the edge's weight in adj_data; both are n x n,
     n = max(num_rows, num_cols), the columns of every row ascending.  `symmetric` says whether the two PATTERNS are the same;
     csr_out is returned even then, because its weights are the transposed ones.  weighted=False returns exactly what
     simple_pattern returns (zero values are no edges, every value 1, csr_out None for a symmetric pattern).  Applied after
     padding: padding vertices have empty rows."""
+    if keep not in ("smallest", "largest"):
+        raise ValueError("directed_weighted: keep is %r, not \"smallest\" or \"largest\"" % (keep,))
     if not weighted:
         return simple_pattern(csr_matrix)
     n = max(int(csr_matrix.num_rows), int(csr_matrix.num_cols))
@@ -355,7 +358,7 @@ def directed_weighted(csr_matrix, weighted=True):
     if rows.shape[0] > 0xFFFFFFFF:
         raise ValueError("directed_weighted: %d entries do not fit 32-bit offsets" % rows.shape[0])
     key = rows * n + cols
-    order = np.lexsort((-w, key))                                             # by entry, the largest value of each first
+    order = np.lexsort((w if keep == "smallest" else -w, key))                # by entry, the value to keep of each first
     key, w = key[order], w[order]
     once = np.ones(key.shape[0], dtype=bool)
     once[1:] = key[1:] != key[:-1]

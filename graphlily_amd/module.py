@@ -469,6 +469,23 @@ class SpMVModule(BaseModule):
         self._finish(level_buf, order_buf, dist_buf, parent_buf)
         return stats
 
+    def sssp_delta(self, out_module, weight_buf, weight_out_buf, sources, delta, dist_buf, parent_buf=None):
+        """Extension (gl_sssp_delta): delta-stepping shortest paths over this module's matrix, read as a directed graph -- row v:
+        the predecessors of v, `out_module` (None: the pattern is symmetric) holds the transposed pattern -- from `sources`
+        (host vertex numbers, all at distance 0) into `dist_buf` (get_num_rows() floats: Dijkstra's f32 result to the bit,
+        whatever `delta`, a float > 0 or +inf; the bits 0x7f800000 when unreached) -> (reached, buckets, rounds, relaxations,
+        launches).  `weight_buf` and `weight_out_buf` (get_nnz() floats each, finite and >= +0.0) are aligned with this
+        matrix's entries and with out_module's.  `parent_buf` (optional, get_num_rows() words) receives the predecessor tree,
+        ties to the smallest predecessor.  The call synchronises.  Raises GraphLilyError (GL_ERR_UNSUPPORTED) when a plan keeps
+        no row copy (only the (||,&&) layout does), is not square, is a row shard, its rows are no strictly ascending sets, or
+        the two are not each other's transpose (io.directed_weighted prepares them)."""
+        if self.plan_ is None or (out_module is not None and out_module.plan_ is None):
+            _fatal("SpMVModule.sssp_delta: send_matrix_host_to_device first")
+        stats = self.plan_.sssp_delta(None if out_module is None else out_module.plan_, weight_buf, weight_out_buf, sources, delta, dist_buf,
+                                      parent_buf)
+        self._finish(dist_buf, parent_buf)
+        return stats
+
     def msbfs(self, sources, far_buf, reach_buf, harmonic_buf, accumulate=False, hops_buf=None):
         """Extension (gl_msbfs): the bit-parallel breadth-first search from up to 64 `sources` (host vertex numbers) over this
         module's matrix, read as a directed graph -- row v: the predecessors of v, so the distances run FROM the sources; the

@@ -51,6 +51,39 @@ protected:
         }
     }
 
+    // What the drivers whose kernels take a directed pattern as TWO plans share (TopologicalOrder, ShortestPaths): the pattern of
+    // g with every value 1 (the row copy would store a zero value as no entry) ...
+    static CSRMatrix<float> ones_of(CSRMatrix<float> const &g) {
+        CSRMatrix<float> ones = g;
+        ones.adj_data.assign(ones.adj_indices.size(), 1.0f);
+        return ones;
+    }
+    // ... the transposed pattern's module, created by the first load that needs two plans (owned by the collection from then on;
+    // runtime_up: set_up_runtime has run, so the new module gets what ModuleCollection::set_up_runtime gives every module) ...
+    void load_transposed(graphlily::module::SpMVModule<graphlily::val_t, graphlily::val_t> *&out, CSRMatrix<float> const &graph_out,
+                         bool skip_empty_rows, bool runtime_up) {
+        if (!out) {
+            out = new graphlily::module::SpMVModule<graphlily::val_t, graphlily::val_t>(num_channels_, spmv_out_buf_len_, vec_buf_len_);
+            out->set_semiring(graphlily::LogicalSemiring);
+            out->set_mask_type(graphlily::kNoMask);
+            add_module(out);
+            if (runtime_up) {
+                out->set_device(device_);
+                out->set_unused_args();
+                out->set_mode();
+                out->set_blocking(getenv("GRAPHLILY_BLOCKING") != nullptr && atoi(getenv("GRAPHLILY_BLOCKING")) != 0);
+            }
+        }
+        out->load_and_format_matrix(ones_of(graph_out), skip_empty_rows);
+    }
+    // ... and a buffer of the weights of g, aligned with its entries
+    static DeviceBuffer upload_weights(CSRMatrix<float> const &g) {
+        const size_t nnz = g.adj_data.size();
+        DeviceBuffer buf(sizeof(float) * (nnz ? nnz : 1));
+        if (nnz) buf.upload(g.adj_data.data(), sizeof(float) * nnz);
+        return buf;
+    }
+
     // gl_kcore on the same plan -> a degeneracy ordering of the padded matrix's vertices (what the "smallest_last" colouring order
     // is made of) and, if asked for, the degeneracy.  The call waits for the device.
     std::vector<uint32_t> peel_order(uint32_t *degeneracy = nullptr) {

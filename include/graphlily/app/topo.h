@@ -25,7 +25,7 @@ namespace app {
 
 class TopologicalOrder : public app::PatternApp {
 private:
-    // the transposed pattern's module: created by the first load that needs two plans (owned by the collection from then on)
+    // the transposed pattern's module (PatternApp::load_transposed)
     graphlily::module::SpMVModule<graphlily::val_t, graphlily::val_t> *out_ = nullptr;
     CSRMatrix<float> graph_, graph_out_;
     DeviceBuffer weight_, weight_out_;
@@ -35,12 +35,6 @@ private:
     std::vector<uint64_t> level_sizes_;
     uint64_t num_peeled_ = 0, widest_ = 0, launches_ = 0;
     float critical_length_ = 0.0f;
-
-    static CSRMatrix<float> ones_of(CSRMatrix<float> const &g) {
-        CSRMatrix<float> ones = g;
-        ones.adj_data.assign(ones.adj_indices.size(), 1.0f);
-        return ones;
-    }
 
     // get_nnz() counts the edges of the directed graph
     CSRMatrix<float> prepare(CSRMatrix<float> &padded) override {
@@ -62,33 +56,15 @@ public:
     void load_and_format_matrix(std::string csr_float_npz_path, bool skip_empty_rows, bool weighted = false) {
         weighted_ = weighted;
         PatternApp::load_and_format_matrix(csr_float_npz_path, skip_empty_rows);      // (calls prepare())
-        if (symmetric_) return;
-        if (!out_) {
-            out_ = new graphlily::module::SpMVModule<graphlily::val_t, graphlily::val_t>(num_channels_, spmv_out_buf_len_, vec_buf_len_);
-            out_->set_semiring(graphlily::LogicalSemiring);
-            out_->set_mask_type(graphlily::kNoMask);
-            add_module(out_);
-            if (runtime_up_) {      // what ModuleCollection::set_up_runtime does per module
-                out_->set_device(device_);
-                out_->set_unused_args();
-                out_->set_mode();
-                out_->set_blocking(getenv("GRAPHLILY_BLOCKING") != nullptr && atoi(getenv("GRAPHLILY_BLOCKING")) != 0);
-            }
-        }
-        out_->load_and_format_matrix(ones_of(graph_out_), skip_empty_rows);
+        if (!symmetric_) load_transposed(out_, graph_out_, skip_empty_rows, runtime_up_);
     }
 
     void send_matrix_host_to_device() {
         PatternApp::send_matrix_host_to_device();
         if (!symmetric_) out_->send_matrix_host_to_device();
         if (!weighted_) return;
-        const size_t nnz = graph_.adj_data.size();
-        weight_ = DeviceBuffer(sizeof(float) * (nnz ? nnz : 1));
-        weight_out_ = DeviceBuffer(sizeof(float) * (nnz ? nnz : 1));
-        if (nnz) {
-            weight_.upload(graph_.adj_data.data(), sizeof(float) * nnz);
-            weight_out_.upload(graph_out_.adj_data.data(), sizeof(float) * nnz);
-        }
+        weight_ = upload_weights(graph_);
+        weight_out_ = upload_weights(graph_out_);
     }
 
     // levels of the padded matrix's vertices (padding vertices are isolated: level 0); reverse swaps the two plans: heights, and

@@ -369,9 +369,11 @@ bool util_simple_pattern(CSRMatrix<data_type> const &m, CSRMatrix<data_type> &in
 // than once gets its LARGEST value; -0.0 becomes +0.0; a NaN or an infinity prints and exits.  Row v of `in` lists the
 // predecessors of v, row u of `out` (the transposed pattern) the successors of u, each with the edge's weight in adj_data; both n
 // x n, n = max(num_rows, num_cols), columns ascending.  Returns whether the two PATTERNS are the same; `out` is filled even then
-// (its weights are the transposed ones).  weighted = false is util_simple_pattern itself.  Apply after padding.
+// (its weights are the transposed ones).  weighted = false is util_simple_pattern itself.  keep_smallest (app::ShortestPaths):
+// an edge stored more than once gets its SMALLEST value instead.  Apply after padding.
 template <typename data_type>
-bool util_directed_weighted(CSRMatrix<data_type> const &m, CSRMatrix<data_type> &in, CSRMatrix<data_type> &out, bool weighted = true) {
+bool util_directed_weighted(CSRMatrix<data_type> const &m, CSRMatrix<data_type> &in, CSRMatrix<data_type> &out, bool weighted = true,
+                            bool keep_smallest = false) {
     if (!weighted) return util_simple_pattern(m, in, out);
     const uint64_t n = std::max(m.num_rows, m.num_cols);
     std::vector<std::pair<uint64_t, data_type>> entry;          // {row * n + column, weight}
@@ -387,10 +389,11 @@ bool util_directed_weighted(CSRMatrix<data_type> const &m, CSRMatrix<data_type> 
             }
             entry.push_back(std::make_pair(v * n + u, w));
         }
-    std::sort(entry.begin(), entry.end());                      // by entry, the largest value of each last
+    std::sort(entry.begin(), entry.end());                      // by entry, the smallest value of each first, the largest last
     std::vector<std::pair<uint64_t, data_type>> once, back;
     for (size_t i = 0; i < entry.size(); i++)
-        if (i + 1 == entry.size() || entry[i + 1].first != entry[i].first) once.push_back(entry[i]);
+        if (keep_smallest ? (i == 0 || entry[i - 1].first != entry[i].first) : (i + 1 == entry.size() || entry[i + 1].first != entry[i].first))
+            once.push_back(entry[i]);
     back.reserve(once.size());
     for (auto const &e : once) back.push_back(std::make_pair(e.first % n * n + e.first / n, e.second));
     std::sort(back.begin(), back.end());

@@ -22,6 +22,7 @@
 #include "graphlily_hip_msbfs.h"
 #include "graphlily_hip_sim.h"
 #include "graphlily_hip_clique.h"
+#include "graphlily_hip_sssp_delta.h"
 #include "graphlily/io/data_formatter.h"
 #include "graphlily/io/data_loader.h"
 #include "graphlily/module/base_module.h"
@@ -324,6 +325,21 @@ public:
               uint32_t *parent = nullptr, uint64_t *stats = nullptr) {
         barrier_();
         GRAPHLILY_CHECK(gl_topo(plan_, out ? out->plan_ : plan_, weight, (uint32_t *)level.ptr(), order, dist, parent, stats));
+        finish_();
+    }
+    // extension (gl_sssp_delta, graphlily_hip_sssp_delta.h): delta-stepping shortest paths over this module's matrix, read as a
+    // directed graph -- row v: the predecessors of v; `out` holds the transposed pattern (nullptr: the pattern is symmetric); both
+    // in the (||,&&) layout, rows strictly ascending (graphlily::io::util_directed_weighted prepares them) -- from the
+    // num_sources vertices `sources` (DEVICE words), all at distance 0, into `dist` (get_num_rows() device floats: Dijkstra's f32
+    // result to the bit whatever `delta`, a float > 0 or +inf; the bits 0x7f800000 when unreached).  `weight` and `weight_out`
+    // (get_nnz() device floats each, finite and >= +0.0) are aligned with this matrix's entries and with out's.  `parent`
+    // (get_num_rows() device words, or nullptr) receives the predecessor tree, ties to the smallest predecessor.  stats (optional,
+    // 5 host words) receives {reached, buckets, rounds, relaxations, launches}.  The call synchronises.
+    void sssp_delta(SpMVModule *out, const float *weight, const float *weight_out, const uint32_t *sources, uint32_t num_sources,
+                    float delta, DeviceBuffer dist, uint32_t *parent = nullptr, uint64_t *stats = nullptr) {
+        barrier_();
+        GRAPHLILY_CHECK(gl_sssp_delta(plan_, out ? out->plan_ : plan_, weight, weight_out, sources, num_sources, delta, (float *)dist.ptr(),
+                                      parent, stats));
         finish_();
     }
     // extension (gl_msbfs, graphlily_hip_msbfs.h): the bit-parallel breadth-first search from the k <= 64 vertices `sources` (host
