@@ -1,10 +1,14 @@
 // The plain CSR row copy that a GL_PLAN_BOOLEAN plan keeps (gl_spmv_plan.h: d_csr_indptr / d_csr_indices / csr_nz_base), as the
-// graph kernels that walk it see it -- gl_bfs_parents, gl_cc, gl_tc, gl_kcore, gl_color, gl_truss, gl_bc, gl_scc, gl_bicc, gl_topo, gl_msbfs, gl_sim, gl_clique, gl_lpa, and gl_msf,
-// gl_match, gl_louvain and gl_spgemm (which also take a value per entry of the copy from their caller): what a caller may require of it,
-// the verdicts about it that the plan caches, the few helpers every such kernel wants, and the walk over a row -- a thread per
-// row, then the wavefront -- that ten of them run and gl_bc copies (rows_walk_*, at the end; gl_tc, gl_truss, gl_sim and gl_clique intersect rows
-// instead, gl_spgemm forms product rows; these keep their contract cases in their own test files).  gl_rows.hip holds the check kernels.  A new caller adds itself to tests/test_gpu_rows.py (the contract) and
-// tests/test_gpu_walk.py (the walk).
+// graph kernels that walk it see it -- gl_bfs_parents, gl_cc, gl_tc, gl_kcore, gl_color, gl_truss, gl_bc, gl_scc, gl_bicc, gl_topo,
+// gl_msbfs, gl_sim, gl_clique, gl_contract, gl_lpa, and gl_msf, gl_match, gl_louvain, gl_spgemm and gl_sssp_delta (which also take a
+// value per entry of the copy from their caller): what a caller may require of it, the verdicts about it that the plan caches, the
+// few helpers every such kernel wants, and the walk over a row -- a thread per row, then the wavefront -- that eleven of them run
+// and gl_bc copies (rows_walk_*, at the end; gl_tc, gl_truss, gl_sim and gl_clique intersect rows instead, gl_spgemm forms product
+// rows, gl_contract streams a group's member rows and uses the takeover for its row sums).  gl_rows.hip holds the check kernels.
+// A new caller adds itself to tests/test_gpu_rows.py (the contract: every caller above is called there before and behind every
+// other on one plan; the wording of its refusals stays in its own test file), to tests/test_gpu_walk.py (the walk: there, or in
+// a star test of its own that the file's header names) and, when it runs rounds_run or reads the staging words, to
+// tests/test_gpu_rounds.py.
 // gl_rounds.h, on top of this, holds what the kernels that run in rounds over a queue share: the atomics of their memory rule,
 // the queue append, the peel record and the gated host loop.
 #ifndef GL_ROWS_H_
@@ -42,7 +46,7 @@ int rows_check_sorted(gl_spmv_plan p);
 // partner == p asks whether the pattern is symmetric (diagonal entries are then not looked up): kRowsSymmetric's verdict.
 int rows_check_transpose(gl_spmv_plan p, gl_spmv_plan partner, bool *ok);
 // The refusals of the calls that take a pattern as TWO plans, plan_in (row v: the vertices v is pulled from) and plan_out (the
-// transposed pattern; plan_out == plan_in declares the pattern symmetric) -- gl_bc_accumulate, gl_scc, gl_topo -- in this order:
+// transposed pattern; plan_out == plan_in declares the pattern symmetric) -- gl_bc_accumulate, gl_scc, gl_topo, gl_sssp_delta -- in this order:
 // rows_require(plan_in, kRowsSymmetric if the two are one plan, else kRowsSets), rows_require(plan_out, kRowsSets), as many
 // vertices, and plan_out IS the transpose: as many entries and rows_check_transpose, whose verdict plan_in caches for the last
 // partner (by handle and uid).  All GL_ERR_UNSUPPORTED.
@@ -85,7 +89,8 @@ __device__ __forceinline__ uint32_t rows_lower_bound(P s, uint32_t n, uint32_t w
 }
 
 // THE WALK over the entries [beg, end) of one row per lane, 64 rows per wavefront (gl_bfs_parents, gl_cc, gl_kcore, gl_msf, gl_match,
-// gl_color, gl_scc, gl_bicc, gl_topo and gl_msbfs run all of it -- match_collect_kernel with a copy of the thread steps in which every lane takes every step --,
+// gl_color, gl_scc, gl_bicc, gl_topo, gl_msbfs and gl_sssp_delta run all of it -- match_collect_kernel and sssp_round_kernel with a
+// copy of the thread steps in which every lane takes every step --,
 // gl_lpa and gl_louvain the takeover and the wavefront's steps behind a thread path of their own; DESIGN.md 4.13.  bc_sweep_kernel of
 // gl_bc keeps a copy of its own, in the same forms: through these templates its accumulate figure on one stand-in was 1 - 2 % above
 // the parent's worse run in two visits, EXPERIMENTS.md Round 21):

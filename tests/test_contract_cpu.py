@@ -89,3 +89,25 @@ def test_directed_statement_is_the_condensation():
     assert 1 < c.num_rows < n and np.array_equal(c.adj_indptr, dag.adj_indptr) and np.array_equal(c.adj_indices, dag.adj_indices)
     assert np.array_equal(part, rank[labels]) and int(w.sum()) <= graph.nnz and int(tot.sum()) == graph.nnz
     assert app.validate_quotient(raw, labels, (c, w, tot, part)) == c.num_rows
+
+
+@pytest.mark.parametrize("members", [18, 65, 129])
+def test_walk_stars_one_entry_of_every_hub_row_decides(members):
+    """the inputs of tests/test_gpu_contract.py::test_walk_stars_in_one_group: without the last (first) entry of every hub row and
+    its mirror, the product row of the hubs' group loses every such leaf that is not a member itself, and the group's tot the
+    weight of all 17 -- so a walk that loses one end of a member row cannot return io.aggregate_communities' answer"""
+    from test_gpu_contract import contract_stars
+    from test_gpu_walk import _stars, star_hubs
+    hubs, last = star_hubs(1), _stars()[4]
+    g, labels, weights = contract_stars(members)
+    c, w, tot, part = io.aggregate_communities(g, weights, None, labels)
+    row = set(c.adj_indices[:c.adj_indptr[1]].tolist())
+    assert len(row) == 2519 - (members - 18) and np.count_nonzero(part == 0) == members
+    for drop, gone in (("last", last), ("first", hubs + 1)):
+        less = contract_stars(members, drop)
+        cl, wl, totl, partl = io.aggregate_communities(less[0], less[2], None, less[1])
+        assert np.array_equal(partl, part) and less[0].nnz == g.nnz - 2 * 17
+        lost = row - set(cl.adj_indices[:cl.adj_indptr[1]].tolist())
+        assert lost == set(part[gone][part[gone] != 0].tolist()) and (members > 18 or len(lost) == 17)
+        assert tot[0] - totl[0] == sum(int(weights[g.adj_indptr[h]:g.adj_indptr[h + 1]][-1 if drop == "last" else 0]) for h in hubs) + \
+            sum(int(weights[g.adj_indptr[v]]) for v in gone if part[v] == 0)

@@ -5,8 +5,11 @@ d_tree -- is a function of the graph, so every comparison is exact, and a failur
 and the first index that differ.  Every test runs with the default dealing of the rows and with bicc_cut=0, every output buffer
 starts as garbage with 64 guard words behind it, and every case is called twice on one plan.
 
-gl_rows.h asks a new caller of the contract and of the walk to add itself to tests/test_gpu_rows.py and tests/test_gpu_walk.py;
-this caller's contract and walk tests are here instead and import the shared inputs from those modules."""
+gl_rows.h asks a new caller of the contract and of the walk to add itself to tests/test_gpu_rows.py and tests/test_gpu_walk.py:
+tests/test_gpu_rows.py calls gl_bicc before and behind every other asker of the cached verdicts, tests/test_gpu_rounds.py runs it
+before and behind the other users of rounds_run and of the staging words (bicc_batch 1 and default), and tests/test_gpu_walk.py
+points at test_walk_stars below, which runs the walk's boundaries on that module's stars at the cuts 0, 4, 8 and the default.
+This file keeps the refusals' wording (test_contract)."""
 import ctypes
 import os
 import subprocess
@@ -20,7 +23,7 @@ from helpers import set_knob
 from test_bicc_cpu import (BICC_DRIVER, CASES, DEGREES, EXPECTED, GOLDEN, RESULTS, TREE, bicc_case, bicc_model_of,
                            build_cpp_driver)
 from test_cc_cpu import permute_rows
-from test_gpu_rows import _bool_plan, _graph
+from test_gpu_kcore import _bool_plan, _graph
 from test_gpu_walk import N as STAR_N, _stars
 from test_kcore_cpu import _csr
 

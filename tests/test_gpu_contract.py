@@ -3,8 +3,9 @@ app.QuotientGraph, Louvain.run(aggregate="device")) against io.aggregate_communi
 statement app.validate_quotient uses, which tests/test_contract_cpu.py checks against condensation().  Every comparison is
 np.array_equal.  Every test runs with the default paths, with contract_wave=0 (no wavefront path) and with contract_lds=0 (every
 group in a slab); the boundary cases also shrink the tables to 64 and 256 slots.  Outputs start as garbage with guard words
-behind them, and every check is made twice: the second call runs from the cached scratch.  This caller's contract cases
-(gl_rows.h) live here."""
+behind them, and every check is made twice: the second call runs from the cached scratch.  This caller's refusals live here;
+tests/test_gpu_rows.py calls it before and behind every other asker of the plan's cached verdicts, and
+test_walk_stars_in_one_group below is its part of tests/test_gpu_walk.py."""
 import functools
 import os
 import subprocess
@@ -18,6 +19,7 @@ from helpers import set_knob
 from test_contract_cpu import QUOTIENT_DRIVER, directed_graph, smallest_member
 from test_gpu_louvain import _driver as louvain_driver
 from test_gpu_spgemm import G32, GUARD, _bins, _plan, random_pair
+from test_gpu_walk import N as STAR_N, _star_edges, _stars
 from test_kcore_cpu import _csr as _csr_as_given
 from test_louvain_cpu import driver_graph
 from test_spgemm_cpu import GOLDEN
@@ -122,6 +124,34 @@ def test_one_group_at_every_table_boundary(gpu, mode, monkeypatch, kind, c):
     g, labels, weights = group_case(kind, c)
     got = _check(g, labels, mode, weights, tables=tables, what="%s c=%d" % (kind, c))[0]
     assert got.adj_indptr[1] == c
+
+
+@functools.lru_cache(maxsize=None)
+def contract_stars(members=18, drop=None):
+    """tests/test_gpu_walk.py's stars -> (symmetric graph, labels, entry weights): group 0 = the 18 hubs and, for 65 and 129
+    members, the first 47 and 111 leaves (those of the smallest stars) with them; every other vertex a group of its own.  The
+    weights 1 .. 3 depend on the entry's two vertices only.  `drop`: without every hub's last (first) entry and its mirror."""
+    hub, leaf, kept = _star_edges(drop)
+    g = _symmetric(STAR_N, hub[kept], leaf[kept])
+    labels = np.arange(STAR_N, dtype=np.uint32)
+    labels[_stars()[3]] = 0
+    labels[leaf[:members - 18]] = 0
+    rows = np.repeat(np.arange(STAR_N), np.diff(g.adj_indptr.astype(np.int64)))
+    return g, labels, (1 + (rows + g.adj_indices) % 3).astype(np.uint32)
+
+
+@pytest.mark.parametrize("members", [18, 65, 129])
+def test_walk_stars_in_one_group(gpu, mode, members):
+    """18 long member rows of every boundary length -- 0, 1, 3 .. 545 entries -- in ONE 64-member window of contract_stream, where
+    group_case's members have one to three entries or are alone; with 65 and 129 members the window scan crosses 64 and 128, the
+    long rows in the first window and one-entry rows behind them.  The product row holds every leaf outside the group: 2519
+    distinct neighbours with 18 members.  tot comes from the row sums (no vertex weights are given): a thread for a row of at most
+    16 entries, rows_walk_takeover for the longer ones.  tests/test_contract_cpu.py shows that C and tot change when the last or
+    the first entry of every hub row is lost."""
+    g, labels, weights = contract_stars(members)
+    c, w, tot, part = _check(g, labels, mode, weights, what="%d members" % members)
+    assert c.adj_indptr[1] == 2519 - (members - 18) and not part[_stars()[3]].any() and np.count_nonzero(part == 0) == members
+    assert tot[0] == weights[np.repeat(labels, np.diff(g.adj_indptr.astype(np.int64))) == 0].sum()
 
 
 @pytest.mark.parametrize("p", [65, 257, 1200])

@@ -1,34 +1,52 @@
 """What a plan knows about its row copy is shared state (csrc/gl_rows.h: rows_sorted, rows_are_sets, rows_symmetric, each
 established by whoever asks first, and the transpose partner that rows_require_pair caches): the outcome of every entry point
 that walks the rows must not depend on which of them touched the plan first.  The entry points: rows_sorted, gl_cc_labels and
-gl_bfs_parents (kRowsIndexable), gl_tc_count (kRowsSets), gl_kcore, gl_color, gl_msf, gl_truss, gl_match, gl_lpa and
-gl_louvain_move (kRowsSymmetric), gl_bc_accumulate and gl_scc (rows_require_pair; with one plan: kRowsSymmetric).  Every order
-below runs on a FRESH boolean plan and calls everything twice -- the second time from the cached verdicts -- on 256-vertex
-matrices: accepted calls return the host references' values, refused ones GL_ERR_UNSUPPORTED with the same message."""
+gl_bfs_parents (kRowsIndexable), gl_msbfs (kRowsSquare), gl_tc_count, gl_similarity, gl_clique_count, gl_spgemm_* (plan a = plan b,
+without a mask and with the plan as its own mask) and gl_contract_* (kRowsSets), gl_kcore, gl_color, gl_msf, gl_truss, gl_match,
+gl_lpa, gl_louvain_move and gl_bicc (kRowsSymmetric), gl_bc_accumulate, gl_scc, gl_topo and gl_sssp_delta (rows_require_pair; with
+one plan: kRowsSymmetric).  Every order below runs on a FRESH boolean plan and calls everything twice -- the second time from the
+cached verdicts -- on 256-vertex matrices: accepted calls return the host references' values, refused ones GL_ERR_UNSUPPORTED
+with the same message.  The launch helpers and the host models are those of the callers' own test files."""
+import functools
+
 import numpy as np
 import pytest
 
-from graphlily_amd import app, capi, io
+from graphlily_amd import app, capi, io, module as M
 
 from test_cc_cpu import permute_rows
 from test_coloring_cpu import greedy_by_priority
 from test_kcore_cpu import _csr
+from test_bicc_cpu import RESULTS, TREE, bicc_model_of
+from test_clique_cpu import clique_model
+from test_closeness_cpu import bits64, msbfs_model
 from test_gpu_bc import _bc, _levels
+from test_gpu_bicc import _bicc
 from test_gpu_cc import _labels_of
+from test_gpu_clique import _count as _cliques
+from test_gpu_contract import _contract
 from test_gpu_coloring import _color
 from test_gpu_kcore import _bool_plan, _clique_edges, _graph, _kcore, _sorted_rows
 from test_gpu_louvain import _move
 from test_gpu_lpa import _lpa
 from test_gpu_match import _match
+from test_gpu_msbfs import _msbfs
 from test_gpu_msf import _msf
 from test_gpu_scc import _scc
+from test_gpu_sim import _sim
+from test_gpu_spgemm import _product
+from test_gpu_sssp_delta import _call as _sssp_delta, bits, dijkstra_f32
 from test_gpu_tc import _count
+from test_gpu_topo import _topo
 from test_gpu_truss import _truss
 from test_louvain_cpu import move_loop
 from test_lpa_cpu import greedy_colors, propagate
 from test_match_cpu import FREE, greedy, pairs_of, pointer_rounds
 from test_msf_cpu import kruskal
 from test_scc_cpu import scc_model
+from test_similarity_cpu import similarity_model
+from test_spgemm_cpu import spgemm_model
+from test_topo_cpu import topo_model
 from test_truss_cpu import truss_numbers
 
 pytestmark = pytest.mark.gpu
@@ -36,8 +54,12 @@ pytestmark = pytest.mark.gpu
 N, SOURCE, SWEEPS = 256, 10, 10
 GARBAGE = 0xdeadbeef
 CALLS = ["rows_sorted", "cc_labels", "tc_count", "kcore", "bc_accumulate", "bfs_parents",
-         "color", "msf", "truss", "match", "lpa", "louvain_move", "scc"]
-SYMMETRIC_ONLY = ["kcore", "bc_accumulate", "color", "msf", "truss", "match", "lpa", "louvain_move", "scc"]      # kRowsSymmetric
+         "color", "msf", "truss", "match", "lpa", "louvain_move", "scc",
+         "bicc", "topo", "sssp_delta", "msbfs", "similarity", "clique", "spgemm", "spgemm_masked", "contract"]
+SYMMETRIC_ONLY = ["kcore", "bc_accumulate", "color", "msf", "truss", "match", "lpa", "louvain_move", "scc",
+                  "bicc", "topo", "sssp_delta"]                                                                   # kRowsSymmetric
+SETS_ONLY = ["tc_count", "similarity", "clique", "spgemm", "spgemm_masked", "contract"]                          # kRowsSets
+DELTA, CLIQUE_K, MSBFS_SOURCES = 3000.0, 4, [SOURCE, 20, 21, 0]      # (the K_5's weights lie on both sides of the delta)
 ORDERS = [CALLS[i:] + CALLS[:i] for i in range(len(CALLS))] + [CALLS[::-1]]      # every call first once and last once, and the reversed order
 
 
@@ -89,8 +111,54 @@ def _scc_expected(m):
     return lab, (comps, passes, trimmed)
 
 
+def _weighted(m, inputs):
+    return io.CSRMatrix(m.num_rows, m.num_cols, inputs["weights"][:m.nnz], m.adj_indices, m.adj_indptr)
+
+
+def _bicc_expected(m):
+    model = bicc_model_of(m)
+    return tuple(model[k].astype(np.uint32) for k in TREE + RESULTS) + ((model["blocks"], model["articulation"], model["bridges"], model["depth"], model["trees"]),)
+
+
+def _pair_expected(m, inputs):
+    """gl_topo and gl_sssp_delta with one plan -- the pattern declared symmetric --, the entry weights those of gl_msf and gl_match:
+    topo_model peels exactly the vertices without a neighbour; dijkstra_f32's distances as bits, its parents, and the reached"""
+    rows, cols = _entries(m)
+    level, dist, parent, stats = topo_model(m.num_rows, cols, rows, inputs["weights"][:m.nnz])
+    sd, sp, _ = dijkstra_f32(_weighted(m, inputs), [SOURCE])
+    return {"topo": (level, bits(dist), parent, np.flatnonzero(level != 0xffffffff), stats),
+            "sssp_delta": (bits(sd), sp, int(np.isfinite(sd).sum()))}
+
+
+def _sets_expected(m, inputs, symmetric):
+    """the callers of kRowsSets, and gl_msbfs (kRowsSquare), from their suites' host models; the quotient of a pattern that is not
+    symmetric is the directed statement, as tests/test_gpu_contract.py has it"""
+    w = inputs["weights"][:m.nnz].astype(np.uint32) if m.nnz else None
+    q = io.aggregate_communities(m, w, None, inputs["labels"]) if symmetric else app._quotient_of(m, inputs["labels"], w, None)
+    want = {"similarity": tuple(similarity_model(m, inputs["pairs"], inputs["vertex_weights"])) + (0,),
+            "clique": clique_model(m, CLIQUE_K),
+            "contract": (q[0].adj_indptr, q[0].adj_indices) + tuple(q[1:]) + (q[0].num_rows, q[0].nnz)}
+    for call, mask in (("spgemm", None), ("spgemm_masked", m)):
+        c = spgemm_model(m, m, M.kMulAdd, mask)[0]
+        want[call] = (c.adj_indptr, c.adj_indices, c.adj_data, c.nnz, c.nnz)
+    return want
+
+
+def _msbfs_expected(m):
+    far, reach, harmonic, hops, source_stats, levels = msbfs_model(m, MSBFS_SOURCES)
+    return far, reach, bits64(harmonic), hops, source_stats, tuple(levels)
+
+
+def _more_inputs(m):
+    """what the eight newer calls take beside the plan: the matrix itself (its entry count, and the weights' alignment), the pairs
+    among the K_5, the edge {20, 21} and vertex 0, u == v included, 64-bit vertex weights, and labels that cut the K_5 in two"""
+    v, n = np.array([0, 10, 11, 12, 13, 14, 20, 21]), m.num_rows
+    return {"graph": m, "pairs": np.stack(np.meshgrid(v, v, indexing="ij"), axis=-1).reshape(-1, 2), "vertex_weights": (1 << 40) + np.arange(n, dtype=np.uint64),
+            "labels": (np.arange(n) // 3 * 3).astype(np.uint32)}
+
+
 def _symmetric_expected(m, inputs):
-    """the seven callers that only a symmetric matrix reaches, from their suites' host models"""
+    """the callers that only a symmetric matrix reaches, from their suites' host models"""
     weighted = io.CSRMatrix(N, N, inputs["weights"], m.adj_indices, m.adj_indptr)
     mate, rounds, scans = pointer_rounds(weighted)
     assert np.array_equal(mate, greedy(weighted))
@@ -104,33 +172,43 @@ def _symmetric_expected(m, inputs):
             "match": (mate, (len(pairs_of(mate)), rounds, scans)),
             "lpa": (lab, (sweeps, changes, evals, converged)),
             "louvain_move": (moved[0], tuple(moved[1:])),
-            "scc": _scc_expected(m)}
+            "scc": _scc_expected(m), "bicc": _bicc_expected(m), **_pair_expected(m, inputs)}
 
 
 def _expected(name, m):
     """call -> the value it must return, or the message fragment it must be refused with; and what the calls take beside the plan"""
     level = _levels(m, None, [SOURCE], N)
-    inputs = {"level": level, "weights": _weights(m), "colors": greedy_colors(_matrices()["symmetric"]), "nnz": m.nnz}
+    inputs = {"level": level, "weights": _weights(m), "colors": greedy_colors(_matrices()["symmetric"]), "nnz": m.nnz, **_more_inputs(m)}
     sigma, delta = app.betweenness_by_levels(m, None, level)
     want = {"rows_sorted": name != "shuffled",
             "cc_labels": app._components_of(m.adj_indptr, m.adj_indices, None, N).astype(np.uint32),
             "tc_count": _triangles_by_definition(m),
             "kcore": app._core_numbers_of(m.adj_indptr, m.adj_indices, N).astype(np.uint32),
             "bc_accumulate": (np.where(level >= 2, delta, 0.0), sigma),
-            "bfs_parents": _parents_by_definition(m, level)}
+            "bfs_parents": _parents_by_definition(m, level), "msbfs": _msbfs_expected(m)}
+    if name != "shuffled":
+        want.update(_sets_expected(m, inputs, name == "symmetric"))
     if name == "symmetric":
         want.update(_symmetric_expected(m, inputs))
-    # the refusals, in rows_require's order: the sets before the symmetry, and gl_tc_count asks for the sets only
+    # the refusals, in rows_require's order: the sets before the symmetry; gl_tc_count and the other callers of kRowsSets ask for
+    # the sets only, gl_msbfs for neither
     if name == "one_way":
         want.update({call: "not symmetric" for call in SYMMETRIC_ONLY})
     if name == "shuffled":
-        want.update({call: "strictly ascending" for call in SYMMETRIC_ONLY + ["tc_count"]})
+        want.update({call: "strictly ascending" for call in SYMMETRIC_ONLY + SETS_ONLY})
     assert sorted(want) == sorted(CALLS)
     return inputs, want
 
 
+@functools.lru_cache(maxsize=None)
+def _case(name):
+    """-> (matrix, inputs, want), computed once and shared by every order; never written"""
+    m = _matrices()[name]
+    return (m,) + _expected(name, m)
+
+
 def _call(plan, call, inputs, plan_out=None):
-    """(plan_out: for the two calls that take a second plan; None declares the pattern symmetric)"""
+    """(plan_out: for the four calls that take a second plan; None declares the pattern symmetric)"""
     level = inputs["level"]
     n = level.shape[0]
     if call == "rows_sorted":
@@ -163,6 +241,33 @@ def _call(plan, call, inputs, plan_out=None):
     if call == "scc":
         label, stats = _scc(plan, plan_out, n)
         return label, stats[:3]
+    nnz = inputs["graph"].nnz if "graph" in inputs else 0
+    if call == "bicc":
+        got, stats = _bicc(plan, n, nnz)
+        return tuple(got[k] for k in TREE + RESULTS) + (stats[:4] + stats[5:],)
+    if call == "topo":
+        w = inputs["weights"][:nnz] if nnz else np.ones(1, np.float32)
+        level, order, dist, parent, stats = _topo(plan, plan_out, n, w)
+        return level, dist, parent, np.sort(order[:stats[0]]), stats[:3]
+    if call == "sssp_delta":
+        g = _weighted(inputs["graph"], inputs)
+        dist, parent, stats = _sssp_delta(plan, plan_out, g, inputs.get("graph_out", g), inputs.get("sources", [SOURCE]), DELTA)
+        return dist, parent, stats[0]
+    if call == "msbfs":
+        got = _msbfs(plan, n, MSBFS_SOURCES)
+        return got[:5] + (got[5][:2],)
+    if call == "similarity":
+        common, weighted, stats = _sim(plan, inputs["pairs"], inputs["vertex_weights"])
+        return common, weighted, stats[0]
+    if call == "clique":
+        return _cliques(plan, n, CLIQUE_K)[:2]
+    if call in ("spgemm", "spgemm_masked"):
+        ones = capi.DeviceBuffer.from_host(np.ones(max(1, nnz), np.float32))
+        c, sym, num = _product(plan, plan, ones, ones, n, M.kMulAdd, plan if call == "spgemm_masked" else None)
+        return c.adj_indptr, c.adj_indices, c.adj_data, sym[0], num[0]
+    if call == "contract":
+        c, w, tot, part, sym, num = _contract(plan, n, inputs["labels"], inputs["weights"][:nnz].astype(np.uint32) if nnz else None)
+        return c.adj_indptr, c.adj_indices, w, tot, part, sym[0], sym[1]
     parent = capi.DeviceBuffer(4 * n)
     plan.bfs_parents(capi.DeviceBuffer.from_host(np.ascontiguousarray(level, np.float32)), parent)
     capi.sync()
@@ -193,14 +298,18 @@ def _run(plan, order, inputs, want):
 
 @pytest.mark.parametrize("name", ["symmetric", "one_way", "shuffled"])
 def test_outcomes_do_not_depend_on_who_asks_first(gpu, name):
-    m = _matrices()[name]
-    inputs, want = _expected(name, m)
+    m, inputs, want = _case(name)
     assert want["tc_count"] == "strictly ascending" or want["tc_count"][0] == 60             # K_5: ten triangles, six times each
+    assert want["msbfs"][3][0, 11] == 1 and want["msbfs"][5][0] == 1                         # (accepted on all three: vertex 11 is a step from 10)
+    if name != "shuffled":
+        assert want["clique"][0] == 5 * 4 * 3 * 2 and want["similarity"][0][1 * 8 + 2] == 3 and want["spgemm"][2][want["spgemm"][0][10]] == 4
+        assert want["spgemm_masked"][3] == 5 * 4 + 0 and want["contract"][5:] == ((N + 2) // 3, 4 if name == "symmetric" else 3)
     if name == "symmetric":                                  # the closed forms, so that no comparison is between two empty answers
         assert int(want["color"].max()) == 4 and int(want["msf"][0].sum()) == 2 * 5 and want["truss"][2][:2] + want["truss"][2][3:] == (5, 2, 11, 10)
         assert want["match"][1][0] == 3 and want["scc"][1] == (1 + 1 + 249, 1, 249)
         assert np.unique(want["lpa"][0][10:15]).shape[0] == 1 == np.unique(want["louvain_move"][0][10:15]).shape[0]
         assert want["lpa"][1][3] == 1 and want["louvain_move"][1][3] == 1 and want["louvain_move"][1][5] > want["louvain_move"][1][4]
+        assert want["bicc"][-1][:3] + want["bicc"][-1][4:] == (2, 0, 1, N - 7 + 2) and want["topo"][4] == (N - 7, 1, N - 7) and want["sssp_delta"][2] == 5
     for order in ORDERS:
         _run(_bool_plan(m), order, inputs, want)
 
@@ -234,6 +343,55 @@ def test_the_transpose_partner_is_cached_per_handle(gpu):
             assert _same(_call(pin, call, inputs, pout), want[call]), call
 
 
+PAIR_CALLS = ["bc_accumulate", "scc", "topo", "sssp_delta"]
+
+
+def test_the_partner_cache_serves_its_four_users_alike(gpu):
+    """rows_require_pair keeps ONE verdict, "the last partner", for gl_bc_accumulate, gl_scc, gl_topo and gl_sssp_delta.  Three
+    plans: p_in (the one-way matrix), p_out (its transpose) and p_other (as many rows and entries, but p_in's own pattern).  The
+    four calls alternate between the two partners in two interleavings, the second of which begins with the wrong one: every call
+    with p_out returns its host model's values, every call with p_other is refused with "not the transpose", whoever stored the
+    verdict last.  Then p_out is destroyed and plans of p_in's own pattern are created until one gets p_out's handle: the verdict
+    was stored under p_out's uid and must not serve the new plan."""
+    cin = _matrices()["one_way"]
+    rows, cols = _entries(cin)
+    cout = _sorted_rows(_csr(N, cols, rows))
+    level = _levels(cin, cout, [SOURCE], N)
+    inputs = {"level": level, "weights": _weights(cin), "graph": cin, "sources": [SOURCE, 21]}
+    inputs["graph_out"] = io.CSRMatrix(N, N, _weights(cout), cout.adj_indices, cout.adj_indptr)
+    sigma, delta = app.betweenness_by_levels(cin, cout, level)
+    want = {"scc": _scc_expected(cin), "bc_accumulate": (np.where(level >= 2, delta, 0.0), sigma), **_pair_expected(cin, inputs)}
+    sd, sp, _ = dijkstra_f32(_weighted(cin, inputs), inputs["sources"])
+    want["sssp_delta"] = (bits(sd), sp, int(np.isfinite(sd).sum()))
+    # 21 -> 20 is no cycle: 20 is peeled behind 21, and reached from it over the edge's weight
+    assert want["topo"][4] == (N - 5, 2, N - 6) and want["topo"][0][20] == 1 and want["topo"][2][20] == 21
+    assert want["sssp_delta"][2] == 5 + 2 and sd[20] == 1 + 20 * N + 21 and sp[20] == 21
+    a, b = PAIR_CALLS, PAIR_CALLS[::-1]
+    interleavings = ([(c, i % 2 == 0) for i, c in enumerate(a)] + [(c, i % 2 == 1) for i, c in enumerate(a)],
+                     [(c, i % 2 == 1) for i, c in enumerate(b)] + [(c, i % 2 == 0) for i, c in enumerate(b)])
+    for steps in interleavings:
+        pin, pout, pother = _bool_plan(cin), _bool_plan(cout), _bool_plan(cin)
+        for time in range(2):
+            for call, right in steps:
+                where = "%s with %s, time %d of %s" % (call, "p_out" if right else "p_other", time, steps)
+                if right:
+                    assert _same(_call(pin, call, inputs, pout), want[call]), where
+                else:
+                    _refused("not the transpose", where, _call, pin, call, inputs, pother)
+        assert _same(_call(pin, "topo", inputs, pout), want["topo"])           # p_out's verdict is the cached one now
+        handle = pout.handle
+        pout.destroy()
+        tries = []
+        for _ in range(8):
+            tries.append(_bool_plan(cin))
+            if tries[-1].handle == handle:
+                for call in PAIR_CALLS:
+                    _refused("not the transpose", "%s with a new plan under p_out's handle" % call, _call, pin, call, inputs, tries[-1])
+                break
+        else:
+            print("no new plan got the destroyed partner's handle in 8 tries: the uid half of the cache key was not exercised")
+
+
 def test_a_matrix_without_entries(gpu):
     """it keeps no row copy: the empty graph to everybody who asks for a square matrix -- each answers as its own suite's test of a
     plan without entries says --, refused by whoever indexes by row"""
@@ -241,13 +399,19 @@ def test_a_matrix_without_entries(gpu):
     e = _csr(n, [], [])
     level = np.zeros(n, np.float32)
     level[3] = 1.0
-    inputs = {"level": level, "weights": np.zeros(16, np.float32), "colors": np.zeros(n, np.uint32), "nnz": 16}
+    inputs = {"level": level, "weights": np.zeros(16, np.float32), "colors": np.zeros(n, np.uint32), "nnz": 16, **_more_inputs(e)}
     iota, untouched = np.arange(n, dtype=np.uint32), np.full(16, GARBAGE, np.uint32)
     want = {"rows_sorted": "row copy", "cc_labels": "row copy", "bfs_parents": "row copy", "tc_count": (0, np.zeros(n, np.uint64)),
             "kcore": np.zeros(n, np.uint32), "bc_accumulate": (np.zeros(n), level.astype(np.float64)),
             "color": np.zeros(n, np.uint32), "msf": (untouched, iota, (0, n)), "truss": (untouched, untouched, (0, 0, 0, 0, 0)),
             "match": (np.full(n, FREE, np.uint32), (0, 0, 0)), "lpa": (iota, (1, 0, 0, 1)), "louvain_move": (iota, (1, 0, 0, 1, 0, 0)),
             "scc": (iota, (n, 0, 0))}
+    # the eight newer callers: their host models on the empty graph, with the closed forms of their own suites
+    want.update({"bicc": _bicc_expected(e), "msbfs": _msbfs_expected(e), **_pair_expected(e, inputs), **_sets_expected(e, inputs, True)})
+    none = np.full(n, 0xffffffff, np.uint32)
+    assert want["bicc"][-1] == (0, 0, 0, 0, n) and _same(want["topo"], (np.zeros(n), np.zeros(n), none, iota, (n, 1, n)))
+    assert want["sssp_delta"][2] == 1 and want["sssp_delta"][0][SOURCE] == 0 and want["clique"][0] == 0 and want["contract"][5:] == ((n + 2) // 3, 0)
+    assert not want["similarity"][0].any() and want["spgemm"][3] == 0 and not want["msbfs"][0].any()
     assert sorted(want) == sorted(CALLS)
     for order in (CALLS, CALLS[::-1]):
         plan = capi.SpMVPlan(n, n, e.adj_indptr, e.adj_indices, e.adj_data, 0, n, flags=capi.GL_PLAN_BOOLEAN)

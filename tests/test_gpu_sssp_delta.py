@@ -2,7 +2,10 @@
 against a plain Dijkstra in f32 on the host (dijkstra_f32 below).  dist is the unique least fixed point of f32 relaxation, parent
 and the orphan count follow from it, so every comparison is exact, dist as 32-bit words -- under every delta, which only changes the
 schedule.  On the integer-weight cases the host reference is itself checked once against scipy's f64 Dijkstra (sums below 2^24 are
-exact in f32).  This kernel's contract and walk cases live here, as gl_tc's and gl_spgemm's do."""
+exact in f32).  The wording of this kernel's refusals is tested here (test_refusals); tests/test_gpu_rows.py calls it before and
+behind every other asker of the cached verdicts and of the transpose-partner cache, tests/test_gpu_rounds.py runs it before and
+behind the other users of rounds_run and of the staging words (sssp_delta_batch 1 and default), and
+tests/test_gpu_walk.py::test_sssp_delta runs its two walk sites on the star union at the cuts 0, 4, 8 and the default."""
 import functools
 import heapq
 import os

@@ -3,7 +3,10 @@ graphlily::app::TopologicalOrder) against the host model kept in tests/test_topo
 networkx and the closed forms).  level, dist, parent and the first three stats are functions of (graph, weights), so every
 comparison is exact, dist as 32-bit words.  Every test runs with the default dealing of the rows and with topo_cut=0, every output
 buffer starts as garbage with 64 guard words behind it, the weights are read only, and every case is called twice on one pair of
-plans.  This kernel's walk, contract and batch tests live here; the shared suites are a follow-up."""
+plans.  The wording of this kernel's refusals and its batch edges are tested here; the shared suites hold the rest:
+tests/test_gpu_rows.py calls it before and behind every other asker of the cached verdicts and of the transpose-partner cache,
+tests/test_gpu_rounds.py runs it on a 308-level DAG before and behind the other users of rounds_run (topo_batch 1 and default),
+and tests/test_gpu_walk.py::test_topo runs both of its walk sites on the star union at the cuts 0, 4, 8 and the default."""
 import os
 import subprocess
 

@@ -2,10 +2,16 @@
 rows_walk_wave, launched through rows_walk_shape): a thread per row, four entries per step for `cut` entries, then the wavefront
 takes the row over, 256 entries per step.  This file runs the skeleton's boundaries through every caller, so that a mistake in the
 header fails under the header's name:
-  all three templates   gl_cc_labels, gl_kcore, gl_color, gl_msf, gl_bfs_parents, gl_scc (over two plans) and gl_match, whose
-                        collect kernel keeps a copy of the thread steps of its own
+  all three templates   gl_cc_labels, gl_kcore, gl_color, gl_msf, gl_bfs_parents, gl_scc and gl_topo (over two plans each), and
+                        gl_match and gl_sssp_delta, whose collect and round kernels keep a copy of the thread steps of their own
+                        in which every lane takes every step (gl_sssp_delta's parent pull runs the templates themselves)
   takeover and wave     gl_lpa and gl_louvain_move, which count a row of at most 8 entries in registers instead of thread steps
   a copy of its own     gl_bc_accumulate, whose sweep walks the same way
+  elsewhere, on _stars()  gl_bicc: tests/test_gpu_bicc.py::test_walk_stars; gl_msbfs: tests/test_gpu_msbfs.py::
+                        test_walk_boundaries_on_the_star_union -- both at the cuts 0, 4, 8 and the default, both import this module,
+                        which therefore cannot import theirs; gl_contract, whose row sums use the takeover behind a path of
+                        their own for rows of at most 16 entries, and whose groups are streamed through 64-member windows:
+                        tests/test_gpu_contract.py::test_walk_stars_in_one_group, in that file's three modes
 The graph: a disjoint union of stars whose hub rows end on every side of a four-entry step, of the default cuts (8 and 32), of
 the wavefront (64) and of the 256-entry takeover step.  In every star the hub has the LOWEST number and the leaf a check cares
 about the HIGHEST, so that it is the last entry of the hub's row, in the row's last, partial group.  Each caller's cut runs over
@@ -14,8 +20,10 @@ app.py and the callers' host models.  gl_match and gl_scc deal a short list one 
 gl_lpa and gl_louvain_move deal a colour class: their tests set the knobs and choose the inputs so that BOTH deals run, and say
 in their docstrings why.  That the last entry of a hub row decides every one of their answers is proven without a GPU: the
 *_stars() inputs below are run through the host models again with that entry (and its mirror) removed, in
-tests/test_match_cpu.py, test_scc_cpu.py, test_lpa_cpu.py and test_louvain_cpu.py."""
+tests/test_match_cpu.py, test_scc_cpu.py, test_lpa_cpu.py, test_louvain_cpu.py, test_sssp_delta_cpu.py, test_topo_cpu.py and
+test_contract_cpu.py."""
 import functools
+import types
 
 import numpy as np
 import pytest
@@ -34,12 +42,15 @@ from test_gpu_lpa import _lpa
 from test_gpu_match import _match
 from test_gpu_msf import _msf
 from test_gpu_scc import _scc
+from test_gpu_sssp_delta import _call as _sssp_delta, bits, dijkstra_f32
+from test_gpu_topo import _topo
 from test_kcore_cpu import _csr
 from test_louvain_cpu import move_loop
 from test_lpa_cpu import propagate
 from test_match_cpu import FREE, greedy, mate_of_pairs, pairs_of, pointer_rounds
 from test_msf_cpu import graph_of, ones_of
 from test_scc_cpu import scc_model
+from test_topo_cpu import topo_model
 
 pytestmark = pytest.mark.gpu
 
@@ -291,6 +302,49 @@ def louvain_stars(packed=False, drop=None):
     return sym, weights, colors, heavy, first, full
 
 
+@functools.lru_cache(maxsize=None)
+def sssp_stars(sources, drop=None):
+    """whole weights 1 .. d, ascending inside each star (distinct there, the same in both entries of an edge), and the sources
+    "one": the highest leaf of the largest star; "every": the highest leaf of every star; "with_a_hub": those and the hub of the
+    star with 255 leaves
+    -> (the weighted symmetric matrix, the sources, dijkstra_f32()'s (dist, parent, orphans))"""
+    hub, leaf, kept = _star_edges(drop)
+    g = graph_of(N, hub[kept], leaf[kept], (leaf - hub)[kept])
+    last = _stars()[4]
+    src = {"one": last[-1:], "every": last, "with_a_hub": np.concatenate([last, star_hubs(255)[:1]])}[sources]
+    want = dijkstra_f32(g, src)
+    _frozen(want[0], want[1], g.adj_data, g.adj_indices, g.adj_indptr)
+    return g, [int(x) for x in src], want
+
+
+def sssp_delta_of(kind, g):
+    """tiny: below every weight, all entries heavy; default: the driver's rule; inf: one bucket, all entries light"""
+    return {"tiny": 0.5, "inf": np.inf}[kind] if kind != "default" else float(app.ShortestPaths.default_delta(types.SimpleNamespace(graph_=g, n_real_=N)))
+
+
+@functools.lru_cache(maxsize=None)
+def topo_stars(kind, heavy="last", packed=False, drop=None):
+    """kind "in":  every leaf -> its hub: the long rows are plan_in's, and the weights -- whole, 1 .. d inside a star -- put the
+                   heaviest edge on the hub's LAST in-entry (heavy "first": on its first).  packed: each of the 24 vertices
+                   without a neighbour gets one predecessor, a leaf of the largest star, so that level 1 has 41 members, not 17
+            "out": the hub -> every leaf: the long rows are plan_out's
+    `drop` removes the hub's last (first) entry of the long row, and its mirror in the other plan.
+    -> (csr_in, csr_out, the weights aligned with csr_in's entries, topo_model()'s (level, dist, parent, (peeled, levels, widest)))"""
+    hub, leaf, kept = _star_edges(drop)
+    place = leaf - hub
+    w = (place if heavy == "last" else _stars()[0].adj_indptr.astype(np.int64)[hub + 1] - _stars()[0].adj_indptr.astype(np.int64)[hub] + 1 - place)[kept]
+    src, dst = (leaf[kept], hub[kept]) if kind == "in" else (hub[kept], leaf[kept])
+    if packed:
+        spare = np.flatnonzero(_stars()[2] < 0)
+        assert kind == "in" and spare.shape[0] == 24
+        src, dst, w = np.concatenate([src, _stars()[3][-1] + 1 + np.arange(24)]), np.concatenate([dst, spare]), np.concatenate([w, np.ones(24, np.int64)])
+    cin, cout = _sorted_rows(_csr(N, dst, src)), _sorted_rows(_csr(N, src, dst))      # an entry A[v, u] is the edge u -> v
+    w_in = np.ascontiguousarray(w[np.lexsort((src, dst))], np.float32)
+    want = topo_model(N, src, dst, w)
+    _frozen(w_in, want[0], want[1], want[2], cin.adj_indices, cin.adj_indptr, cout.adj_indices, cout.adj_indptr)
+    return cin, cout, w_in, want
+
+
 # ------------------------------------------------------------------ ... and their tests
 MATCH_CUTS = [0, 4, 8, None, 64]
 SCC_DEALS = [(True, 0), (True, 4), (True, None), (True, 32), (False, None)]
@@ -435,3 +489,83 @@ def test_louvain_move(gpu, monkeypatch, cut, packed, table):
         got, stats = _move(plan, N, weights, None, colors, 20, 0)
         assert np.array_equal(got, full[0])
         assert stats[:3] + stats[4:] == tuple(full[1:])
+
+
+@pytest.mark.parametrize("delta", ["tiny", "default", "inf"])
+@pytest.mark.parametrize("sources", ["one", "every", "with_a_hub"])
+@pytest.mark.parametrize("cut", CUTS)
+def test_sssp_delta(gpu, monkeypatch, cut, sources, delta):
+    """The deal.  A round launch has rows_walk_shape's cdiv(2560, 256) = 10 workgroups (sssp_delta_grid counts workgroups per
+    compute unit and cannot make it fewer): 40 wavefronts, and sssp_round_kernel gives each ceil(listed / 40) vertices, 64 at
+    most; with ONE it drops its thread steps and the wavefront takes the whole row, whatever the cut.
+      one         round 1 lists the source, round 2 the hub of the largest star ALONE: the one-vertex-per-wavefront deal on a row
+                  of 545 entries; round 3 its 544 other leaves, 14 per wavefront, rows of one entry in the thread steps
+      every       the 17 hubs are listed together -- and that is still ceil(17 / 40) = 1 per wavefront: all 17 long rows go
+                  through the takeover-less hand-over, none through the round kernel's own copy of the thread steps
+      with_a_hub  the hub of the star with 255 leaves is a source too: round 1 lowers the 16 other hubs AND its 254 other leaves,
+                  round 2 lists these 270 together, 7 per wavefront, and the 16 hub rows -- every boundary length but 255 --
+                  run the thread steps for sssp_delta_cut entries and the takeover behind them.  That holds where the hubs and
+                  the leaves share a bucket and the entries are light: delta = inf and the default (above every distance here);
+                  with the tiny delta every entry is heavy, every epoch holds the few vertices of one distance, and the heavy
+                  pass walks their rows one per wavefront.
+    The parent pull (sssp_parent_kernel, the templates themselves) always deals 64 vertices per wavefront by number, a hub with
+    its leaves, under every cut.
+    The answer.  Every leaf's distance is its hub's plus the weight of ONE entry of the hub's row, all different inside a star;
+    the hub's parent is the only neighbour nearer than itself, the source: the LAST entry of its row, behind every early exit.
+    dist as bits, parent, reached and orphans equal dijkstra_f32, twice on one plan; tests/test_sssp_delta_cpu.py shows that the
+    answer changes at every star when the hub's last or first entry is lost."""
+    set_knob(monkeypatch, "sssp_delta_cut", cut)
+    g, src, (dist, parent, orphans) = sssp_stars(sources)
+    hub_of, last = _stars()[2], _stars()[4]
+    hubs = star_hubs(1) if sources != "one" else star_hubs(max(DEGREES))
+    leaves = np.flatnonzero((hub_of >= 0) & (hub_of != np.arange(N)) & np.isin(hub_of, hubs) & ~np.isin(np.arange(N), src))
+    reached = int(np.isfinite(dist).sum())
+    assert orphans == 0 and reached == (DEGREES[-1] + 1 if sources == "one" else 2536) and np.array_equal(parent[leaves], hub_of[leaves])
+    if sources != "with_a_hub":
+        assert np.array_equal(dist[hubs], np.asarray(DEGREES, np.float32)[-hubs.shape[0]:]) and np.array_equal(parent[hubs], last[-hubs.shape[0]:])
+        assert np.array_equal(dist[leaves], dist[hub_of[leaves]] + (leaves - hub_of[leaves]))
+    plan = _bool_plan(ones_of(g))
+    for _ in range(2):
+        got, par, stats = _sssp_delta(plan, None, g, g, src, sssp_delta_of(delta, g))
+        assert np.array_equal(got, bits(dist)), "dist: first difference at vertex %d" % int(np.flatnonzero(got != bits(dist))[0])
+        assert np.array_equal(par, parent), "parent: first difference at vertex %d" % int(np.flatnonzero(par != parent)[0])
+        assert stats[0] == reached and np.count_nonzero((got != 0x7f800000) & (par == NONE)) == orphans
+        assert delta != "inf" or stats[1] == 1
+
+
+@pytest.mark.parametrize("kind,heavy,packed", [("in", "last", False), ("in", "first", False), ("in", "last", True), ("in", "first", True),
+                                               ("out", "last", False)],
+                         ids=["in_last_row_per_wavefront", "in_first_row_per_wavefront", "in_last_two_rows_per_wavefront",
+                              "in_first_two_rows_per_wavefront", "out_two_rows_per_wavefront"])
+@pytest.mark.parametrize("cut", CUTS)
+def test_topo(gpu, monkeypatch, cut, kind, heavy, packed):
+    """The deal is gl_sssp_delta's: 40 wavefronts, ceil(slice / 40) queued vertices each, and with ONE no thread steps.
+      in   level 0 is the leaves and the vertices without a neighbour, 64 per wavefront, with empty rows of plan_in; level 1 is
+           the 17 hubs: a row per wavefront, the pull over the long rows is the wavefront's under every cut.  packed: 24 more
+           vertices are on level 1, 41 in all: two per wavefront, and the pull runs topo_cut entries in the thread steps.
+      out  level 0 is the 18 hubs and the 23 vertices behind the stars, 41: two per wavefront, and the PUSH over the long rows of
+           plan_out runs the thread steps and the takeover.
+    The answer.  in: the hub's dist is the weight of its heaviest in-edge and its parent that leaf -- its LAST entry (its FIRST in
+    the second variant); every candidate is different, so a lost entry shows.  out: a leaf is peeled only when its hub's
+    decrement walk reaches its entry: level 1 for every leaf, all N vertices peeled, nobody left as cyclic.  Equal to topo_model,
+    twice on one pair of plans; tests/test_topo_cpu.py shows that the answers change when one end of the long row is lost."""
+    set_knob(monkeypatch, "topo_cut", cut)
+    cin, cout, w, (level, dist, parent, stats) = topo_stars(kind, heavy, packed)
+    hub_of, hubs, last = _stars()[2], star_hubs(1), _stars()[4]
+    is_leaf = (hub_of >= 0) & (hub_of != np.arange(N))
+    spare = np.flatnonzero(hub_of < 0)
+    if kind == "in":
+        assert np.array_equal(level[hubs], np.ones(17)) and not level[is_leaf].any() and np.array_equal(level[spare], np.full(24, int(packed)))
+        assert np.array_equal(dist[hubs], np.asarray(DEGREES, np.float32)[1:]) and np.array_equal(parent[hubs], last if heavy == "last" else hubs + 1)
+        assert stats == (N, 2, N - 17 - 24 * packed)
+    else:
+        assert np.array_equal(level[is_leaf], np.ones(2519)) and not level[~is_leaf].any() and stats == (N, 2, 2519)
+    assert np.array_equal(np.diff((cin if kind == "in" else cout).adj_indptr.astype(np.int64))[hubs], DEGREES[1:])
+    pin, pout = _bool_plan(cin), _bool_plan(cout)
+    for _ in range(2):
+        got_level, order, got_dist, got_parent, got_stats = _topo(pin, pout, N, w)
+        assert np.array_equal(got_level, level), "level: first difference at vertex %d" % int(np.flatnonzero(got_level != level)[0])
+        assert np.array_equal(got_dist, bits(dist)), "dist: first difference at vertex %d" % int(np.flatnonzero(got_dist != bits(dist))[0])
+        assert np.array_equal(got_parent, parent), "parent: first difference at vertex %d" % int(np.flatnonzero(got_parent != parent)[0])
+        assert got_stats[:3] == stats and np.array_equal(np.sort(order), np.arange(N))      # all N peeled: nobody is cyclic
+        assert np.all(np.diff(level[order].astype(np.int64)) >= 0)

@@ -71,3 +71,23 @@ def test_library_exports_and_binds_the_entry_point():
     assert callable(app.ShortestPaths.run) and callable(app.ShortestPaths.path) and issubclass(app.TopologicalOrder, app._DirectedPairApp)
     if capi.device_count() == 0:
         assert L.gl_sssp_delta(None, None, None, None, None, 0, 1.0, None, None, None) == capi.GL_ERR_NOT_INITIALIZED
+
+
+def test_walk_stars_one_entry_of_every_hub_row_decides():
+    """the inputs of tests/test_gpu_walk.py::test_sssp_delta: without the last entry of every hub row and its mirror the sources
+    reach nobody; without the first, the first leaf is unreached -- so a push or a parent pull that loses one end of a long row
+    cannot return dijkstra_f32's answer.  (The star whose hub is a source itself keeps its hub; it loses its first leaf.)"""
+    from test_gpu_sssp_delta import bits
+    from test_gpu_walk import DEGREES, _stars, sssp_stars, star_hubs
+    for sources in ("one", "every", "with_a_hub"):
+        g, src, (dist, parent, orphans) = sssp_stars(sources)
+        hubs = star_hubs(max(DEGREES)) if sources == "one" else star_hubs(1)
+        hubs = hubs[~np.isin(hubs, src)]
+        last = hubs + np.diff(g.adj_indptr.astype(np.int64))[hubs]
+        assert np.array_equal(parent[hubs], last) and np.array_equal(dist[hubs], last - hubs) and orphans == 0
+        less = sssp_stars(sources, "last")[2]
+        assert np.all(np.isinf(less[0][hubs])) and np.all(less[1][hubs] == 0xFFFFFFFF)
+        less = sssp_stars(sources, "first")[2]
+        one_leaf = last == hubs + 1
+        assert np.all(np.isinf(less[0][hubs + 1][~one_leaf])) and np.all(np.isinf(less[0][hubs][one_leaf])) and np.isfinite(dist[hubs + 1]).all()
+        assert np.count_nonzero(bits(less[0]) != bits(dist)) >= hubs.shape[0]

@@ -526,3 +526,23 @@ def test_cpp_driver_compiles_and_fails_loudly_without_gpu(tmp_path):
         r = subprocess.run([TOPO_DRIVER, str(tmp_path / "none.npz"), str(tmp_path)], capture_output=True, text=True)
         assert r.returncode != 0
         assert "gl_init" in r.stdout + r.stderr       # print-and-exit convention of the reference
+
+
+def test_walk_stars_one_entry_of_every_hub_row_decides():
+    """the inputs of tests/test_gpu_walk.py::test_topo: without the heaviest entry of the hub's row of plan_in -- its last, or its
+    first -- and its mirror, dist and parent of every hub with a leaf change; without the last (first) entry of its row of
+    plan_out, that leaf has no predecessor and is on level 0, not 1 -- so a walk that loses one end of a long row cannot return
+    topo_model's answer"""
+    from test_gpu_walk import _stars, star_hubs, topo_stars
+    hubs, last = star_hubs(1), _stars()[4]
+    for packed in (False, True):
+        for heavy, gone in (("last", last), ("first", hubs + 1)):
+            level, dist, parent, stats = topo_stars("in", heavy, packed)[3]
+            assert np.array_equal(parent[hubs], gone) and stats[:2] == (2560, 2)
+            less = topo_stars("in", heavy, packed, heavy)[3]
+            assert np.all(bits(less[1])[hubs] != bits(dist)[hubs]) and np.all(less[2][hubs] != parent[hubs])
+            assert np.array_equal(less[1][hubs[1:]], dist[hubs[1:]] - 1) and less[0][hubs[0]] == 0      # (the star with one leaf: no predecessor left)
+    level, dist, parent, stats = topo_stars("out")[3]
+    for drop, gone in (("last", last), ("first", hubs + 1)):
+        less = topo_stars("out", "last", False, drop)[3]
+        assert np.array_equal(level[gone], np.ones(17)) and not less[0][gone].any() and less[3] == (2560, 2, 2519 - 17) != stats
