@@ -365,6 +365,61 @@ def validate_spgemm(a, b, c, semiring, mask=None, complement=False):
     return int(cp[n])
 
 
+def validate_spmm(csr, X, Y, semiring, mask=None, mask_type=M.kNoMask, rows=None):
+    """Host-side check that the (num_rows, k) block `Y` is A (+).(x) X as include/graphlily_hip_spmm.h defines it, in numpy f64
+    and no other code of the library.  `csr` is A (any shape; every stored entry counts, a zero value included, an entry stored
+    twice counts twice), `X` an (num_cols, k) block, `semiring` a SemiringType; `mask` an (num_rows, k) block read per element as
+    SpMVModule reads its mask per row; `rows` = (row_begin, row_end) checks those rows only.  An element the mask switches off
+    must be the literal 0.  Of the others: (||,&&) exactly 1.0 where an entry of the row meets an X != 0, else the semiring's
+    zero; (min,+) equal as a number to min(zero, min of the f32 sums a + x); (+,x) within 2^-24 |ref| + p 2^-52 sum|a x| +
+    2^-149 of ref = zero + the f64 sum of the p exact products -- one f32 rounding on top of an f64 sum in any order (p counts
+    a non-zero `zero` as one more term).  Raises ValueError naming the first offending element; returns the elements checked."""
+    op, zero = semiring.op, np.float32(semiring.zero)
+    n = int(csr.num_rows)
+    X, Y = np.asarray(X, np.float32), np.asarray(Y, np.float32)
+    if X.ndim != 2 or X.shape[0] != csr.num_cols or Y.shape != (n, X.shape[1]):
+        raise ValueError("validate_spmm: X is %s and Y %s for a %d x %d matrix" % (X.shape, Y.shape, n, csr.num_cols))
+    k = X.shape[1]
+    indptr = np.asarray(csr.adj_indptr).astype(np.int64)[:n + 1]
+    lens = np.diff(indptr)
+    nnz = int(indptr[n])
+    cols, a = np.asarray(csr.adj_indices[:nnz]).astype(np.int64), np.asarray(csr.adj_data[:nnz], np.float32)
+    full, starts = np.flatnonzero(lens), indptr[:-1][lens > 0]
+    bound = np.zeros((n, k))
+    with np.errstate(all="ignore"):
+        if op == M.kMulAdd:
+            prod = a.astype(np.float64)[:, None] * X[cols].astype(np.float64)
+            ref, abs_sum = np.full((n, k), float(zero)), np.full((n, k), abs(float(zero)))
+            if nnz:
+                ref[full] += np.add.reduceat(prod, starts, axis=0)
+                abs_sum[full] += np.add.reduceat(np.abs(prod), starts, axis=0)
+            bound = 2.0 ** -24 * np.abs(ref) + (lens + (zero != 0))[:, None] * 2.0 ** -52 * abs_sum + 2.0 ** -149
+        elif op == M.kAddMin:
+            ref = np.full((n, k), zero, np.float32)
+            if nnz:
+                ref[full] = np.minimum(ref[full], np.minimum.reduceat(a[:, None] + X[cols], starts, axis=0))
+        else:
+            hit = np.zeros((n, k), bool)
+            if nnz:
+                hit[full] = np.logical_or.reduceat(X[cols] != 0, starts, axis=0)
+            ref = np.where(hit, np.float32(1.0), zero)
+        keep = np.ones((n, k), bool)
+        if mask_type != M.kNoMask:
+            is_zero = np.asarray(mask, np.float32).reshape(n, k) == 0
+            keep = is_zero if mask_type == M.kMaskWriteToZero else ~is_zero
+        got = Y.astype(np.float64)
+        bad = np.where(keep, ~(np.abs(got - ref) <= bound) & ~((got == ref) & np.isinf(ref)), ~(got == 0))
+    r0, r1 = (0, n) if rows is None else rows
+    bad[:r0], bad[r1:] = False, False
+    if bad.any():
+        r, c = (int(v[0]) for v in np.nonzero(bad))
+        if not keep[r, c]:
+            raise ValueError("validate_spmm: Y[%d, %d] is %r where the mask switches it off: must be the literal 0" % (r, c, float(Y[r, c])))
+        raise ValueError("validate_spmm: Y[%d, %d] is %r, the %d entries of the row give %r (bound %r)" %
+                         (r, c, float(Y[r, c]), int(lens[r]), float(ref[r, c]), float(bound[r, c])))
+    return (r1 - r0) * k
+
+
 def _quotient_of(graph, labels, weights, vertex_weights):
     """The DIRECTED statement of the quotient, by np.unique on keys -> io.aggregate_communities' tuple.  `graph`: a simple
     pattern without diagonal (io.simple_pattern's csr_in); an entry (v, u) gives (part[v], part[u])."""

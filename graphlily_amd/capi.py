@@ -63,7 +63,8 @@ EXT_HEADERS = {"graphlily_hip_ext.h": EXT_EXPORTS, "graphlily_hip_truss.h": ["gl
                "graphlily_hip_sim.h": ["gl_similarity"], "graphlily_hip_clique.h": ["gl_clique_count"],
                "graphlily_hip_spgemm.h": ["gl_spgemm_numeric", "gl_spgemm_symbolic"],
                "graphlily_hip_contract.h": ["gl_contract_numeric", "gl_contract_symbolic"],
-               "graphlily_hip_sssp_delta.h": ["gl_sssp_delta"]}
+               "graphlily_hip_sssp_delta.h": ["gl_sssp_delta"],
+               "graphlily_hip_spmm.h": ["gl_spmm"]}
 
 
 class GraphLilyError(RuntimeError):
@@ -144,6 +145,7 @@ def lib():
         "gl_clique_count": [vp, u32, vp, vp, P(u64)],
         "gl_spgemm_symbolic": [vp, vp, vp, u32, vp, P(u64)],
         "gl_spgemm_numeric": [vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, P(u64)],
+        "gl_spmm": [vp, vp, vp, u64, vp, u64, vp, u64, u32, i32, f32, i32, P(u64)],
         "gl_louvain_move": [vp, vp, vp, vp, vp, u32, u64, P(u64)],
         "gl_contract_symbolic": [vp, u32, vp, vp, vp, P(u64)],
         "gl_contract_numeric": [vp, u32, vp, u32, vp, vp, vp, vp, vp, vp, P(u64)],
@@ -519,6 +521,19 @@ class SpMVPlan:
                                       ctypes.c_uint32(GL_SPGEMM_MASK_COMPLEMENT if complement else 0), ctypes.c_uint32(semiring),
                                       _p(a_val), _p(b_val), _p(c_indptr), _p(c_indices), _p(c_val), out))
         return tuple(int(x) for x in out) if stats else None
+
+    def spmm(self, a_val, x, y, k, op, zero, mask=None, mask_type=GL_NOMASK, ldx=None, ldy=None, ldm=None, stats=False):
+        """gl_spmm: y[r, c] = mask(r, c) ? (zero (+) sum over the entries (r, j) of this plan's rows of a_val (x) x[j, c]) : 0 for
+        the plan's rows and c < k.  `x` is num_cols x k floats, row-major with the leading dimension ldx (None: k), `y` and `mask`
+        num_rows x k with ldy / ldm; `a_val`: an f32 per entry of the plan's row copy (None under GL_OP_ANDOR).  The plan is a
+        GL_PLAN_BOOLEAN plan, may be rectangular and a row shard.  Enqueued (the plan's first call waits once), unless stats=True
+        -> (rows on the short path, rows on the wavefront path, rows on the workgroup path, column tiles)."""
+        out = (ctypes.c_uint64 * 4)(*([0xdeadbeefdeadbeef] * 4)) if stats else None
+        k = int(k)
+        check(lib().gl_spmm(ctypes.c_void_p(self.handle), _p(a_val), _p(x), ctypes.c_uint64(k if ldx is None else ldx), _p(mask),
+                            ctypes.c_uint64(k if ldm is None else ldm), _p(y), ctypes.c_uint64(k if ldy is None else ldy), ctypes.c_uint32(k),
+                            int(op), float(zero), int(mask_type), out))
+        return tuple(int(v) for v in out) if stats else None
 
     def contract_symbolic(self, num_vertices, label, part, c_indptr):
         """gl_contract_symbolic: the quotient of this plan's graph by `label` (num_vertices device words, each a vertex number

@@ -316,6 +316,13 @@ struct gl_spmv_plan_s {
     // path, and what the host keeps of the last symbolic call for the numeric call behind it: k, num_vertices, its bins, the knobs it read
     unsigned char *d_contract_scratch = nullptr, *d_contract_slab = nullptr;
     uint32_t contract_k = 0xffffffffu, contract_nv = 0, contract_bins[3] = {0, 0, 0}, contract_slabs = 0, contract_wave_slots = 0, contract_lds_slots = 0;
+    // gl_spmm (gl_spmm.hip), set up by the first call: the scratch -- 256 bytes of control words (the three counts), then three
+    // lists of row_end - row_begin words: the local numbers of the short, the wavefront and the workgroup rows -- and what the host
+    // keeps: the knobs that call read (the two cuts the lists are keyed by, -1 = the path is closed; the load width) and the lists' sizes
+    unsigned char *d_spmm_scratch = nullptr;
+    long spmm_cut = 0, spmm_wg = 0;
+    bool spmm_vec = true;
+    uint32_t spmm_rows[3] = {0, 0, 0};
     // gl_bc_accumulate (gl_bc.hip), as plan_in, set up by the first call: the pass's scratch -- 256 bytes of control words, two
     // arrays of num_rows + 2 level offsets, num_rows words of queue, num_rows doubles each of sigma and coef -- the page-locked
     // room the offsets are read back to, and the verdict on the last plan_out that was not this plan itself: is it the

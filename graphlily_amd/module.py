@@ -665,6 +665,118 @@ class SpGEMMModule(BaseModule):
                             self.c_indptr_buf.read(np.uint32, n + 1))
 
 
+class SpMMModule(BaseModule):
+    """Extension (gl_spmm): Y = A (+).(x) X for a dense block X of k vectors, under the three semirings, with an
+    optional dense mask of Y's shape -- one pass over A where k SpMVModule runs make k.  The interface mirrors SpMVModule's; X is
+    an (num_cols, k) array, Y and the mask are (num_rows, k), all row-major.  A may be rectangular and a row shard.  The plan is a
+    boolean plan of all-ones values -- a zero VALUE is a value here, and the row copy would store it as no entry -- and the
+    values travel in a buffer of their own, in the matrix' order."""
+
+    def __init__(self):
+        super().__init__()
+        self.semiring_ = ArithmeticSemiring
+        self.mask_type_ = kNoMask
+        self.csr_matrix_ = None
+        self.plan_ = None
+        self.row_begin_, self.row_end_ = 0, None
+        self.k_ = 0
+        self.ldx_ = self.ldy_ = self.ldm_ = None               # leading dimensions of bound buffers (None: k)
+        self.vectors_nan_ = self.vectors_inf_ = False          # of the X that send_vectors_host_to_device saw
+        self.a_val_buf = self.vectors_buf = self.mask_buf = self.results_buf = None
+        self.stats_ = None
+
+    def set_semiring(self, semiring):
+        self.semiring_ = semiring
+
+    def set_mask_type(self, mask_type):
+        assert mask_type in (kNoMask, kMaskWriteToZero, kMaskWriteToOne)
+        self.mask_type_ = mask_type
+
+    def set_row_shard(self, row_begin, row_end):
+        """this device owns rows [row_begin, row_end) of the matrix: only those rows of Y are written"""
+        self.row_begin_, self.row_end_ = int(row_begin), int(row_end)
+
+    def get_num_rows(self):
+        return self.csr_matrix_.num_rows
+
+    def get_num_cols(self):
+        return self.csr_matrix_.num_cols
+
+    def get_num_vectors(self):
+        return self.k_
+
+    def load_and_format_matrix(self, csr_matrix_float):
+        self.csr_matrix_ = csr_matrix_float
+
+    def send_matrix_host_to_device(self):
+        m = self.csr_matrix_
+        r0, r1 = self.row_begin_, m.num_rows if self.row_end_ is None else self.row_end_
+        indptr = np.asarray(m.adj_indptr).astype(np.int64)
+        nnz = int(indptr[m.num_rows])
+        self.plan_ = capi.SpMVPlan(m.num_rows, m.num_cols, m.adj_indptr, m.adj_indices, np.ones(nnz, dtype=np.float32), r0, r1,
+                                   capi.GL_PLAN_BOOLEAN | capi.GL_PLAN_NO_MULADD)
+        self.values_ = np.ascontiguousarray(m.adj_data[int(indptr[r0]):int(indptr[r1])], dtype=np.float32)   # the shard's entries
+        self.a_val_buf = capi.DeviceBuffer.from_host(self.values_ if self.values_.shape[0] else np.zeros(1, np.float32))
+        self._finish(self.a_val_buf)
+
+    def send_vectors_host_to_device(self, vectors):
+        """X: an (num_cols, k) array; k is taken from it.  Allocates the results buffer for that k (zero-filled) unless one of that
+        size is there."""
+        x = np.ascontiguousarray(vectors, dtype=np.float32)
+        if x.ndim != 2 or x.shape[0] != self.get_num_cols() or x.shape[1] == 0:
+            raise ValueError("SpMMModule.send_vectors_host_to_device: X must be (%d, k >= 1), got %s" % (self.get_num_cols(), x.shape))
+        self.k_, self.ldx_ = int(x.shape[1]), None
+        self.vectors_nan_, self.vectors_inf_ = bool(np.isnan(x).any()), bool(np.isinf(x).any())
+        self.vectors_buf = capi.DeviceBuffer.from_host(x)
+        if self.results_buf is None or self.ldy_ is not None or self.results_buf.nbytes != 4 * self.get_num_rows() * self.k_:
+            self.results_buf, self.ldy_ = capi.DeviceBuffer(4 * max(1, self.get_num_rows() * self.k_)), None
+            capi.fill_f32(self.results_buf, 0.0, self.get_num_rows() * self.k_)
+        self._finish(self.vectors_buf, self.results_buf)
+
+    def send_mask_host_to_device(self, mask):
+        """M: an (num_rows, k) array"""
+        m = np.ascontiguousarray(mask, dtype=np.float32)
+        if m.shape != (self.get_num_rows(), self.k_):
+            raise ValueError("SpMMModule.send_mask_host_to_device: the mask must be %s, got %s" % ((self.get_num_rows(), self.k_), m.shape))
+        self.mask_buf, self.ldm_ = capi.DeviceBuffer.from_host(m if m.size else np.zeros(1, np.float32)), None
+        self._finish(self.mask_buf)
+
+    def bind_vectors_buf(self, src_buf, k, ld=None):
+        """a device block of num_cols x k floats with the leading dimension `ld` (None: k); its contents are the caller's business"""
+        self.vectors_buf, self.k_, self.ldx_ = src_buf, int(k), ld
+        self.vectors_nan_ = self.vectors_inf_ = False
+
+    def bind_mask_buf(self, src_buf, ld=None):
+        self.mask_buf, self.ldm_ = src_buf, ld
+
+    def bind_results_buf(self, src_buf, ld=None):
+        self.results_buf, self.ldy_ = src_buf, ld
+
+    def run(self):
+        """Leaves stats_ = (rows on the short path, rows on the wavefront path, rows on the workgroup path, column tiles).  NaN
+        values are refused under every semiring, +-inf under (+,x) (ValueError): of A, and of an X this module uploaded."""
+        if self.plan_ is None or self.vectors_buf is None:
+            _fatal("SpMMModule.run: send_matrix_host_to_device and send_vectors_host_to_device first")
+        op = self.semiring_.op
+        if op != kLogicalAndOr and (np.isnan(self.values_).any() or self.vectors_nan_ or
+                                    (op == kMulAdd and (np.isinf(self.values_).any() or self.vectors_inf_))):
+            raise ValueError("SpMMModule.run: A or X holds a NaN%s value" % (" or an infinite" if op == kMulAdd else ""))
+        mask = self.mask_buf if self.mask_type_ != kNoMask else None
+        if self.mask_type_ != kNoMask and mask is None:
+            _fatal("SpMMModule.run: a mask type without a mask")
+        self.stats_ = self.plan_.spmm(None if op == kLogicalAndOr else self.a_val_buf, self.vectors_buf, self.results_buf, self.k_, op,
+                                      self.semiring_.zero, mask, self.mask_type_, self.ldx_, self.ldy_, self.ldm_, stats=True)
+        self._finish(self.results_buf)
+
+    def send_results_device_to_host(self):
+        """-> an (num_rows, k) array (of a bound buffer with a leading dimension: its k columns)"""
+        n, ld = self.get_num_rows(), self.k_ if self.ldy_ is None else self.ldy_
+        if n == 0:
+            return np.zeros((0, self.k_), np.float32)
+        flat = self.results_buf.read(np.float32, (n - 1) * ld + self.k_)
+        return np.ascontiguousarray(np.lib.stride_tricks.as_strided(flat, (n, self.k_), (4 * ld, 4)))
+
+
 class SpMSpVModule(BaseModule):
     def __init__(self, out_buf_len=0):
         super().__init__()
