@@ -420,6 +420,57 @@ def validate_spmm(csr, X, Y, semiring, mask=None, mask_type=M.kNoMask, rows=None
     return (r1 - r0) * k
 
 
+def validate_sddmm(csr, X, Y, out, semiring, scaled=True, rows=None):
+    """Host-side check that `out` holds the scores of A's entries as include/graphlily_hip_sddmm.h defines them, in numpy f64 and
+    no other code of the library.  `csr` is A (any shape; every stored entry has a score, an entry stored twice has two), `X` an
+    (num_rows, k) block, `Y` an (num_cols, k) block, `semiring` a SemiringType; `scaled` False leaves A's values out; `rows` =
+    (row_begin, row_end) checks those rows, and `out` then holds their entries only, in A's order.  An entry whose column is
+    0xffffffff (or not below num_cols) must be the literal 0.  Of the others: (||,&&) exactly 1.0 where some feature has X != 0
+    and Y != 0, else the semiring's zero; (min,+) equal as a number to a + min(zero, min of the f32 sums x + y); (+,x) within
+    2^-24 |ref| + (k + 1) 2^-52 |a| sum|x y| + 2^-149 of ref = a (zero + the f64 sum of the k exact products) -- one f32
+    rounding on top of k - 1 f64 additions in any order, the addition of `zero` (k + 2 when it is non-zero, and |zero| then counts
+    as one more term of the sum) and the scaling.
+    Raises ValueError naming the first offending entry; returns the number of entries checked."""
+    op, zero = semiring.op, np.float32(semiring.zero)
+    n = int(csr.num_rows)
+    X, Y, out = np.asarray(X, np.float32), np.asarray(Y, np.float32), np.asarray(out, np.float32)
+    if X.ndim != 2 or Y.ndim != 2 or X.shape[0] != n or Y.shape[0] != csr.num_cols or X.shape[1] != Y.shape[1]:
+        raise ValueError("validate_sddmm: X is %s and Y %s for a %d x %d matrix" % (X.shape, Y.shape, n, csr.num_cols))
+    k = X.shape[1]
+    indptr = np.asarray(csr.adj_indptr).astype(np.int64)[:n + 1]
+    r0, r1 = (0, n) if rows is None else rows
+    first, count = int(indptr[r0]), int(indptr[r1] - indptr[r0])
+    if out.shape != (count,):
+        raise ValueError("validate_sddmm: out is %s for the %d entries of rows [%d, %d)" % (out.shape, count, r0, r1))
+    cols = np.asarray(csr.adj_indices[first:first + count]).astype(np.int64)
+    row_of = np.repeat(np.arange(r0, r1), np.diff(indptr[r0:r1 + 1]))
+    a = np.asarray(csr.adj_data[first:first + count], np.float32) if scaled and op != M.kLogicalAndOr else None
+    marker = cols >= csr.num_cols
+    x, y = X[row_of], Y[np.where(marker, 0, cols)] if csr.num_cols else np.zeros((count, k), np.float32)
+    bound = np.zeros(count)
+    with np.errstate(all="ignore"):
+        if op == M.kMulAdd:
+            prod = x.astype(np.float64) * y.astype(np.float64)
+            scale = np.ones(count) if a is None else a.astype(np.float64)
+            ref = scale * (float(zero) + prod.sum(axis=1))
+            bound = 2.0 ** -24 * np.abs(ref) + (k + 1 + (zero != 0)) * 2.0 ** -52 * np.abs(scale) * (abs(float(zero)) + np.abs(prod).sum(axis=1)) + 2.0 ** -149
+        elif op == M.kAddMin:
+            ref = np.minimum(zero, (x + y).min(axis=1)).astype(np.float32)
+            if a is not None:
+                ref = a + ref
+        else:
+            ref = np.where(((x != 0) & (y != 0)).any(axis=1), np.float32(1.0), zero)
+        got = out.astype(np.float64)
+        bad = np.where(marker, ~(got == 0), ~(np.abs(got - ref) <= bound) & ~((got == ref) & np.isinf(ref)))
+    if bad.any():
+        e = int(np.flatnonzero(bad)[0])
+        if marker[e]:
+            raise ValueError("validate_sddmm: out[%d] (row %d) is %r where the entry's column is a marker: must be the literal 0" % (e, row_of[e], float(out[e])))
+        raise ValueError("validate_sddmm: out[%d] = C[%d, %d] is %r, the %d features give %r (bound %r)" %
+                         (e, row_of[e], cols[e], float(out[e]), k, float(ref[e]), float(bound[e])))
+    return count
+
+
 def _quotient_of(graph, labels, weights, vertex_weights):
     """The DIRECTED statement of the quotient, by np.unique on keys -> io.aggregate_communities' tuple.  `graph`: a simple
     pattern without diagonal (io.simple_pattern's csr_in); an entry (v, u) gives (part[v], part[u])."""

@@ -64,7 +64,8 @@ EXT_HEADERS = {"graphlily_hip_ext.h": EXT_EXPORTS, "graphlily_hip_truss.h": ["gl
                "graphlily_hip_spgemm.h": ["gl_spgemm_numeric", "gl_spgemm_symbolic"],
                "graphlily_hip_contract.h": ["gl_contract_numeric", "gl_contract_symbolic"],
                "graphlily_hip_sssp_delta.h": ["gl_sssp_delta"],
-               "graphlily_hip_spmm.h": ["gl_spmm"]}
+               "graphlily_hip_spmm.h": ["gl_spmm"],
+               "graphlily_hip_sddmm.h": ["gl_sddmm"]}
 
 
 class GraphLilyError(RuntimeError):
@@ -146,6 +147,7 @@ def lib():
         "gl_spgemm_symbolic": [vp, vp, vp, u32, vp, P(u64)],
         "gl_spgemm_numeric": [vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, P(u64)],
         "gl_spmm": [vp, vp, vp, u64, vp, u64, vp, u64, u32, i32, f32, i32, P(u64)],
+        "gl_sddmm": [vp, vp, vp, u64, vp, u64, vp, u32, i32, f32, P(u64)],
         "gl_louvain_move": [vp, vp, vp, vp, vp, u32, u64, P(u64)],
         "gl_contract_symbolic": [vp, u32, vp, vp, vp, P(u64)],
         "gl_contract_numeric": [vp, u32, vp, u32, vp, vp, vp, vp, vp, vp, P(u64)],
@@ -534,6 +536,18 @@ class SpMVPlan:
                             ctypes.c_uint64(k if ldm is None else ldm), _p(y), ctypes.c_uint64(k if ldy is None else ldy), ctypes.c_uint32(k),
                             int(op), float(zero), int(mask_type), out))
         return tuple(int(v) for v in out) if stats else None
+
+    def sddmm(self, a_val, x, y, out, k, op, zero, ldx=None, ldy=None, stats=False):
+        """gl_sddmm: out[e] = a_val[e] (x) (zero (+) sum over c < k of x[r, c] (x) y[j, c]) for every entry e = (r, j) of this
+        plan's rows, in the row copy's order.  `x` is num_rows x k floats, row-major with the leading dimension ldx (None: k), `y`
+        num_cols x k with ldy; `out` and `a_val` (None: no scaling) hold an f32 per entry of the plan's row copy -- what spmm takes
+        as its a_val.  The plan is a GL_PLAN_BOOLEAN plan, may be rectangular and a row shard.  Enqueued (the plan's first call
+        waits once), unless stats=True -> (rows on the short path, pieces on the piece path, feature tiles)."""
+        res = (ctypes.c_uint64 * 3)(*([0xdeadbeefdeadbeef] * 3)) if stats else None
+        k = int(k)
+        check(lib().gl_sddmm(ctypes.c_void_p(self.handle), _p(a_val), _p(x), ctypes.c_uint64(k if ldx is None else ldx), _p(y),
+                             ctypes.c_uint64(k if ldy is None else ldy), _p(out), ctypes.c_uint32(k), int(op), float(zero), res))
+        return tuple(int(v) for v in res) if stats else None
 
     def contract_symbolic(self, num_vertices, label, part, c_indptr):
         """gl_contract_symbolic: the quotient of this plan's graph by `label` (num_vertices device words, each a vertex number

@@ -1,11 +1,13 @@
 // The plain CSR row copy that a GL_PLAN_BOOLEAN plan keeps (gl_spmv_plan.h: d_csr_indptr / d_csr_indices / csr_nz_base), as the
 // graph kernels that walk it see it -- gl_bfs_parents, gl_cc, gl_tc, gl_kcore, gl_color, gl_truss, gl_bc, gl_scc, gl_bicc, gl_topo,
-// gl_msbfs, gl_sim, gl_clique, gl_contract, gl_lpa, and gl_msf, gl_match, gl_louvain, gl_spgemm, gl_sssp_delta and gl_spmm (which also
+// gl_msbfs, gl_sim, gl_clique, gl_contract, gl_lpa, and gl_msf, gl_match, gl_louvain, gl_spgemm, gl_sssp_delta, gl_spmm and gl_sddmm (which also
 // take a value per entry of the copy from their caller): what a caller may require of it, the verdicts about it that the plan caches, the
 // few helpers every such kernel wants, and the walk over a row -- a thread per row, then the wavefront -- that eleven of them run
 // and gl_bc copies (rows_walk_*, at the end; gl_tc, gl_truss, gl_sim and gl_clique intersect rows instead, gl_spgemm forms product
 // rows, gl_contract streams a group's member rows and uses the takeover for its row sums, gl_spmm walks a row with a group, a
-// wavefront or a workgroup over four columns of a dense block per lane).  gl_rows.hip holds the check kernels.
+// wavefront or a workgroup over four columns of a dense block per lane, gl_sddmm scores a short row with a group and a longer one
+// in pieces, a wavefront each; its shared-state cases live in its own test file, tests/test_gpu_sddmm.py).  gl_rows.hip holds the
+// check kernels.
 // A new caller adds itself to tests/test_gpu_rows.py (the contract: every caller above is called there before and behind every
 // other on one plan; the wording of its refusals stays in its own test file), to tests/test_gpu_walk.py (the walk: there, or in
 // a star test of its own that the file's header names) and, when it runs rounds_run or reads the staging words, to

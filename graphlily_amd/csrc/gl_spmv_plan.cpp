@@ -892,6 +892,7 @@ int gl_spmv_plan_destroy(gl_spmv_plan p) {
     (void)hipFree(p->d_spgemm_scratch);
     (void)hipFree(p->d_spgemm_slab);
     (void)hipFree(p->d_spmm_scratch);
+    (void)hipFree(p->d_sddmm_scratch);
     (void)hipFree(p->d_contract_scratch);
     (void)hipFree(p->d_contract_slab);
     (void)hipFree(p->d_bc_scratch);

@@ -323,6 +323,13 @@ struct gl_spmv_plan_s {
     long spmm_cut = 0, spmm_wg = 0;
     bool spmm_vec = true;
     uint32_t spmm_rows[3] = {0, 0, 0};
+    // gl_sddmm (gl_sddmm.hip), set up by the first call and again by a call that reads other knobs: the scratch -- 256 bytes of
+    // control words (the two counts), the short list of row_end - row_begin local row numbers, then the piece list of {local row,
+    // piece} pairs -- and what the host keeps: the two knobs the lists are keyed by (the cut, -1 = the short path is closed; the
+    // entries of a piece) and the lists' sizes
+    unsigned char *d_sddmm_scratch = nullptr;
+    long sddmm_cut = 0, sddmm_piece = 0;
+    uint32_t sddmm_items[2] = {0, 0};
     // gl_bc_accumulate (gl_bc.hip), as plan_in, set up by the first call: the pass's scratch -- 256 bytes of control words, two
     // arrays of num_rows + 2 level offsets, num_rows words of queue, num_rows doubles each of sigma and coef -- the page-locked
     // room the offsets are read back to, and the verdict on the last plan_out that was not this plan itself: is it the

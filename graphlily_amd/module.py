@@ -777,6 +777,114 @@ class SpMMModule(BaseModule):
         return np.ascontiguousarray(np.lib.stride_tricks.as_strided(flat, (n, self.k_), (4 * ld, 4)))
 
 
+class SDDMMModule(BaseModule):
+    """Extension (gl_sddmm): C = A (x) (X (+).(x) Y^T) sampled at A's entries -- one score per stored entry of A from
+    the k features of its row (X, (num_rows, k)) and of its column (Y, (num_cols, k)), under the three semirings; the edge half of
+    a message-passing layer, of which SpMMModule is the aggregating half.  The interface mirrors SpMMModule's.  A may be
+    rectangular and a row shard.  results_buf is the plain per-entry buffer (an f32 per entry of the shard's rows, in the matrix'
+    order): it can be handed to SpMMModule as its a_val_buf as it is."""
+
+    def __init__(self):
+        super().__init__()
+        self.semiring_ = ArithmeticSemiring
+        self.scaled_ = True
+        self.csr_matrix_ = None
+        self.plan_ = None
+        self.row_begin_, self.row_end_ = 0, None
+        self.k_ = 0
+        self.ldx_ = self.ldy_ = None                           # leading dimensions of bound buffers (None: k)
+        self.features_nan_ = self.features_inf_ = False        # of the X and Y that send_features_host_to_device saw
+        self.a_val_buf = self.x_buf = self.y_buf = self.results_buf = None
+        self.stats_ = None
+
+    def set_semiring(self, semiring):
+        self.semiring_ = semiring
+
+    def set_scaled(self, scaled):
+        """True (the default): the scores are scaled by A's values; False: the bracket itself, A gives the pattern only"""
+        self.scaled_ = bool(scaled)
+
+    def set_row_shard(self, row_begin, row_end):
+        """this device owns rows [row_begin, row_end) of the matrix: only those rows' entries are scored"""
+        self.row_begin_, self.row_end_ = int(row_begin), int(row_end)
+
+    def get_num_rows(self):
+        return self.csr_matrix_.num_rows
+
+    def get_num_cols(self):
+        return self.csr_matrix_.num_cols
+
+    def get_num_features(self):
+        return self.k_
+
+    def load_and_format_matrix(self, csr_matrix_float):
+        self.csr_matrix_ = csr_matrix_float
+
+    def send_matrix_host_to_device(self):
+        """Allocates the results buffer, an f32 per entry of the shard's rows (zero-filled)"""
+        m = self.csr_matrix_
+        r0, r1 = self.row_begin_, m.num_rows if self.row_end_ is None else self.row_end_
+        indptr = np.asarray(m.adj_indptr).astype(np.int64)
+        nnz = int(indptr[m.num_rows])
+        self.plan_ = capi.SpMVPlan(m.num_rows, m.num_cols, m.adj_indptr, m.adj_indices, np.ones(nnz, dtype=np.float32), r0, r1,
+                                   capi.GL_PLAN_BOOLEAN | capi.GL_PLAN_NO_MULADD)
+        self.first_, self.count_ = int(indptr[r0]), int(indptr[r1] - indptr[r0])
+        self.values_ = np.ascontiguousarray(m.adj_data[self.first_:self.first_ + self.count_], dtype=np.float32)   # the shard's entries
+        self.a_val_buf = capi.DeviceBuffer.from_host(self.values_ if self.count_ else np.zeros(1, np.float32))
+        self.results_buf = capi.DeviceBuffer(4 * max(1, self.count_))
+        if self.count_:
+            capi.fill_f32(self.results_buf, 0.0, self.count_)
+        self._finish(self.a_val_buf, self.results_buf)
+
+    def send_features_host_to_device(self, X, Y):
+        """X: an (num_rows, k) array, Y: an (num_cols, k) array; k is taken from them"""
+        x, y = np.ascontiguousarray(X, dtype=np.float32), np.ascontiguousarray(Y, dtype=np.float32)
+        if x.ndim != 2 or y.ndim != 2 or x.shape[0] != self.get_num_rows() or y.shape[0] != self.get_num_cols() or x.shape[1] != y.shape[1] or x.shape[1] == 0:
+            raise ValueError("SDDMMModule.send_features_host_to_device: X must be (%d, k) and Y (%d, k), k >= 1, got %s and %s" %
+                             (self.get_num_rows(), self.get_num_cols(), x.shape, y.shape))
+        self.k_, self.ldx_, self.ldy_ = int(x.shape[1]), None, None
+        self.features_nan_ = bool(np.isnan(x).any() or np.isnan(y).any())
+        self.features_inf_ = bool(np.isinf(x).any() or np.isinf(y).any())
+        self.x_buf = capi.DeviceBuffer.from_host(x if x.size else np.zeros(1, np.float32))
+        self.y_buf = capi.DeviceBuffer.from_host(y if y.size else np.zeros(1, np.float32))
+        self._finish(self.x_buf, self.y_buf)
+
+    def bind_features_bufs(self, x_buf, y_buf, k, ldx=None, ldy=None):
+        """device blocks of num_rows x k and num_cols x k floats with the leading dimensions ldx, ldy (None: k); their contents
+        are the caller's business"""
+        self.x_buf, self.y_buf, self.k_, self.ldx_, self.ldy_ = x_buf, y_buf, int(k), ldx, ldy
+        self.features_nan_ = self.features_inf_ = False
+
+    def bind_results_buf(self, src_buf):
+        """a device buffer of an f32 per entry of the shard's rows"""
+        self.results_buf = src_buf
+
+    def run(self):
+        """Leaves stats_ = (rows on the short path, pieces on the piece path, feature tiles).  NaN values are refused under every
+        semiring, +-inf under (+,x) (ValueError): of A when its values scale, and of an X and Y this module uploaded."""
+        if self.plan_ is None or self.x_buf is None:
+            _fatal("SDDMMModule.run: send_matrix_host_to_device and send_features_host_to_device first")
+        op = self.semiring_.op
+        scaled = self.scaled_ and op != kLogicalAndOr
+        if op != kLogicalAndOr and ((scaled and np.isnan(self.values_).any()) or self.features_nan_ or
+                                    (op == kMulAdd and ((scaled and np.isinf(self.values_).any()) or self.features_inf_))):
+            raise ValueError("SDDMMModule.run: A, X or Y holds a NaN%s value" % (" or an infinite" if op == kMulAdd else ""))
+        self.stats_ = self.plan_.sddmm(self.a_val_buf if scaled else None, self.x_buf, self.y_buf, self.results_buf, self.k_, op,
+                                       self.semiring_.zero, self.ldx_, self.ldy_, stats=True)
+        self._finish(self.results_buf)
+
+    def send_results_device_to_host(self):
+        """-> an io.CSRMatrix with A's pattern and the scores as values: the shard's rows filled, the others empty"""
+        from . import io
+        m = self.csr_matrix_
+        r0, r1 = self.row_begin_, m.num_rows if self.row_end_ is None else self.row_end_
+        indptr = np.asarray(m.adj_indptr).astype(np.int64)[:m.num_rows + 1]
+        out_ptr = np.clip(indptr, indptr[r0], indptr[r1]) - indptr[r0]
+        scores = self.results_buf.read(np.float32, self.count_) if self.count_ else np.zeros(0, np.float32)
+        return io.CSRMatrix(m.num_rows, m.num_cols, scores, np.asarray(m.adj_indices[self.first_:self.first_ + self.count_]).astype(np.uint32),
+                            out_ptr.astype(np.uint32))
+
+
 class SpMSpVModule(BaseModule):
     def __init__(self, out_buf_len=0):
         super().__init__()
